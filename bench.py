@@ -3,6 +3,8 @@
 bf16, on N MI355X of one node (BASELINE.json metric, configs[1]).
 
     python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --full          # + every report below the headline
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -22,7 +24,17 @@ reference: the checkpointing modes, batch 1 / 2, the PADDING-FREE PACKED step it
 rank, decode. `--only NAME` times ONE of them as the whole run (what the per-point rocprofv3 kernel stats under
 profiles/ are collected with).
 
-Rank 0 prints ONE JSON line. Besides the contract fields it carries
+A plain run (no --full) sets up, warms up, times the K steps of the headline and prints the record: `alt`, `gpu_baseline`,
+`cpu_baseline` and `roofline` are null, and no HIP-event pairs are recorded inside its timed steps. --full adds all of them
+(the --alt-steps / --no-*-baseline / --roofline-every options only act under --full).
+
+--dump-outputs DIR (headline only): after the timed steps, what the last one computed, as float arrays for comparing two
+builds output for output -- DIR/loss.npy (float64 [1]: the loss of the last timed step) and DIR/lora_params_sample.npy
+(float32: a fixed, seeded sample of 2^22 of the trainable LoRA parameters as that step's AdamW update left them, taken from
+their concatenation in named_parameters() order). The same arguments give the same inputs (seeded weights, LoRA factors
+and token ids) on every run.
+
+Rank 0 prints ONE JSON line. Besides the contract fields, under --full it carries
   roofline     : the dominant kernel (the MFMA GEMM), ALGORITHMIC flops of its launches / their HIP-event
                  durations measured live in the timed region, against the 2.5 PFLOP/s dense bf16 peak
   cpu_baseline : the reference's torch-fp32 CPU composition timed on this box's host cores (bounded sample)
@@ -292,6 +304,21 @@ def hf_gpu_baseline(cfg, dev, B, T, r, steps=3, warmup=2, seed=0, checkpointing=
         torch.cuda.empty_cache()
 
 
+DUMP_SAMPLE = 1 << 22        # trainable parameters written by --dump-outputs: 16 MB of float32
+
+
+def dump_outputs(out_dir, model, last_loss):
+    """--dump-outputs: the loss of the last timed step and a fixed, seeded sample of the trainable (LoRA) parameters as its
+    optimizer step left them, indexed in their concatenation in named_parameters() order."""
+    import numpy as np
+    flat = torch.cat([p.detach().reshape(-1).float() for _, p in model.named_parameters() if p.requires_grad])
+    n = flat.numel()
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:min(n, DUMP_SAMPLE)].sort().values
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([last_loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, "lora_params_sample.npy"), flat[idx.to(flat.device)].cpu().numpy().astype(np.float32))
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` with N > 1 and no torchrun environment: become the launcher. One process per GPU under
     torch.distributed.run on 127.0.0.1 (the driver's own command shape); the ranks find RANK / LOCAL_RANK / WORLD_SIZE in
@@ -366,6 +393,11 @@ def main():
                          "when every step is instrumented (profiles/r03final_step_sequence.csv: all 3.5 ms of idle gaps of a "
                          "step sit before a GEMM or before the kernel that follows one). 1 = every step")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other operating points (alt), the stock-HF GPU baseline, the CPU baseline "
+                         "and the GEMM / attention roofline sampled inside the timed steps. Off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/*.npy (the headline run only)")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -386,6 +418,12 @@ def main():
     if world > 1 and os.environ.get("BENCH_ALT_MULTI", "0") != "1":
         a.alt_steps = 0            # the other operating points are a 1-GPU report; a scaling run times the primary only
     if a.only != "primary":
+        if a.dump_outputs:
+            raise SystemExit("bench.py --dump-outputs writes the headline's outputs: not with --only")
+        a.alt_steps = 0
+        a.no_cpu_baseline = a.no_gpu_baseline = True
+    elif not a.full:
+        # a plain run: the headline alone (no event pairs in its timed steps either: the roofline is a --full report)
         a.alt_steps = 0
         a.no_cpu_baseline = a.no_gpu_baseline = True
     rank = int(os.environ.get("RANK", "0"))
@@ -418,7 +456,8 @@ def main():
     from unsloth_amd.trainer import make_optimizer, training_step
 
     timer = GemmTimer()
-    timer.install()
+    if a.full or a.only != "primary":
+        timer.install()
 
     def sync():
         if world > 1:
@@ -743,12 +782,14 @@ def main():
     # the PRIMARY measurement first, on the freshly initialised model (loss_first_last starts at ~ln V); the other operating
     # points afterwards (their warm-up / timing steps keep training the same adapters, which no longer matters)
     batches, n_items = make_batches(B)
-    if arena is not None:
+    if arena is not None and a.full:
         arena.timing = True              # events around the waits of finish(): what the overlap with the backward did not hide
     dt, peak, loss_vals, gs = measure(GC_MODE[a.gc], a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, loss_vals[-1])
     primary_per_rank = list(last_timing.get("per_rank_ms_per_step", []))
     dp_diag = None
-    if arena is not None:
+    if arena is not None and a.full:
         # (warm-up steps' waits are in the sum too: divide by all the steps that ran)
         exposed = arena.exposed_ms() / max(1, a.steps + a.warmup)
         arena.timing = False
@@ -996,7 +1037,7 @@ def main():
                                           "peak_vram_ratio": round(ours["peak_vram_gb"] / hgc["peak_vram_gb"], 2)}
         rec = {
             "metric": "train tokens/sec, Llama-3-8B QLoRA (NF4) r=16 seq2048 bf16", "value": round(tokens / dt, 1),
-            "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "full": a.full,
             "ms_per_step": round(ms_step, 2), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "bf16", "data": "synthetic (random-init Llama-3-8B-shaped weights -> NF4, "
             "uniform random token ids)",

@@ -47,3 +47,31 @@ def test_world_size_mismatch_is_an_error():
     r = _run(["--gpus", "4"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0", "BENCH_DRY_LAUNCH": "1"}, drop=())
     assert r.returncode == 2 and r.stdout.strip() == ""
     assert "WORLD_SIZE=2" in r.stderr
+
+
+def test_dump_outputs_writes_seeded_float_arrays(tmp_path):
+    """--dump-outputs: the last step's loss and a fixed, seeded sample of the trainable parameters, float arrays only,
+    the same sample on every call and far below 64 MB at the headline's 41.9 M LoRA parameters."""
+    import numpy as np
+    import torch
+    env = dict(os.environ)
+    try:
+        import bench                                    # sets a HIP runtime variable at import: keep it out of this process
+    finally:
+        os.environ.clear()
+        os.environ.update(env)
+    m = torch.nn.Sequential(torch.nn.Linear(64, 32), torch.nn.Linear(32, 8))
+    m[1].weight.requires_grad_(False)
+    n_train = sum(p.numel() for p in m.parameters() if p.requires_grad)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), m, 2.5)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["lora_params_sample.npy", "loss.npy"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [2.5]
+    sample = np.load(tmp_path / "a" / "lora_params_sample.npy")
+    flat = torch.cat([p.detach().reshape(-1) for p in m.parameters() if p.requires_grad]).numpy()
+    assert sample.shape == (min(n_train, bench.DUMP_SAMPLE),) and np.isin(sample, flat).all()
+    assert bench.DUMP_SAMPLE * 4 + 8 < 64 * 2**20

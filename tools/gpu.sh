@@ -5,7 +5,7 @@
 #   test[:EXPR]        pytest -m gpu (optionally -k EXPR; spaces in EXPR as '+')
 #   testfile:PATH      pytest PATH -m gpu
 #   smoke              __graft_entry__.smoke()
-#   bench[:ARGS]       the driver's bench command (ARGS: extra flags, '+' for spaces) -> bench_TAG.json
+#   bench[:ARGS]       bench.py --full (ARGS: extra flags, '+' for spaces) -> bench_TAG.json
 #   only:POINT[:K]     bench.py --only POINT --steps K (default 4), JSON -> bench_TAG_POINT.json
 #   prof:POINT[:K]     rocprofv3 --kernel-trace over `bench.py --only POINT` -> TAG_POINT_kernel_stats.csv (+ step sequence)
 #   trace:POINT        the same with the HIP/RCCL stream timeline kept: TAG_POINT_overlap.csv (kernel start/end per stream)
@@ -51,7 +51,7 @@ for step in "$@"; do
     smoke)
       timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 ;;
     bench)
-      timeout 1200 python bench.py $(unplus "$arg") > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+      timeout 1200 python bench.py --full $(unplus "$arg") > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
       echo "[$step] rc=$? ($SECONDS s)"; brief $OUT/bench_$TAG.json; tail -3 $OUT/bench_$TAG.err ;;
     only)
       P=${arg%%:*}; K=4; [ "$P" != "$arg" ] && K=${arg#*:}
