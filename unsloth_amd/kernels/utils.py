@@ -176,10 +176,30 @@ def _use_gemm256(M, K, Ns):
     return ((M + 255) // 256) * cols >= GEMM256_MIN_TILES or ((M + 127) // 128) * cols >= GEMM256_MIN_TILES
 
 
+# The 256-tile kernels address every operand through 32-bit byte offsets from its base (csrc/gemm256.hip refuses a launch
+# whose A, XK or B would span 4 GiB). A per-row operand past that span -- A = h or [df | de] with ld = 2 I + 64 from ~57 K
+# tokens at Qwen2-7B widths, ~75 K at Llama-3-8B's -- is launched as row chunks (NT / NN) or contraction chunks (TN,
+# dense_dw) that each stay below it. The limit is applied conservatively to every kernel of _launch_gemm: the 128-tile
+# uamd_gemm_nt / uamd_gemm_nt_nf4 (64-bit addressing, no span guard) and the fp32 XA only the 128-tile prologue reads are
+# counted too -- at most a few extra launches at sizes no 128-tile launch reaches. A weight B past the span is not split
+# (still refused by the kernel's guard). Module attribute: tests lower it to force chunking at small shapes.
+GEMM_SPAN_LIMIT = 1 << 32
+
+
+def _chunk_rows(row_bytes, align):
+    """The most rows, a multiple of `align`, whose operand spans less than GEMM_SPAN_LIMIT bytes."""
+    rows = (GEMM_SPAN_LIMIT - 1) // max(row_bytes, 1) // align * align
+    if rows < align:
+        raise RuntimeError(f"unsloth_amd: a GEMM operand row of {row_bytes} bytes leaves no whole {align}-row chunk "
+                           f"below the {GEMM_SPAN_LIMIT}-byte span limit")
+    return rows
+
+
 def _launch_gemm(X2d, groups, nf4, accumulate=False, nn=False):
     """`nn`: the groups' B (and rank-block BK) are [K, N] row-major, C = A @ B (uamd_gemm_nn_256); callers check
-    `_use_gemm256` first -- only the 256-tile kernel family has that form."""
-    arr = (GemmGroup * len(groups))(*groups)
+    `_use_gemm256` first -- only the 256-tile kernel family has that form.
+    A launch whose per-row operands (A, the rank block XK, the fp32 XA) span GEMM_SPAN_LIMIT bytes or more is issued as
+    row chunks of a multiple of 256 rows (whole tiles of every kernel); below the limit it is exactly one launch."""
     L = _lib.lib()
     M, K = X2d.shape
     # a LoRA term given as (fp32 XA, LB) -- no rank block -- is the register prologue of the 128 x 128 kernels only
@@ -192,10 +212,35 @@ def _launch_gemm(X2d, groups, nf4, accumulate=False, nn=False):
         fn, name = L.uamd_gemm_nt_256, "uamd_gemm_nt_256"
     else:
         fn, name = L.uamd_gemm_nt, "uamd_gemm_nt"
+    item = X2d.element_size()
+    row_bytes = X2d.stride(0) * item
+    for g in groups:
+        if g.lora_xk:
+            row_bytes = max(row_bytes, g.ld_xk * item)
+        if g.lora_xa:
+            row_bytes = max(row_bytes, g.ld_xa * 4)
+    if M * row_bytes < GEMM_SPAN_LIMIT:
+        spans = [(0, M)]
+    else:
+        step = _chunk_rows(row_bytes, 256)
+        spans = [(r0, min(step, M - r0)) for r0 in range(0, M, step)]
     with _lib.device_ctx(X2d):
-        rc = fn(_lib.ptr(X2d), X2d.stride(0), M, K, arr, len(groups), int(accumulate),
-                _lib.dtype_code(X2d.dtype), _lib.stream_of(X2d))
-    _lib.check(rc, name)
+        for r0, rows in spans:
+            chunk = []
+            for g in groups:
+                c = GemmGroup.from_buffer_copy(g)
+                if r0:                             # C is in the activation dtype; XA is fp32
+                    c.C += r0 * c.ldc * item
+                    if c.lora_xk:
+                        c.lora_xk += r0 * c.ld_xk * item
+                    if c.lora_xa:
+                        c.lora_xa += r0 * c.ld_xa * 4
+                chunk.append(c)
+            arr = (GemmGroup * len(chunk))(*chunk)
+            rc = fn(ctypes.c_void_p(X2d.data_ptr() + r0 * X2d.stride(0) * item), X2d.stride(0), rows, K, arr, len(chunk),
+                    int(accumulate),
+                    _lib.dtype_code(X2d.dtype), _lib.stream_of(X2d))
+            _lib.check(rc, name)
     return name
 
 
@@ -1045,8 +1090,8 @@ def dense_dw(dY, X, out=None, accumulate=False):
     """dW[out, in] (+)= dY[T, out]^T @ X[T, in]: the weight gradient of a trainable dense projection (full fine-tuning;
     torch.nn.Linear's `grad_output.t().mm(input)`). `dY` may be several projections' gradients side by side in one buffer
     ([T, sum out_g]: dQ | dK | dV as the attention backward writes them) -- then `out` is their stacked gradient
-    [sum out_g, in]. One uamd_gemm_tn_256 launch, both operands read in place; a token count that is not a multiple of
-    64 is zero-padded (zero rows add nothing)."""
+    [sum out_g, in]. One uamd_gemm_tn_256 launch (token chunks past GEMM_SPAN_LIMIT), both operands read in place; a token
+    count that is not a multiple of 64 is zero-padded (zero rows add nothing)."""
     dY2d, X2d = _rows2d(dY), _rows2d(X)
     _lib.require_gpu(X2d)
     T, N_out = dY2d.shape
@@ -1070,13 +1115,21 @@ def dense_dw(dY, X, out=None, accumulate=False):
         out = torch.empty((N_out, N_in), dtype=dtype, device=X2d.device)
         accumulate = False
     assert out.dtype == dtype and tuple(out.shape) == (N_out, N_in) and out.stride(1) == 1
-    g = _group(X2d, out, N_in, X2d.stride(0))
-    g.ldc = out.stride(0)
-    arr = (GemmGroup * 1)(g)
+    # both operands have the contracted token dimension as rows: past GEMM_SPAN_LIMIT the tokens go in chunks (multiples of
+    # 64), each launch after the first accumulating into `out` -- one more rounding of a 16-bit `out` per extra chunk
+    item = X2d.element_size()
+    row_bytes = max(dY2d.stride(0), X2d.stride(0)) * item
+    step = T if T * row_bytes < GEMM_SPAN_LIMIT else _chunk_rows(row_bytes, 64)
     with _lib.device_ctx(X2d):
-        rc = _lib.lib().uamd_gemm_tn_256(_lib.ptr(dY2d), dY2d.stride(0), N_out, T, arr, 1, int(bool(accumulate)),
-                                        _lib.dtype_code(dtype), _lib.stream_of(X2d))
-    _lib.check(rc, "uamd_gemm_tn_256")
+        for t0 in range(0, T, step):
+            g = _group(X2d, out, N_in, X2d.stride(0))
+            g.B += t0 * X2d.stride(0) * item
+            g.ldc = out.stride(0)
+            arr = (GemmGroup * 1)(g)
+            rc = _lib.lib().uamd_gemm_tn_256(ctypes.c_void_p(dY2d.data_ptr() + t0 * dY2d.stride(0) * item), dY2d.stride(0),
+                                            N_out, min(step, T - t0), arr, 1, int(bool(accumulate) or t0 > 0),
+                                            _lib.dtype_code(dtype), _lib.stream_of(X2d))
+            _lib.check(rc, "uamd_gemm_tn_256")
     return out
 
 
