@@ -230,3 +230,10 @@ def check(rc, name):
     if rc != 0:
         why = _ERR.get(rc, f"hipError {rc}")
         raise RuntimeError(f"unsloth_amd: {name} failed: {why} (code {rc})")
+
+
+def call(name, ref, *args):
+    """Launch the library's `name` with `args` on the device of tensor `ref`; raises when it reports an error."""
+    with device_ctx(ref):
+        rc = getattr(lib(), name)(*args)
+    check(rc, name)

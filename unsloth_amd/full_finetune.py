@@ -355,12 +355,10 @@ class ShardedAdamW(torch.optim.Optimizer):
                 if p32.is_cuda:
                     from . import _lib
                     es = g16.element_size()
-                    with _lib.device_ctx(p32):
-                        rc = _lib.lib().uamd_adamw_shard(
-                            p32.data_ptr() + 4 * a, g16.data_ptr() + es * a, p16.data_ptr() + es * a, m.data_ptr() + 4 * a,
-                            v.data_ptr() + 4 * a, e - a, float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), wd, bc1,
-                            bc2_sqrt, float(grad_scale), _lib.dtype_code(g16.dtype), _lib.stream_of(p32))
-                    _lib.check(rc, "uamd_adamw_shard")
+                    _lib.call("uamd_adamw_shard", p32, p32.data_ptr() + 4 * a, g16.data_ptr() + es * a, p16.data_ptr() + es * a,
+                              m.data_ptr() + 4 * a, v.data_ptr() + 4 * a, e - a, float(grp["lr"]), float(b1), float(b2),
+                              float(grp["eps"]), wd, bc1, bc2_sqrt, float(grad_scale), _lib.dtype_code(g16.dtype),
+                              _lib.stream_of(p32))
                 else:                                    # host arithmetic of the gloo tests: the same formula in torch
                     g = g16[a:e].to(torch.float32) * grad_scale
                     p32[a:e].mul_(1.0 - grp["lr"] * wd)

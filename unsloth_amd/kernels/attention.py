@@ -213,16 +213,13 @@ def _forward_native(q, k, v, scale, band, causal=True):
     if not causal and band is None:
         band = document_band(T, batch=B, device=q.device)
     lo, hi = _band_ptrs(band, B, T, q.device)
-    with _lib.device_ctx(q):
-        if causal:
-            rc = _lib.lib().uamd_attn_fwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse),
-                                          _strides(q, k, v, o), B, T, Hq, Hk, D, Tp, float(scale), 1, lo,
-                                          _lib.dtype_code(q.dtype), _lib.stream_of(q))
-        else:
-            rc = _lib.lib().uamd_attn_fwd_band(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse),
-                                               _strides(q, k, v, o), B, T, Hq, Hk, D, Tp, float(scale), 0, lo, hi,
-                                               _lib.dtype_code(q.dtype), _lib.stream_of(q))
-    _lib.check(rc, "uamd_attn_fwd")
+    if causal:
+        _lib.call("uamd_attn_fwd", q, _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse), _strides(q, k, v, o),
+                  B, T, Hq, Hk, D, Tp, float(scale), 1, lo, _lib.dtype_code(q.dtype), _lib.stream_of(q))
+    else:
+        _lib.call("uamd_attn_fwd_band", q, _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse),
+                  _strides(q, k, v, o), B, T, Hq, Hk, D, Tp, float(scale), 0, lo, hi, _lib.dtype_code(q.dtype),
+                  _lib.stream_of(q))
     return o, lse[:, :, :T]
 
 
@@ -282,12 +279,9 @@ def _backward_native(do, q, k, v, o, lse, scale, band, causal=True):
     if not causal and band is None:
         band = document_band(T, batch=B, device=q.device)
     lo, hi = _band_ptrs(band, B, T, q.device)
-    with _lib.device_ctx(q):
-        rc = _lib.lib().uamd_attn_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(do),
-                                      _lib.ptr(lse), _lib.ptr(dq), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(delta),
-                                      _strides(q, k, v, o, do, dq, dk, dv), B, T, Hq, Hk, D, Tp, float(scale),
-                                      1 if causal else 0, lo, hi, _lib.dtype_code(q.dtype), _lib.stream_of(q))
-    _lib.check(rc, "uamd_attn_bwd")
+    _lib.call("uamd_attn_bwd", q, _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(do), _lib.ptr(lse), _lib.ptr(dq),
+              _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(delta), _strides(q, k, v, o, do, dq, dk, dv), B, T, Hq, Hk, D, Tp,
+              float(scale), 1 if causal else 0, lo, hi, _lib.dtype_code(q.dtype), _lib.stream_of(q))
     return dq, dk, dv
 
 

@@ -21,23 +21,17 @@ def _ce_forward(logits2d, labels, softcap, scale):
     n_rows, vocab = logits2d.shape
     losses = torch.empty(n_rows, dtype=torch.float32, device=logits2d.device)
     lse = torch.empty(n_rows, dtype=torch.float32, device=logits2d.device)
-    with _lib.device_ctx(logits2d):
-        rc = _lib.lib().uamd_cross_entropy_forward(
-            _lib.ptr(logits2d), logits2d.stride(0), _lib.ptr(losses), _lib.ptr(lse), _lib.ptr(labels),
-            n_rows, vocab, float(softcap), float(scale), _lib.dtype_code(logits2d.dtype),
-            _lib.stream_of(logits2d))
-    _lib.check(rc, "uamd_cross_entropy_forward")
+    _lib.call("uamd_cross_entropy_forward", logits2d, _lib.ptr(logits2d), logits2d.stride(0), _lib.ptr(losses), _lib.ptr(lse),
+              _lib.ptr(labels), n_rows, vocab, float(softcap), float(scale), _lib.dtype_code(logits2d.dtype),
+              _lib.stream_of(logits2d))
     return losses, lse
 
 
 def _ce_backward_(logits2d, dlosses, lse, labels, softcap, scale):
     n_rows, vocab = logits2d.shape
-    with _lib.device_ctx(logits2d):
-        rc = _lib.lib().uamd_cross_entropy_backward(
-            _lib.ptr(logits2d), logits2d.stride(0), _lib.ptr(dlosses), dlosses.stride(0), _lib.ptr(lse),
-            _lib.ptr(labels), n_rows, vocab, float(softcap), float(scale),
-            _lib.dtype_code(logits2d.dtype), _lib.stream_of(logits2d))
-    _lib.check(rc, "uamd_cross_entropy_backward")
+    _lib.call("uamd_cross_entropy_backward", logits2d, _lib.ptr(logits2d), logits2d.stride(0), _lib.ptr(dlosses),
+              dlosses.stride(0), _lib.ptr(lse), _lib.ptr(labels), n_rows, vocab, float(softcap), float(scale),
+              _lib.dtype_code(logits2d.dtype), _lib.stream_of(logits2d))
     return logits2d
 
 
@@ -165,7 +159,7 @@ def fused_ce_chunk_rows(T, V, itemsize, device, target_gb=None):
 def _nn_ok(rows, V, H):
     """d(hidden) = dlogits [rows, V] @ W [V, H] can contract over W's ROWS in place (NN form of the 256-tile GEMM):
     no transposed copy of the lm_head (1.05 GB at Llama-3's vocabulary) has to exist."""
-    return _u.NN_DX and V % 64 == 0 and H % 8 == 0 and _u._use_gemm256(rows, V, [H])
+    return V % 64 == 0 and H % 8 == 0 and _u._use_gemm256(rows, V, [H])
 
 
 def _dhidden(chunk, dlogits, weight, weight_t, out):

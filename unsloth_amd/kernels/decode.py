@@ -147,10 +147,8 @@ def gemv(x, groups, nf4, blocksize=64, pro=None):
         e.bias = bias.data_ptr() if bias is not None else None
         e.N, e.y_f32 = N, int(y_f32)
     if pro is None:
-        with _lib.device_ctx(ref):
-            rc = _lib.lib().uamd_gemv(_lib.ptr(x), K, arr, len(groups), int(bool(nf4)), int(blocksize),
-                                      _lib.dtype_code(dtype), _lib.stream_of(ref))
-        _lib.check(rc, "uamd_gemv")
+        _lib.call("uamd_gemv", ref, _lib.ptr(x), K, arr, len(groups), int(bool(nf4)), int(blocksize), _lib.dtype_code(dtype),
+                  _lib.stream_of(ref))
         return outs
     P = GemvPrologue()
     P.mode = int(pro.get("mode", 0))
@@ -180,10 +178,8 @@ def gemv(x, groups, nf4, blocksize=64, pro=None):
         P.sync, P.tag = ho.ws.data_ptr(), tag
         P.tag_dev = tag_dev.data_ptr() if tag_dev is not None else None
         keep += [ho.ws, tag_dev]
-    with _lib.device_ctx(ref):
-        rc = _lib.lib().uamd_gemv_fused(_lib.ptr(x) if x is not None else None, K, arr, len(groups), int(bool(nf4)),
-                                        int(blocksize), _lib.dtype_code(dtype), _lib.stream_of(ref), ctypes.byref(P))
-    _lib.check(rc, "uamd_gemv_fused")
+    _lib.call("uamd_gemv_fused", ref, _lib.ptr(x) if x is not None else None, K, arr, len(groups), int(bool(nf4)),
+              int(blocksize), _lib.dtype_code(dtype), _lib.stream_of(ref), ctypes.byref(P))
     return outs
 
 
@@ -267,13 +263,10 @@ def rope_kv_append(qkv, cos, sin, kv_len, k_cache, v_cache, Hq, Hk, D, rope_pos=
     B = qkv.shape[0]
     assert qkv.stride(1) == 1 and k_cache.is_contiguous() and v_cache.is_contiguous() and kv_len.dtype == torch.int32
     assert cos.stride(1) == 1 and sin.stride() == cos.stride() and cos.dtype == qkv.dtype
-    with _lib.device_ctx(qkv):
-        rc = _lib.lib().uamd_rope_kv_append(
-            _lib.ptr(qkv), qkv.stride(0), _lib.ptr(cos), _lib.ptr(sin), cos.stride(0), _lib.ptr(kv_len),
-            _lib.ptr(rope_pos) if rope_pos is not None else None, _lib.ptr(k_cache), _lib.ptr(v_cache),
-            k_cache.stride(0), k_cache.stride(1), B, Hq, Hk, D, k_cache.shape[2], _lib.dtype_code(qkv.dtype),
-            _lib.stream_of(qkv))
-    _lib.check(rc, "uamd_rope_kv_append")
+    _lib.call("uamd_rope_kv_append", qkv, _lib.ptr(qkv), qkv.stride(0), _lib.ptr(cos), _lib.ptr(sin), cos.stride(0),
+              _lib.ptr(kv_len), _lib.ptr(rope_pos) if rope_pos is not None else None, _lib.ptr(k_cache), _lib.ptr(v_cache),
+              k_cache.stride(0), k_cache.stride(1), B, Hq, Hk, D, k_cache.shape[2], _lib.dtype_code(qkv.dtype),
+              _lib.stream_of(qkv))
 
 
 def attn_decode(q, k_cache, v_cache, kv_len, out, partials, split_keys, scale, len_add=1, window=0):
@@ -282,12 +275,9 @@ def attn_decode(q, k_cache, v_cache, kv_len, out, partials, split_keys, scale, l
     Hq = partials.shape[1]
     nsplit = partials.shape[2]
     assert nsplit * split_keys >= S_max and q.stride(1) == 1 and out.stride(1) == 1
-    with _lib.device_ctx(q):
-        rc = _lib.lib().uamd_attn_decode(
-            _lib.ptr(q), q.stride(0), _lib.ptr(k_cache), _lib.ptr(v_cache), k_cache.stride(0), k_cache.stride(1),
-            _lib.ptr(kv_len), int(len_add), _lib.ptr(partials), _lib.ptr(out), out.stride(0), B, Hq, Hk, D, nsplit,
-            int(split_keys), int(window), float(scale), _lib.dtype_code(q.dtype), _lib.stream_of(q))
-    _lib.check(rc, "uamd_attn_decode")
+    _lib.call("uamd_attn_decode", q, _lib.ptr(q), q.stride(0), _lib.ptr(k_cache), _lib.ptr(v_cache), k_cache.stride(0),
+              k_cache.stride(1), _lib.ptr(kv_len), int(len_add), _lib.ptr(partials), _lib.ptr(out), out.stride(0), B, Hq, Hk, D,
+              nsplit, int(split_keys), int(window), float(scale), _lib.dtype_code(q.dtype), _lib.stream_of(q))
     return out
 
 
@@ -314,14 +304,11 @@ def attn_decode_fused(qkv, cos, sin, kv_len, k_cache, v_cache, out, partials, co
     assert counters.dtype == torch.int32 and counters.numel() >= B * Hk
     assert cos.stride(1) == 1 and sin.stride() == cos.stride() and cos.dtype == qkv.dtype
     tag, tag_dev = partials.tags(site)
-    with _lib.device_ctx(qkv):
-        rc = _lib.lib().uamd_attn_decode_fused(
-            _lib.ptr(qkv), qkv.stride(0), _lib.ptr(cos), _lib.ptr(sin), cos.stride(0), _lib.ptr(kv_len),
-            _lib.ptr(rope_pos) if rope_pos is not None else None, _lib.ptr(k_cache), _lib.ptr(v_cache), k_cache.stride(0),
-            k_cache.stride(1), partials.ws.data_ptr(), _lib.ptr(counters), _lib.ptr(out), out.stride(0), B, Hq, Hk, D, S_max,
-            nsplit, int(split_keys), int(window), float(scale), tag, tag_dev.data_ptr() if tag_dev is not None else None,
-            _lib.dtype_code(qkv.dtype), _lib.stream_of(qkv))
-    _lib.check(rc, "uamd_attn_decode_fused")
+    _lib.call("uamd_attn_decode_fused", qkv, _lib.ptr(qkv), qkv.stride(0), _lib.ptr(cos), _lib.ptr(sin), cos.stride(0),
+              _lib.ptr(kv_len), _lib.ptr(rope_pos) if rope_pos is not None else None, _lib.ptr(k_cache), _lib.ptr(v_cache),
+              k_cache.stride(0), k_cache.stride(1), partials.ws.data_ptr(), _lib.ptr(counters), _lib.ptr(out), out.stride(0),
+              B, Hq, Hk, D, S_max, nsplit, int(split_keys), int(window), float(scale), tag,
+              tag_dev.data_ptr() if tag_dev is not None else None, _lib.dtype_code(qkv.dtype), _lib.stream_of(qkv))
     return out
 
 
@@ -335,8 +322,6 @@ def argmax_f32(logits, out=None, ws=None):
     if ws is None:
         ws = (torch.empty(rows * 64, dtype=torch.float32, device=logits.device),
               torch.empty(rows * 64, dtype=torch.long, device=logits.device))
-    with _lib.device_ctx(logits):
-        rc = _lib.lib().uamd_argmax_f32(_lib.ptr(logits), rows, n, _lib.ptr(ws[0]), _lib.ptr(ws[1]), _lib.ptr(out),
-                                        _lib.stream_of(logits))
-    _lib.check(rc, "uamd_argmax_f32")
+    _lib.call("uamd_argmax_f32", logits, _lib.ptr(logits), rows, n, _lib.ptr(ws[0]), _lib.ptr(ws[1]), _lib.ptr(out),
+              _lib.stream_of(logits))
     return out

@@ -97,9 +97,6 @@ _ACT_NAMES = {swiglu_fg_kernel: "swiglu", swiglu_DWf_DW_dfg_kernel: "swiglu",
               geglu_approx_forward_kernel: "geglu_approx", geglu_approx_backward_kernel: "geglu_approx"}
 
 
-MERGE_GATE_UP = True          # module attribute (tests flip it); the environment switch went with its A/B (profiles/r06_gemm_row_padding.jsonl)
-
-
 def _gate_up(X, gate, up, return_xa=False):
     """(e, g) = X @ W_gate^T, X @ W_up^T (+ LoRA) as the two column halves of ONE row-padded buffer (utils.alloc_rows): the
     in-place activation backward then leaves df | de side by side, so dX = [df | de] @ [W_up; W_gate] is ONE GEMM over the
@@ -108,7 +105,7 @@ def _gate_up(X, gate, up, return_xa=False):
     4 KiB pages."""
     outs = None
     widths = [(q.shape[0] if q is not None else W.shape[0]) for (W, q, *_rest) in (gate, up)]
-    if (MERGE_GATE_UP and X.is_cuda and X.dtype in (torch.bfloat16, torch.float16) and widths[0] == widths[1]
+    if (X.is_cuda and X.dtype in (torch.bfloat16, torch.float16) and widths[0] == widths[1]
             and widths[0] % 64 == 0 and all(len(p) <= 5 or p[5] is None for p in (gate, up))):
         M = X.numel() // X.shape[-1]
         eg = alloc_rows(M, 2 * widths[0], X.dtype, X.device)

@@ -26,11 +26,9 @@ class Fast_Layernorm(torch.autograd.Function):
         Y = torch.empty((n_rows, dim), dtype=X.dtype, device=X.device)
         r = torch.empty(n_rows, dtype=torch.float32, device=X.device)
         mu = torch.empty(n_rows, dtype=torch.float32, device=X.device)
-        with _lib.device_ctx(X2):
-            rc = _lib.lib().uamd_layernorm_fwd(_lib.ptr(X2), _lib.ptr(Wc), _lib.ptr(bc), _lib.ptr(Y), _lib.ptr(r),
-                                               _lib.ptr(mu), n_rows, dim, X2.stride(0), Y.stride(0), float(eps),
-                                               _lib.dtype_code(X.dtype), _lib.dtype_code(Wc.dtype), _lib.stream_of(X2))
-        _lib.check(rc, "uamd_layernorm_fwd")
+        _lib.call("uamd_layernorm_fwd", X2, _lib.ptr(X2), _lib.ptr(Wc), _lib.ptr(bc), _lib.ptr(Y), _lib.ptr(r), _lib.ptr(mu),
+                  n_rows, dim, X2.stride(0), Y.stride(0), float(eps), _lib.dtype_code(X.dtype), _lib.dtype_code(Wc.dtype),
+                  _lib.stream_of(X2))
         ctx.save_for_backward(X2, Wc, r, mu)
         return Y.view(*shape)
 
@@ -42,11 +40,8 @@ class Fast_Layernorm(torch.autograd.Function):
         dY2 = dY.reshape(-1, dim)
         if dY2.stride(1) != 1 or dY2.dtype != X2.dtype:
             dY2 = dY2.to(X2.dtype).contiguous()
-        with _lib.device_ctx(dY2):
-            rc = _lib.lib().uamd_layernorm_bwd(_lib.ptr(dY2), _lib.ptr(X2), _lib.ptr(W), _lib.ptr(r), _lib.ptr(mu),
-                                               dY2.shape[0], dim, dY2.stride(0), X2.stride(0),
-                                               _lib.dtype_code(dY2.dtype), _lib.dtype_code(W.dtype), _lib.stream_of(dY2))
-        _lib.check(rc, "uamd_layernorm_bwd")
+        _lib.call("uamd_layernorm_bwd", dY2, _lib.ptr(dY2), _lib.ptr(X2), _lib.ptr(W), _lib.ptr(r), _lib.ptr(mu), dY2.shape[0],
+                  dim, dY2.stride(0), X2.stride(0), _lib.dtype_code(dY2.dtype), _lib.dtype_code(W.dtype), _lib.stream_of(dY2))
         return dY2.view(*shape), None, None, None          # dX written over dY (layernorm.py:104, :161-163)
 
 

@@ -13,9 +13,8 @@ class Fast_QuickGELU(torch.autograd.Function):
         _lib.require_gpu(X)
         Xc = X if X.is_contiguous() else X.contiguous()
         Y = torch.empty_like(Xc)
-        with _lib.device_ctx(Xc):
-            rc = _lib.lib().uamd_quick_gelu_forward(_lib.ptr(Xc), _lib.ptr(Y), Xc.numel(), _lib.dtype_code(Xc.dtype), _lib.stream_of(Xc))
-        _lib.check(rc, "uamd_quick_gelu_forward")
+        _lib.call("uamd_quick_gelu_forward", Xc, _lib.ptr(Xc), _lib.ptr(Y), Xc.numel(), _lib.dtype_code(Xc.dtype),
+                  _lib.stream_of(Xc))
         ctx.save_for_backward(Xc)
         return Y.view(X.shape)
 
@@ -23,9 +22,8 @@ class Fast_QuickGELU(torch.autograd.Function):
     def backward(ctx, dY):
         (X,) = ctx.saved_tensors
         d = dY if (dY.is_contiguous() and dY.dtype == X.dtype) else dY.to(X.dtype).contiguous()
-        with _lib.device_ctx(d):
-            rc = _lib.lib().uamd_quick_gelu_backward(_lib.ptr(X), _lib.ptr(d), X.numel(), _lib.dtype_code(X.dtype), _lib.stream_of(d))
-        _lib.check(rc, "uamd_quick_gelu_backward")
+        _lib.call("uamd_quick_gelu_backward", d, _lib.ptr(X), _lib.ptr(d), X.numel(), _lib.dtype_code(X.dtype),
+                  _lib.stream_of(d))
         return d.view(dY.shape)
 
 

@@ -25,11 +25,9 @@ def rms_fwd(X, W, eps, gemma=False):
     Y = torch.empty((n_rows, n_cols), dtype=X2.dtype, device=X2.device)
     r = torch.empty(n_rows, dtype=torch.float32, device=X2.device)
     W = W.contiguous()
-    with _lib.device_ctx(X2):
-        rc = _lib.lib().uamd_rms_layernorm_fwd(
-            _lib.ptr(X2), _lib.ptr(W), _lib.ptr(Y), _lib.ptr(r), n_rows, n_cols, X2.stride(0), Y.stride(0),
-            float(eps), int(bool(gemma)), _lib.dtype_code(X2.dtype), _lib.dtype_code(W.dtype), _lib.stream_of(X2))
-    _lib.check(rc, "uamd_rms_layernorm_fwd")
+    _lib.call("uamd_rms_layernorm_fwd", X2, _lib.ptr(X2), _lib.ptr(W), _lib.ptr(Y), _lib.ptr(r), n_rows, n_cols,
+              X2.stride(0), Y.stride(0), float(eps), int(bool(gemma)), _lib.dtype_code(X2.dtype), _lib.dtype_code(W.dtype),
+              _lib.stream_of(X2))
     return Y, r
 
 
@@ -42,12 +40,9 @@ def add_rms_fwd(X, residual, W, eps):
     Y = torch.empty((n_rows, dim), dtype=X2.dtype, device=X2.device)
     r = torch.empty(n_rows, dtype=torch.float32, device=X2.device)
     W = W.contiguous()
-    with _lib.device_ctx(X2):
-        rc = _lib.lib().uamd_add_rms_layernorm_fwd(
-            _lib.ptr(X2), _lib.ptr(R2), _lib.ptr(W), _lib.ptr(H), _lib.ptr(Y), _lib.ptr(r), n_rows, dim,
-            X2.stride(0), R2.stride(0), H.stride(0), Y.stride(0), float(eps), _lib.dtype_code(X2.dtype),
-            _lib.dtype_code(W.dtype), _lib.stream_of(X2))
-    _lib.check(rc, "uamd_add_rms_layernorm_fwd")
+    _lib.call("uamd_add_rms_layernorm_fwd", X2, _lib.ptr(X2), _lib.ptr(R2), _lib.ptr(W), _lib.ptr(H), _lib.ptr(Y),
+              _lib.ptr(r), n_rows, dim, X2.stride(0), R2.stride(0), H.stride(0), Y.stride(0), float(eps),
+              _lib.dtype_code(X2.dtype), _lib.dtype_code(W.dtype), _lib.stream_of(X2))
     return H, Y, r
 
 
@@ -63,12 +58,9 @@ def rms_dw(dY, X, r, W, out=None, accumulate=False):
     col_blocks = (dim // (16 // dY2.element_size()) + 255) // 256
     chunks = max(1, min((2048 + col_blocks - 1) // col_blocks, (n_rows + 7) // 8))
     ws = _nf4.scratch(dY2.device, chunks * dim, torch.float32, slot=41)
-    with _lib.device_ctx(dY2):
-        rc = _lib.lib().uamd_rms_layernorm_dw(
-            _lib.ptr(dY2), _lib.ptr(X2), _lib.ptr(r), _lib.ptr(out), _lib.ptr(ws), ws.numel(), n_rows, dim,
-            dY2.stride(0), X2.stride(0), int(bool(accumulate)), _lib.dtype_code(dY2.dtype), _lib.dtype_code(W.dtype),
-            _lib.stream_of(dY2))
-    _lib.check(rc, "uamd_rms_layernorm_dw")
+    _lib.call("uamd_rms_layernorm_dw", dY2, _lib.ptr(dY2), _lib.ptr(X2), _lib.ptr(r), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+              n_rows, dim, dY2.stride(0), X2.stride(0), int(bool(accumulate)), _lib.dtype_code(dY2.dtype),
+              _lib.dtype_code(W.dtype), _lib.stream_of(dY2))
     return out
 
 
@@ -87,71 +79,42 @@ def _weight_grad(dY, X, r, W, needed):
     return rms_dw(dY, X, r, W)
 
 
-def rms_bwd_(dY, H, W, r, dH=None):
-    """dX = rmsnorm_backward(dY; H, W, r) (+ dH, the gradient reaching H from the residual path), written IN PLACE
-    over dY (rms_layernorm.py:218) and returned. Llama-style norm."""
-    dY2 = _rows(dY)
+def rms_bwd_(dY, H, W, r, dH=None, gemma=False):
+    """dX = rmsnorm_backward(dY; H, W, r) (+ dH, the gradient reaching H from the residual path), [rows, dim]. Llama-style
+    norm: written IN PLACE over dY (rms_layernorm.py:218); `gemma`: the (1 + W) form, into a fresh tensor (:92-95)."""
+    dY2, H2 = _rows(dY), _rows(H)
     n_rows, dim = dY2.shape
-    H2 = _rows(H)
-    with _lib.device_ctx(dY2):
-        if dH is None:
-            rc = _lib.lib().uamd_rms_layernorm_bwd(
-                _lib.ptr(dY2), _lib.ptr(dY2), _lib.ptr(H2), _lib.ptr(W), _lib.ptr(r), n_rows, dim, dY2.stride(0),
-                dY2.stride(0), H2.stride(0), 0, _lib.dtype_code(dY2.dtype), _lib.dtype_code(W.dtype),
-                _lib.stream_of(dY2))
-            _lib.check(rc, "uamd_rms_layernorm_bwd")
-        else:
-            dH2 = _rows(dH)
-            rc = _lib.lib().uamd_add_rms_layernorm_bwd(
-                _lib.ptr(dY2), _lib.ptr(dH2), _lib.ptr(dY2), _lib.ptr(H2), _lib.ptr(W), _lib.ptr(r), n_rows, dim,
-                dY2.stride(0), dH2.stride(0), dY2.stride(0), H2.stride(0), _lib.dtype_code(dY2.dtype),
-                _lib.dtype_code(W.dtype), _lib.stream_of(dY2))
-            _lib.check(rc, "uamd_add_rms_layernorm_bwd")
-    return dY2
+    dX = torch.empty_like(dY2) if gemma else dY2
+    if dH is None:
+        _lib.call("uamd_rms_layernorm_bwd", dY2, _lib.ptr(dY2), _lib.ptr(dX), _lib.ptr(H2), _lib.ptr(W), _lib.ptr(r), n_rows,
+                  dim, dY2.stride(0), dX.stride(0), H2.stride(0), int(gemma), _lib.dtype_code(dY2.dtype),
+                  _lib.dtype_code(W.dtype), _lib.stream_of(dY2))
+    else:
+        assert not gemma
+        dH2 = _rows(dH)
+        _lib.call("uamd_add_rms_layernorm_bwd", dY2, _lib.ptr(dY2), _lib.ptr(dH2), _lib.ptr(dY2), _lib.ptr(H2), _lib.ptr(W),
+                  _lib.ptr(r), n_rows, dim, dY2.stride(0), dH2.stride(0), dY2.stride(0), H2.stride(0),
+                  _lib.dtype_code(dY2.dtype), _lib.dtype_code(W.dtype), _lib.stream_of(dY2))
+    return dX
 
 
 class Fast_RMS_Layernorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, W, eps, gemma=False):
-        _lib.require_gpu(X, W)
-        shape = X.shape
-        dim = shape[-1]
-        X = X.reshape(-1, dim)
-        if X.stride(1) != 1:
-            X = X.contiguous()
-        n_rows, n_cols = X.shape
-        Y = torch.empty((n_rows, n_cols), dtype=X.dtype, device=X.device)
-        r = torch.empty(n_rows, dtype=torch.float32, device=X.device)
-        W = W.contiguous()
-        with _lib.device_ctx(X):
-            rc = _lib.lib().uamd_rms_layernorm_fwd(
-                _lib.ptr(X), _lib.ptr(W), _lib.ptr(Y), _lib.ptr(r), n_rows, n_cols, X.stride(0),
-                Y.stride(0), float(eps), int(bool(gemma)), _lib.dtype_code(X.dtype),
-                _lib.dtype_code(W.dtype), _lib.stream_of(X))
-        _lib.check(rc, "uamd_rms_layernorm_fwd")
+        X2, W = _rows(X), W.contiguous()
+        Y, r = rms_fwd(X2, W, eps, gemma)
         ctx.eps = eps
         ctx.GEMMA = bool(gemma)
-        ctx.save_for_backward(X, W, r)
-        return Y.view(*shape)
+        ctx.save_for_backward(X2, W, r)
+        return Y.view(*X.shape)
 
     @staticmethod
     def backward(ctx, dY):
-        shape = dY.shape
-        dim = shape[-1]
-        dY = dY.reshape(-1, dim)
-        if dY.stride(1) != 1:
-            dY = dY.contiguous()
+        dY2 = _rows(dY)
         X, W, r = ctx.saved_tensors
-        n_rows, n_cols = dY.shape
-        dW = _weight_grad(dY, X, r, W, ctx.needs_input_grad[1])
-        dX = torch.empty_like(dY) if ctx.GEMMA else dY      # rms_layernorm.py:218
-        with _lib.device_ctx(dY):
-            rc = _lib.lib().uamd_rms_layernorm_bwd(
-                _lib.ptr(dY), _lib.ptr(dX), _lib.ptr(X), _lib.ptr(W), _lib.ptr(r), n_rows, n_cols,
-                dY.stride(0), dX.stride(0), X.stride(0), int(ctx.GEMMA), _lib.dtype_code(dY.dtype),
-                _lib.dtype_code(W.dtype), _lib.stream_of(dY))
-        _lib.check(rc, "uamd_rms_layernorm_bwd")
-        return dX.view(*shape), dW, None, None
+        dW = _weight_grad(dY2, X, r, W, ctx.needs_input_grad[1])       # (before the in-place pass overwrites dY)
+        dX = rms_bwd_(dY2, X, W, r, gemma=ctx.GEMMA)
+        return dX.view(*dY.shape), dW, None, None
 
 
 class Fast_Add_RMS_Layernorm(torch.autograd.Function):
@@ -161,58 +124,20 @@ class Fast_Add_RMS_Layernorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, residual, W, eps):
-        _lib.require_gpu(X, residual, W)
-        shape = X.shape
-        dim = shape[-1]
-        X2 = X.reshape(-1, dim)
-        R2 = residual.reshape(-1, dim)
-        if X2.stride(1) != 1:
-            X2 = X2.contiguous()
-        if R2.stride(1) != 1:
-            R2 = R2.contiguous()
-        n_rows = X2.shape[0]
-        H = torch.empty((n_rows, dim), dtype=X.dtype, device=X.device)
-        Y = torch.empty((n_rows, dim), dtype=X.dtype, device=X.device)
-        r = torch.empty(n_rows, dtype=torch.float32, device=X.device)
         W = W.contiguous()
-        with _lib.device_ctx(X):
-            rc = _lib.lib().uamd_add_rms_layernorm_fwd(
-                _lib.ptr(X2), _lib.ptr(R2), _lib.ptr(W), _lib.ptr(H), _lib.ptr(Y), _lib.ptr(r), n_rows, dim,
-                X2.stride(0), R2.stride(0), H.stride(0), Y.stride(0), float(eps), _lib.dtype_code(X.dtype),
-                _lib.dtype_code(W.dtype), _lib.stream_of(X))
-        _lib.check(rc, "uamd_add_rms_layernorm_fwd")
+        H, Y, r = add_rms_fwd(X, residual, W, eps)
         ctx.set_materialize_grads(False)           # an unused h (last layer) arrives as dH = None, not as a zero tensor
         ctx.save_for_backward(H, W, r)
-        return H.view(*shape), Y.view(*shape)
+        return H.view(*X.shape), Y.view(*X.shape)
 
     @staticmethod
     def backward(ctx, dH, dY):
         H, W, r = ctx.saved_tensors
         if dY is None:                             # only the residual stream was used downstream
             return dH, dH, None, None
-        shape = dY.shape
-        dim = shape[-1]
-        dY = dY.reshape(-1, dim)
-        if dY.stride(1) != 1:
-            dY = dY.contiguous()
-        n_rows = dY.shape[0]
-        dW = _weight_grad(dY, H, r, W, ctx.needs_input_grad[2])
-        with _lib.device_ctx(dY):
-            if dH is None:
-                rc = _lib.lib().uamd_rms_layernorm_bwd(
-                    _lib.ptr(dY), _lib.ptr(dY), _lib.ptr(H), _lib.ptr(W), _lib.ptr(r), n_rows, dim, dY.stride(0),
-                    dY.stride(0), H.stride(0), 0, _lib.dtype_code(dY.dtype), _lib.dtype_code(W.dtype),
-                    _lib.stream_of(dY))
-            else:
-                dH = dH.reshape(-1, dim)
-                if dH.stride(1) != 1:
-                    dH = dH.contiguous()
-                rc = _lib.lib().uamd_add_rms_layernorm_bwd(
-                    _lib.ptr(dY), _lib.ptr(dH), _lib.ptr(dY), _lib.ptr(H), _lib.ptr(W), _lib.ptr(r), n_rows, dim,
-                    dY.stride(0), dH.stride(0), dY.stride(0), H.stride(0), _lib.dtype_code(dY.dtype),
-                    _lib.dtype_code(W.dtype), _lib.stream_of(dY))
-        _lib.check(rc, "uamd_add_rms_layernorm_bwd")
-        dX = dY.view(*shape)                       # written over dY, like rms_layernorm.py:218
+        dY2 = _rows(dY)
+        dW = _weight_grad(dY2, H, r, W, ctx.needs_input_grad[2])
+        dX = rms_bwd_(dY2, H, W, r, dH=dH).view(*dY.shape)        # written over dY, like rms_layernorm.py:218
         return dX, dX, dW, None
 
 

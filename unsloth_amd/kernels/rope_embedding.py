@@ -31,14 +31,11 @@ def _launch_qk(Q, K, cos, sin, idx, backward):
     n_heads_K = K.shape[1] if K is not None else 0
     if Q.stride(3) != 1 or (K is not None and K.stride(3) != 1):
         raise ValueError("head_dim must be the contiguous dimension")
-    with _lib.device_ctx(Q):
-        rc = _lib.lib().uamd_rope_embedding_qk(
-            _lib.ptr(Q), Q.stride(0), Q.stride(1), Q.stride(2),
-            _lib.ptr(K), *( (K.stride(0), K.stride(1), K.stride(2)) if K is not None else (0, 0, 0) ),
-            _lib.ptr(cos), cos.stride(0), _lib.ptr(sin), sin.stride(0), _lib.ptr(idx),
-            batch, seq_len, n_heads_Q, n_heads_K, head_dim, int(backward),
-            _lib.dtype_code(Q.dtype), _lib.dtype_code(cos.dtype), _lib.stream_of(Q))
-    _lib.check(rc, "uamd_rope_embedding_qk")
+    _lib.call("uamd_rope_embedding_qk", Q, _lib.ptr(Q), Q.stride(0), Q.stride(1), Q.stride(2),
+              _lib.ptr(K), *((K.stride(0), K.stride(1), K.stride(2)) if K is not None else (0, 0, 0)),
+              _lib.ptr(cos), cos.stride(0), _lib.ptr(sin), sin.stride(0), _lib.ptr(idx),
+              batch, seq_len, n_heads_Q, n_heads_K, head_dim, int(backward),
+              _lib.dtype_code(Q.dtype), _lib.dtype_code(cos.dtype), _lib.stream_of(Q))
 
 
 class Fast_RoPE_Embedding(torch.autograd.Function):
@@ -59,12 +56,9 @@ class Fast_RoPE_Embedding(torch.autograd.Function):
 
     @staticmethod
     def _run(Q2d, cos, sin, seq_len, n_heads, head_dim, backward):
-        with _lib.device_ctx(Q2d):
-            rc = _lib.lib().uamd_rope_embedding(
-                _lib.ptr(Q2d), Q2d.stride(0), _lib.ptr(cos), cos.stride(0), _lib.ptr(sin), sin.stride(0),
-                Q2d.shape[0], seq_len, n_heads, head_dim, int(backward), _lib.dtype_code(Q2d.dtype),
-                _lib.dtype_code(cos.dtype), _lib.stream_of(Q2d))
-        _lib.check(rc, "uamd_rope_embedding")
+        _lib.call("uamd_rope_embedding", Q2d, _lib.ptr(Q2d), Q2d.stride(0), _lib.ptr(cos), cos.stride(0), _lib.ptr(sin),
+                  sin.stride(0), Q2d.shape[0], seq_len, n_heads, head_dim, int(backward), _lib.dtype_code(Q2d.dtype),
+                  _lib.dtype_code(cos.dtype), _lib.stream_of(Q2d))
 
     @staticmethod
     def backward(ctx, dY):
@@ -137,13 +131,10 @@ class Fast_MRoPE_Embedding_QK(torch.autograd.Function):
     @staticmethod
     def _run(Q, K, cos, sin, pos3, s_t, s_h, backward):
         batch, n_heads_Q, seq_len, head_dim = Q.shape
-        with _lib.device_ctx(Q):
-            rc = _lib.lib().uamd_rope_embedding_qk_mrope(
-                _lib.ptr(Q), Q.stride(0), Q.stride(1), Q.stride(2), _lib.ptr(K), K.stride(0), K.stride(1), K.stride(2),
-                _lib.ptr(cos), cos.stride(0), _lib.ptr(sin), sin.stride(0), _lib.ptr(pos3), s_t, s_h, batch, seq_len,
-                n_heads_Q, K.shape[1], head_dim, int(backward), _lib.dtype_code(Q.dtype), _lib.dtype_code(cos.dtype),
-                _lib.stream_of(Q))
-        _lib.check(rc, "uamd_rope_embedding_qk_mrope")
+        _lib.call("uamd_rope_embedding_qk_mrope", Q, _lib.ptr(Q), Q.stride(0), Q.stride(1), Q.stride(2), _lib.ptr(K),
+                  K.stride(0), K.stride(1), K.stride(2), _lib.ptr(cos), cos.stride(0), _lib.ptr(sin), sin.stride(0),
+                  _lib.ptr(pos3), s_t, s_h, batch, seq_len, n_heads_Q, K.shape[1], head_dim, int(backward),
+                  _lib.dtype_code(Q.dtype), _lib.dtype_code(cos.dtype), _lib.stream_of(Q))
 
     @staticmethod
     def backward(ctx, dQ, dK):

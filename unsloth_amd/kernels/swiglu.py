@@ -9,10 +9,7 @@ def _glu_fwd(name, e, g):
     assert e.shape == g.shape and e.dtype == g.dtype
     e, g = e.contiguous(), g.contiguous()
     h = torch.empty_like(e)
-    with _lib.device_ctx(e):
-        rc = getattr(_lib.lib(), name)(_lib.ptr(e), _lib.ptr(g), _lib.ptr(h), e.numel(),
-                                       _lib.dtype_code(e.dtype), _lib.stream_of(e))
-    _lib.check(rc, name)
+    _lib.call(name, e, _lib.ptr(e), _lib.ptr(g), _lib.ptr(h), e.numel(), _lib.dtype_code(e.dtype), _lib.stream_of(e))
     return h
 
 
@@ -23,10 +20,7 @@ def _glu_bwd(name, DW, e, g):
     if not (DW.is_contiguous() and e.is_contiguous() and g.is_contiguous()):
         raise ValueError("in-place GLU backward needs contiguous DW, e, g")
     assert DW.shape == e.shape == g.shape and DW.dtype == e.dtype == g.dtype
-    with _lib.device_ctx(e):
-        rc = getattr(_lib.lib(), name)(_lib.ptr(DW), _lib.ptr(e), _lib.ptr(g), e.numel(),
-                                       _lib.dtype_code(e.dtype), _lib.stream_of(e))
-    _lib.check(rc, name)
+    _lib.call(name, e, _lib.ptr(DW), _lib.ptr(e), _lib.ptr(g), e.numel(), _lib.dtype_code(e.dtype), _lib.stream_of(e))
     return DW, e, g
 
 

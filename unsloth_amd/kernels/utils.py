@@ -195,23 +195,31 @@ def _chunk_rows(row_bytes, align):
     return rows
 
 
+def _row_spans(M, row_bytes, align):
+    """[(first row, rows)] of the launches over M operand rows of `row_bytes` bytes: one below GEMM_SPAN_LIMIT, else
+    `_chunk_rows` steps (multiples of `align`, the last one short)."""
+    if M * row_bytes < GEMM_SPAN_LIMIT:
+        return [(0, M)]
+    step = _chunk_rows(row_bytes, align)
+    return [(r0, min(step, M - r0)) for r0 in range(0, M, step)]
+
+
 def _launch_gemm(X2d, groups, nf4, accumulate=False, nn=False):
     """`nn`: the groups' B (and rank-block BK) are [K, N] row-major, C = A @ B (uamd_gemm_nn_256); callers check
     `_use_gemm256` first -- only the 256-tile kernel family has that form.
     A launch whose per-row operands (A, the rank block XK, the fp32 XA) span GEMM_SPAN_LIMIT bytes or more is issued as
     row chunks of a multiple of 256 rows (whole tiles of every kernel); below the limit it is exactly one launch."""
-    L = _lib.lib()
     M, K = X2d.shape
     # a LoRA term given as (fp32 XA, LB) -- no rank block -- is the register prologue of the 128 x 128 kernels only
     prologue_lora = any(g.lora_xa and not g.lora_xk for g in groups)
     if nn:
-        fn, name = L.uamd_gemm_nn_256, "uamd_gemm_nn_256"
+        name = "uamd_gemm_nn_256"
     elif nf4:
-        fn, name = L.uamd_gemm_nt_nf4, "uamd_gemm_nt_nf4"
+        name = "uamd_gemm_nt_nf4"
     elif _use_gemm256(M, K, [g.N for g in groups]) and not prologue_lora:
-        fn, name = L.uamd_gemm_nt_256, "uamd_gemm_nt_256"
+        name = "uamd_gemm_nt_256"
     else:
-        fn, name = L.uamd_gemm_nt, "uamd_gemm_nt"
+        name = "uamd_gemm_nt"
     item = X2d.element_size()
     row_bytes = X2d.stride(0) * item
     for g in groups:
@@ -219,28 +227,20 @@ def _launch_gemm(X2d, groups, nf4, accumulate=False, nn=False):
             row_bytes = max(row_bytes, g.ld_xk * item)
         if g.lora_xa:
             row_bytes = max(row_bytes, g.ld_xa * 4)
-    if M * row_bytes < GEMM_SPAN_LIMIT:
-        spans = [(0, M)]
-    else:
-        step = _chunk_rows(row_bytes, 256)
-        spans = [(r0, min(step, M - r0)) for r0 in range(0, M, step)]
-    with _lib.device_ctx(X2d):
-        for r0, rows in spans:
-            chunk = []
-            for g in groups:
-                c = GemmGroup.from_buffer_copy(g)
-                if r0:                             # C is in the activation dtype; XA is fp32
-                    c.C += r0 * c.ldc * item
-                    if c.lora_xk:
-                        c.lora_xk += r0 * c.ld_xk * item
-                    if c.lora_xa:
-                        c.lora_xa += r0 * c.ld_xa * 4
-                chunk.append(c)
-            arr = (GemmGroup * len(chunk))(*chunk)
-            rc = fn(ctypes.c_void_p(X2d.data_ptr() + r0 * X2d.stride(0) * item), X2d.stride(0), rows, K, arr, len(chunk),
-                    int(accumulate),
-                    _lib.dtype_code(X2d.dtype), _lib.stream_of(X2d))
-            _lib.check(rc, name)
+    for r0, rows in _row_spans(M, row_bytes, 256):
+        chunk = []
+        for g in groups:
+            c = GemmGroup.from_buffer_copy(g)
+            if r0:                             # C is in the activation dtype; XA is fp32
+                c.C += r0 * c.ldc * item
+                if c.lora_xk:
+                    c.lora_xk += r0 * c.ld_xk * item
+                if c.lora_xa:
+                    c.lora_xa += r0 * c.ld_xa * 4
+            chunk.append(c)
+        arr = (GemmGroup * len(chunk))(*chunk)
+        _lib.call(name, X2d, ctypes.c_void_p(X2d.data_ptr() + r0 * X2d.stride(0) * item), X2d.stride(0), rows, K, arr,
+                  len(chunk), int(accumulate), _lib.dtype_code(X2d.dtype), _lib.stream_of(X2d))
     return name
 
 
@@ -281,7 +281,7 @@ class _PreparedFactors:
         self.params = {}        # id -> [weakref, rm, tr, version, epoch, padspec]
         self.pad_bufs = {}      # key -> zero-initialised [rows, width] buffer (rank-block BK operands of the GEMM)
         self.epoch = -1
-        self.table = None       # (ptr signature, descs tensor, prefix tensor, total tiles)
+        self.table = None       # (descriptor bytes, descs tensor, prefix tensor, total tiles, identity key)
 
     @staticmethod
     def _tiles(P):
@@ -298,41 +298,33 @@ class _PreparedFactors:
         key = tuple((P.data_ptr(), P.shape[0], P.shape[1], rm.data_ptr(), tr.data_ptr(),
                      None if pad is None else (pad[0].data_ptr(), pad[0].stride(0)) + tuple(pad[1:]))
                     for (P, rm, tr, pad) in ents) if len(ents) > 1 else None
-        if key is not None and self.table is not None and len(self.table) > 4 and self.table[4] == key:
-            tab = self.table
-            any_p = ents[0][0]
-            with _lib.device_ctx(any_p):
-                rc = _lib.lib().uamd_lora_prepare(_lib.ptr(tab[1]), _lib.ptr(tab[2]), len(ents), tab[3],
-                                                  _lib.dtype_code(self.dtype), _lib.stream_of(any_p))
-            _lib.check(rc, "uamd_lora_prepare")
-            return
-        descs = np.zeros(len(ents), dtype=np.dtype(self._DESC))
-        assert descs.dtype.itemsize == 56
-        prefix, tot = np.zeros(len(ents), dtype=np.int32), 0
-        for i, (P, rm, tr, pad) in enumerate(ents):
-            if pad is None:
-                descs[i] = (P.data_ptr(), rm.data_ptr(), tr.data_ptr(), P.shape[0], P.shape[1], 0, 0, 0.0, 0)
-            else:
-                buf, col, scale, transposed = pad
-                descs[i] = (P.data_ptr(), rm.data_ptr(), tr.data_ptr(), P.shape[0], P.shape[1],
-                            buf.data_ptr() + col * buf.element_size(), buf.stride(0), scale, int(transposed))
-            prefix[i] = tot
-            tot += self._tiles(P)
-        sig = descs.tobytes()
-        if self.table is None or self.table[0] != sig:
-            d = torch.from_numpy(descs.view(np.uint8).copy()).to(self.device)
-            pf = torch.from_numpy(prefix).to(self.device)
-            tab = (sig, d, pf, tot, key)
-            if len(ents) > 1:
+        tab = self.table
+        if key is None or tab is None or tab[4] != key:
+            descs = np.zeros(len(ents), dtype=np.dtype(self._DESC))
+            assert descs.dtype.itemsize == 56
+            prefix, tot = np.zeros(len(ents), dtype=np.int32), 0
+            for i, (P, rm, tr, pad) in enumerate(ents):
+                if pad is None:
+                    descs[i] = (P.data_ptr(), rm.data_ptr(), tr.data_ptr(), P.shape[0], P.shape[1], 0, 0, 0.0, 0)
+                else:
+                    buf, col, scale, transposed = pad
+                    descs[i] = (P.data_ptr(), rm.data_ptr(), tr.data_ptr(), P.shape[0], P.shape[1],
+                                buf.data_ptr() + col * buf.element_size(), buf.stride(0), scale, int(transposed))
+                prefix[i] = tot
+                tot += self._tiles(P)
+            sig = descs.tobytes()
+            if tab is None or tab[0] != sig:
+                d = torch.from_numpy(descs.view(np.uint8).copy()).to(self.device)
+                pf = torch.from_numpy(prefix).to(self.device)
+                tab = (sig, d, pf, tot, key)
+            else:                                   # same descriptors under a new identity key
+                tab = tab[:4] + (key,)
+            if len(ents) > 1:                       # (a single-entry launch never matches the stored table's bytes)
                 self.table = tab
-        else:
-            tab = self.table = self.table[:4] + (key,)
         any_p = ents[0][0]
-        with _lib.device_ctx(any_p):
-            rc = _lib.lib().uamd_lora_prepare(_lib.ptr(tab[1]), _lib.ptr(tab[2]), len(ents), tab[3],
-                                              _lib.dtype_code(self.dtype), _lib.stream_of(any_p))
-        _lib.check(rc, "uamd_lora_prepare")
         # the table tensors must outlive the launch: stream-ordered free is fine for torch's caching allocator
+        _lib.call("uamd_lora_prepare", any_p, _lib.ptr(tab[1]), _lib.ptr(tab[2]), len(ents), tab[3],
+                  _lib.dtype_code(self.dtype), _lib.stream_of(any_p))
 
     def _forget(self, pid):
         self.params.pop(pid, None)
@@ -388,19 +380,26 @@ class _PreparedFactors:
 
 
 _PREPARED = {}
-LORA_PREPARE = True
+
+
+def _preparable(P, dtype):
+    """The factors `uamd_lora_prepare` keeps current: fp32 CUDA Parameters (the training case) used in a 16-bit dtype."""
+    return (isinstance(P, torch.nn.Parameter) and P.is_cuda and P.dtype == torch.float32 and P.dim() == 2
+            and P.is_contiguous() and dtype in (torch.bfloat16, torch.float16))
+
+
+def _prepared_for(device, dtype):
+    g = _PREPARED.get((device, dtype))
+    if g is None:
+        g = _PREPARED[(device, dtype)] = _PreparedFactors(device, dtype)
+    return g
 
 
 def _cached_cast(P, tag, dtype, build):
     if not isinstance(P, torch.nn.Parameter):
         return build()
-    if (LORA_PREPARE and tag in ("rowmajor", "T") and P.is_cuda and P.dtype == torch.float32 and P.dim() == 2
-            and P.is_contiguous() and dtype in (torch.bfloat16, torch.float16)):
-        key = (P.device, dtype)
-        g = _PREPARED.get(key)
-        if g is None:
-            g = _PREPARED[key] = _PreparedFactors(P.device, dtype)
-        return g.get(P, tag)
+    if tag in ("rowmajor", "T") and _preparable(P, dtype):
+        return _prepared_for(P.device, dtype).get(P, tag)
     pid = id(P)
     ent = _CAST_CACHE.get(pid)
     if (ent is None or ent[0]() is not P or ent[1] != P._version or ent[2] != P.data_ptr()
@@ -422,10 +421,7 @@ def rank_block_bk(members, rows, width, transposed, dtype, by_rows=False):
     `transposed`) at columns col_off.. for every member (P, col_off, scale). When the factors are fp32 CUDA
     Parameters (the training case) the buffer is persistent and kept current by the once-per-step
     uamd_lora_prepare launch; otherwise it is built here."""
-    prepared = LORA_PREPARE and dtype in (torch.bfloat16, torch.float16) and all(
-        isinstance(P, torch.nn.Parameter) and P.is_cuda and P.dtype == torch.float32 and P.dim() == 2
-        and P.is_contiguous() for P, _, _ in members)
-    if not prepared:
+    if not all(_preparable(P, dtype) for P, _, _ in members):
         # plain tensors (tests, ad-hoc calls of matmul_lora): built per call with torch ops
         with torch.no_grad():
             buf = torch.zeros((rows, width), dtype=dtype, device=members[0][0].device)
@@ -437,11 +433,7 @@ def rank_block_bk(members, rows, width, transposed, dtype, by_rows=False):
                 else:
                     buf[:, off:off + src.shape[1]] = val
         return buf
-    key = (members[0][0].device, dtype)
-    g = _PREPARED.get(key)
-    if g is None:
-        g = _PREPARED[key] = _PreparedFactors(members[0][0].device, dtype)
-    return g.get_pad(members, rows, width, transposed, by_rows)
+    return _prepared_for(members[0][0].device, dtype).get_pad(members, rows, width, transposed, by_rows)
 
 
 def lora_xa(X2d, A_list, out=None, out_k=None, k_cols=0):
@@ -455,8 +447,7 @@ def lora_xa(X2d, A_list, out=None, out_k=None, k_cols=0):
     Rp = [(r + 7) // 8 * 8 for r in Rs]
     K = X2d.shape[1]
     if len(A_list) == 1 and Rs[0] == Rp[0]:
-        A0 = A_list[0]
-        Acat = _cached_cast(A0, "rowmajor", dtype, lambda: A0.to(dtype).contiguous())   # A.to(dtype), utils.py:1166
+        Acat = cast_lora(A_list[0], dtype)                                              # A.to(dtype), utils.py:1166
     else:
         def _cat():
             if Rs == Rp:
@@ -481,20 +472,15 @@ def lora_xa(X2d, A_list, out=None, out_k=None, k_cols=0):
     else:
         assert out.dtype == torch.float32 and tuple(out.shape) == (X2d.shape[0], Rt) and out.stride(1) == 1 \
             and out.stride(0) % 4 == 0
-    L = _lib.lib()
     if out_k is not None:
         assert Rt <= 64 and out_k.dtype == dtype and out_k.stride(1) == 1 and k_cols >= Rt
-        with _lib.device_ctx(X2d):
-            rc = L.uamd_lora_xa2k(_lib.ptr(X2d), X2d.stride(0), _lib.ptr(Acat), Acat.stride(0), _lib.ptr(out),
-                                  out.stride(0), _lib.ptr(out_k), out_k.stride(0), k_cols, X2d.shape[0], K, Rt, Rt,
-                                  _lib.dtype_code(dtype), _lib.stream_of(X2d))
-        _lib.check(rc, "uamd_lora_xa2k")
+        _lib.call("uamd_lora_xa2k", X2d, _lib.ptr(X2d), X2d.stride(0), _lib.ptr(Acat), Acat.stride(0), _lib.ptr(out),
+                  out.stride(0), _lib.ptr(out_k), out_k.stride(0), k_cols, X2d.shape[0], K, Rt, Rt,
+                  _lib.dtype_code(dtype), _lib.stream_of(X2d))
     else:
-        fn, name = (L.uamd_lora_xa2, "uamd_lora_xa2") if (LORA_XA_V2 and Rt <= 64 and K >= 8) else (L.uamd_lora_xa, "uamd_lora_xa")
-        with _lib.device_ctx(X2d):
-            rc = fn(_lib.ptr(X2d), X2d.stride(0), _lib.ptr(Acat), Acat.stride(0), _lib.ptr(out), out.stride(0),
-                    X2d.shape[0], K, Rt, Rt, _lib.dtype_code(dtype), _lib.stream_of(X2d))
-        _lib.check(rc, name)
+        _lib.call("uamd_lora_xa2" if (LORA_XA_V2 and Rt <= 64 and K >= 8) else "uamd_lora_xa", X2d,
+                  _lib.ptr(X2d), X2d.stride(0), _lib.ptr(Acat), Acat.stride(0), _lib.ptr(out), out.stride(0),
+                  X2d.shape[0], K, Rt, Rt, _lib.dtype_code(dtype), _lib.stream_of(X2d))
     offs, o = [], 0
     for rp in Rp:
         offs.append((o, rp))
@@ -507,11 +493,16 @@ def cast_lora(P, dtype):
     return _cached_cast(P, "rowmajor", dtype, lambda: P.to(dtype).contiguous())
 
 
+def cast_lora_t(P, dtype):
+    """P.to(dtype).t() as a contiguous [cols, rows] matrix, converted once per parameter version."""
+    return _cached_cast(P, "T", dtype, lambda: P.to(dtype).t().contiguous())
+
+
 def _pad_rank(B, Rp, dtype):
     """LoRA B [N, r] -> contiguous [N, Rp] in the activation dtype (B.to(dtype), utils.py:1167)."""
     N, r = B.shape
     if r == Rp:
-        return _cached_cast(B, "rowmajor", dtype, lambda: B.to(dtype).contiguous())
+        return cast_lora(B, dtype)
     out = torch.zeros((N, Rp), dtype=dtype, device=B.device)
     out[:, :r] = B
     return out
@@ -561,6 +552,19 @@ def _xa_and_rank_block(X2d, A_list, want_k, out=None):
     return xa, offs, xk
 
 
+def _fused_nf4(q, M, K):
+    """Does a forward launch of M rows decode this weight inside the GEMM (uamd_gemm_nt_nf4)? lora_linear_forward and the
+    kernel that prepares its rank block (glu_fwd_xa) must agree."""
+    return q is not None and FUSED_NF4 and M < FUSED_NF4_MAX_M and q.blocksize == 64 and K % 64 == 0
+
+
+def _decoded_as(Wd, dtype):
+    if Wd.dtype != dtype:
+        raise TypeError(f"quant_state.dtype {Wd.dtype} != activation dtype {dtype}: the dequantised weight would be "
+                        "misread by the GEMM (set quant_state.dtype to the compute dtype)")
+    return Wd
+
+
 def lora_linear_forward(X, projs, outs=None, return_xa=False, pre_xa=None):
     """Y_g = X @ W_g^T + s_g * (X @ A_g^T) @ B_g^T for projections `projs` = [(W, W_quant, A, B, s)]
     that share X. Returns a list of [.., N_g] tensors. This is matmul_lora (utils.py:1128-1170)
@@ -579,8 +583,7 @@ def lora_linear_forward(X, projs, outs=None, return_xa=False, pre_xa=None):
     projs = [tuple(p[:5]) for p in projs]
     with_lora = [p for p in projs if p[2] is not None]
     Ns = [(q.shape[0] if q is not None else W.shape[0]) for (W, q, _, _, _) in projs]
-    fused_nf4 = [q is not None and FUSED_NF4 and M < FUSED_NF4_MAX_M and q.blocksize == 64 and K % 64 == 0
-                 for (_, q, _, _, _) in projs]
+    fused_nf4 = [_fused_nf4(q, M, K) for (_, q, _, _, _) in projs]
     # the dense groups go to the 256x256 kernel when the launch is large enough: there the LoRA term rides along as
     # extra K tiles (XK = T(X A^T) zero-padded to 64 columns, BK_g = T(s_g B_g) at its rank columns)
     dense_Ns = [n for n, f in zip(Ns, fused_nf4) if not f]
@@ -643,10 +646,7 @@ def lora_linear_forward(X, projs, outs=None, return_xa=False, pre_xa=None):
                 Wd = decoded[gi]
             elif W_quant is not None:
                 # one scratch slot per group member: the grouped launch reads all of them
-                Wd = _nf4.dequantize_nf4(W, W_quant, use_global_buffer=True, slot=8 + gi)
-                if Wd.dtype != dtype:
-                    raise TypeError(f"quant_state.dtype {Wd.dtype} != activation dtype {dtype}: the dequantised "
-                                    "weight would be misread by the GEMM (set quant_state.dtype to the compute dtype)")
+                Wd = _decoded_as(_nf4.dequantize_nf4(W, W_quant, use_global_buffer=True, slot=8 + gi), dtype)
             elif Wd.dtype != dtype or Wd.stride(1) != 1 or Wd.stride(0) % 8:
                 Wd = Wd.to(dtype).contiguous()
             keep.append(Wd)
@@ -702,7 +702,7 @@ def lora_dx_terms(dYs, projs):
             terms.append(None)
             continue
         n_left -= 1
-        Bt = _cached_cast(B, "T", dtype, lambda B=B, dtype=dtype: B.to(dtype).t().contiguous())        # [r, N]
+        Bt = cast_lora_t(B, dtype)              # [r, N]
         r = A.shape[0]
         rp = (r + 7) // 8 * 8
         kw = {}
@@ -725,12 +725,6 @@ def lora_dx_terms(dYs, projs):
     return terms
 
 
-MERGE_DX = True
-# dX = dY @ W through the NN form of the 256-tile GEMM (row-major decode, transposing LDS reads) instead of a
-# transposed decode + the NT form
-NN_DX = True
-
-
 def _adjacent_columns(ts):
     """The 2-D views `ts` are consecutive column blocks of one row-major buffer -> the [M, sum N] view, else None."""
     t0 = ts[0]
@@ -746,6 +740,96 @@ def _adjacent_columns(ts):
     return torch.as_strided(t0, (t0.shape[0], off), (t0.stride(0), 1))
 
 
+def _dx_weight(projs, nn, dtype):
+    """The weight operand of ONE dX launch over `projs`: [sum N, Kin], the rows as the forward decodes them (`nn`), or
+    its transpose [Kin, sum N] (NT form). Several projections (the K-concatenated launch; all NF4 in the activation
+    dtype, the caller checked) are stacked in that order: the mirror group when every member keeps a mirror, else decoded
+    into scratch slot 2. One projection: its mirror / the per-device decode buffer, or the dense weight as is or cast."""
+    Ws, qs = [p[0] for p in projs], [p[1] for p in projs]
+    if len(projs) > 1:
+        Kin = qs[0].shape[1]
+        ends = [0]
+        for q in qs:
+            ends.append(ends[-1] + q.shape[0])
+        if nn and all(_nf4.mirror_wanted(q) for q in qs):
+            # (the group is keyed on the members in THIS order; the forward of gate|up caches it as [gate, up] while the
+            # MLP backward asks for [up, gate] -- a second stacked mirror. Ordering the members here, in this one place, is
+            # the fix; it changes memory with mirrors on and so is not part of a behaviour-preserving change)
+            Wd, _ = _nf4.resident_group(Ws, qs)
+        elif nn:
+            Wd = _nf4.scratch(Ws[0].device, ends[-1] * Kin, dtype, slot=2).view(ends[-1], Kin)
+            _nf4.dequantize_nf4_group(Ws, qs, [Wd[a:b] for a, b in zip(ends, ends[1:])])
+        else:
+            Wd = _nf4.scratch(Ws[0].device, Kin * ends[-1], dtype, slot=2).view(Kin, ends[-1])
+            for W, q, a, b in zip(Ws, qs, ends, ends[1:]):
+                _nf4.dequantize_nf4(W, q, out=Wd[:, a:b], transpose=True)             # [Kin, n] at column `a`
+    elif qs[0] is not None:
+        Wd = _nf4.dequantize_nf4(Ws[0], qs[0], transpose=not nn, use_global_buffer=True)
+    elif nn:
+        W = Ws[0]
+        Wd = W if (W.dtype == dtype and W.stride(1) == 1 and W.stride(0) % 8 == 0) else W.to(dtype).contiguous()
+    else:
+        Wd = Ws[0].to(dtype).t().contiguous()
+    return _decoded_as(Wd, dtype)
+
+
+def _dx_rank_term(members, xa, xk, nn, Kin, dtype):
+    """`_group` keywords of the rank term xa @ [s_1 A_1; s_2 A_2; ...] of a dX launch. `members` = [(A, column of its
+    P = dY B in `xa` / `xk`, s)]. With the rank block `xk` (the 256-tile kernels' extra K tiles) BK holds s A at its rank
+    rows (NN form) or s A^T at its rank columns (NT); without it the fp32 `xa` and LB = [A_1^T | A_2^T | ...] go to the
+    128-tile kernels' prologue, which has one scale per launch: None when the members' scales differ."""
+    kw = dict(xa=xa, ld_xa=xa.stride(0), R=xa.shape[1])
+    if xk is not None:
+        if nn:
+            bk = rank_block_bk(members, xk.shape[1], Kin, False, dtype, by_rows=True)      # [Rk, Kin]
+        else:
+            bk = rank_block_bk(members, Kin, xk.shape[1], True, dtype)                     # [Kin, Rk]
+        # (the scales are in BK; only the prologue reads the group's own)
+        return dict(kw, scale=members[0][2] if len(members) == 1 else 1.0, xk=xk, bk=bk)
+    scales = {float(s) for _, _, s in members}
+    if len(scales) != 1:
+        return None
+    A_list = [A for A, _, _ in members]
+    if len(A_list) > 1:
+        tag = ("catT",) + tuple((id(A), A._version, A.data_ptr()) for A in A_list[1:])
+        lb = _cached_cast(A_list[0], tag, dtype,
+                          lambda: torch.cat([cast_lora_t(A, dtype) for A in A_list], dim=1).contiguous())
+    elif A_list[0].shape[0] == xa.shape[1]:
+        lb = cast_lora_t(A_list[0], dtype)                                                 # A^T [Kin, r]
+    else:
+        lb = _pad_rank(A_list[0].to(dtype).t(), xa.shape[1], dtype)
+    return dict(kw, lb=lb, scale=scales.pop())
+
+
+def _dx_gemm(dY2d, projs, terms, xa, out, accumulate):
+    """out (+)= dY2d @ [W_1; W_2; ...] + xa @ [s_1 A_1; s_2 A_2; ...]: one GEMM over the (concatenated) output features
+    of `projs`. `terms` = per projection its P = dY B or None, `xa` = the [M, sum r] view of all of them (None without an
+    adapter). The NN form of the 256-tile family (no transposed copy of any weight) when the launch is large enough for
+    it and every rank term has its rank block, else a transposed decode and the NT form. Returns `out`, or None when the
+    rank term cannot go in one launch."""
+    M, N = dY2d.shape
+    dtype = dY2d.dtype
+    W0, q0 = projs[0][:2]
+    Kin = q0.shape[1] if q0 is not None else W0.shape[1]
+    # per adapter (A, s, (rank block its P was also written to, at column)) -- lora_dx_terms / glu_bwd_terms attach the latter
+    lora = [(A, s, getattr(t, "_uamd_xk", None)) for (_, _, A, _, s), t in zip(projs, terms) if A is not None]
+    have_xk = all(x is not None and x[0] is lora[0][2][0] for _, _, x in lora)         # ONE block shared by all of them
+    use256 = _use_gemm256(M, N, [Kin])
+    nn = use256 and Kin % 8 == 0 and have_xk
+    Wd = _dx_weight(projs, nn, dtype)
+    if out is None:
+        out = torch.empty((M, Kin), dtype=dtype, device=dY2d.device)
+    kw = {}
+    if lora:
+        block = lora[0][2][0] if (have_xk and use256) else None
+        members = [(A, x[1] if block is not None else 0, s) for A, s, x in lora]
+        kw = _dx_rank_term(members, xa, block, nn, Kin, dtype)
+        if kw is None:
+            return None
+    _launch_gemm(dY2d, [_group(Wd, out, Kin, Wd.stride(0), **kw)], nf4=False, accumulate=accumulate, nn=nn)
+    return out
+
+
 def _lora_linear_dx_merged(dYs, projs, out, terms):
     """dX = [dY_1 | dY_2 | ...] @ [W_1; W_2; ...] + s [P_1 | P_2 | ...] @ [A_1; A_2; ...] as ONE GEMM when the
     incoming gradients are column blocks of one buffer (the attention backward writes dQ, dK, dV that way): the
@@ -755,126 +839,30 @@ def _lora_linear_dx_merged(dYs, projs, out, terms):
         return None
     if any(A is None for (_, _, A, _, _) in projs) or any(t is None for t in terms):
         return None
-    dY2 = [_rows2d(dY) for dY in dYs]
-    dYcat = _adjacent_columns(dY2)
+    dYcat = _adjacent_columns([_rows2d(dY) for dY in dYs])
     Pcat = _adjacent_columns(list(terms))
     if dYcat is None or Pcat is None or dYcat.shape[1] % 64 or dYcat.stride(0) % 8:
         return None
-    dtype = dYcat.dtype
     Kin = projs[0][1].shape[1]
-    if any(q.shape[1] != Kin or q.dtype != dtype for (_, q, _, _, _) in projs):
+    if any(q.shape[1] != Kin or q.dtype != dYcat.dtype for (_, q, _, _, _) in projs):
         return None
-    M, Ntot = dYcat.shape
-    A_list = [A for (_, _, A, _, _) in projs]
-    if out is None:
-        out = torch.empty((M, Kin), dtype=dtype, device=dYcat.device)
-    xks = [getattr(t, "_uamd_xk", None) for t in terms]
-    have_xk = all(x is not None and x[0] is xks[0][0] for x in xks)
-    if NN_DX and have_xk and _use_gemm256(M, Ntot, [Kin]) and Kin % 8 == 0:
-        # NN form: [W_q; W_k; W_v] stacked by ROWS is just the three row-major decodes one after the other -- the
-        # layout the forward uses -- and the GEMM contracts over those rows (no transposed copy of any weight)
-        if all(_nf4.mirror_wanted(p_[1]) for p_ in projs):
-            Wcat, _ = _nf4.resident_group([p_[0] for p_ in projs], [p_[1] for p_ in projs])
-        else:
-            Wcat = _nf4.scratch(dYcat.device, Ntot * Kin, dtype, slot=2).view(Ntot, Kin)
-            row, rows_of = 0, []
-            for (W, q, _, _, _) in projs:
-                rows_of.append(Wcat[row:row + q.shape[0]])
-                row += q.shape[0]
-            _nf4.dequantize_nf4_group([p_[0] for p_ in projs], [p_[1] for p_ in projs], rows_of)
-        xk = xks[0][0]
-        bk = rank_block_bk([(A, x[1], s) for (_, _, A, _, s), x in zip(projs, xks)], xk.shape[1], Kin, False, dtype,
-                           by_rows=True)                      # [s_q A_q; s_k A_k; s_v A_v; 0] : [Rk, Kin]
-        g = _group(Wcat, out, Kin, Wcat.stride(0), xa=Pcat, ld_xa=Pcat.stride(0), R=Pcat.shape[1], scale=1.0, xk=xk, bk=bk)
-        _launch_gemm(dYcat, [g], nf4=False, accumulate=False, nn=True)
-        return out
-    Wt = _nf4.scratch(dYcat.device, Kin * Ntot, dtype, slot=2).view(Kin, Ntot)
-    col = 0
-    for (W, q, _, _, _) in projs:
-        n = q.shape[0]
-        _nf4.dequantize_nf4(W, q, out=Wt[:, col:col + n], transpose=True)          # [Kin, n] at column `col`
-        col += n
-    if _use_gemm256(M, Ntot, [Kin]) and have_xk:
-        # rank block as extra K tiles: XK = [T(P_q) | T(P_k) | T(P_v) | 0], BK = [s_q A_q^T | s_k A_k^T | s_v A_v^T | 0]
-        xk = xks[0][0]
-        bk = rank_block_bk([(A, x[1], s) for (_, _, A, _, s), x in zip(projs, xks)], Kin, xk.shape[1], True, dtype)
-        g = _group(Wt, out, Kin, Wt.stride(0), xa=Pcat, ld_xa=Pcat.stride(0), R=Pcat.shape[1], scale=1.0, xk=xk, bk=bk)
-    else:
-        scales = {float(s) for (_, _, _, _, s) in projs}
-        if len(scales) != 1:
-            return None
-        tag = ("catT",) + tuple((id(A), A._version, A.data_ptr()) for A in A_list[1:])
-        lb = _cached_cast(A_list[0], tag, dtype,
-                          lambda: torch.cat([_cached_cast(A, "T", dtype, lambda A=A: A.to(dtype).t().contiguous())
-                                             for A in A_list], dim=1).contiguous())
-        g = _group(Wt, out, Kin, Wt.stride(0), xa=Pcat, ld_xa=Pcat.stride(0), lb=lb, R=Pcat.shape[1],
-                   scale=scales.pop())
-    _launch_gemm(dYcat, [g], nf4=False, accumulate=False)
-    return out
+    return _dx_gemm(dYcat, projs, terms, Pcat, out, False)
 
 
 def lora_linear_dx(dYs, projs, out=None, terms=None):
-    """dX = sum_g dY_g @ W_g + s_g * (dY_g @ B_g) @ A_g   (fast_lora.py:193-204, 497-517, 639-647).
-    The contraction runs over `out`, so the NF4 weight is decoded TRANSPOSED into the per-device
-    scratch (one launch) and fed to the same NT GEMM. `out` (e.g. the saved X, reference's
-    inplace=True) receives the result. `terms` = lora_dx_terms(dYs, projs) when the caller already has them."""
-    dtype = dYs[0].dtype
+    """dX = sum_g dY_g @ W_g + s_g * (dY_g @ B_g) @ A_g   (fast_lora.py:193-204, 497-517, 639-647): one GEMM over all
+    projections when they allow it (_lora_linear_dx_merged), else one per projection, each after the first accumulating.
+    `out` (e.g. the saved X, reference's inplace=True) receives the result. `terms` = lora_dx_terms(dYs, projs) when the
+    caller already has them."""
     projs = [tuple(p[:5]) for p in projs]
     _refuse_fp8(projs)
     if terms is None:
         terms = lora_dx_terms(dYs, projs)
-    merged = _lora_linear_dx_merged(dYs, projs, out, terms) if MERGE_DX else None
+    merged = _lora_linear_dx_merged(dYs, projs, out, terms)
     if merged is not None:
         return merged
-    first = True
-    for dY, (W, W_quant, A, B, s), xa in zip(dYs, projs, terms):
-        dY2d = _rows2d(dY)
-        M, N = dY2d.shape
-        Kin = W_quant.shape[1] if W_quant is not None else W.shape[1]
-        xk = getattr(xa, "_uamd_xk", None) if A is not None else None
-        if NN_DX and _use_gemm256(M, N, [Kin]) and Kin % 8 == 0 and (A is None or xk is not None):
-            # NN form: contract over the rows of the [N, Kin] weight as the forward decodes it
-            if W_quant is not None:
-                Wd = _nf4.dequantize_nf4(W, W_quant, use_global_buffer=True)
-            else:
-                Wd = W if (W.dtype == dtype and W.stride(1) == 1 and W.stride(0) % 8 == 0) else W.to(dtype).contiguous()
-            if Wd.dtype != dtype:
-                raise TypeError(f"quant_state.dtype {Wd.dtype} != activation dtype {dtype}: the dequantised weight "
-                                "would be misread by the GEMM (set quant_state.dtype to the compute dtype)")
-            if out is None:
-                out = torch.empty((M, Kin), dtype=dtype, device=dY.device)
-            kw = {}
-            if A is not None:
-                bk = rank_block_bk([(A, xk[1], s)], xk[0].shape[1], Kin, False, dtype, by_rows=True)   # s A at its rank rows
-                kw = dict(xa=xa, ld_xa=xa.stride(0), R=xa.shape[1], scale=s, xk=xk[0], bk=bk)
-            _launch_gemm(dY2d, [_group(Wd, out, Kin, Wd.stride(0), **kw)], nf4=False, accumulate=not first, nn=True)
-            first = False
-            continue
-        if W_quant is not None:
-            Wt = _nf4.dequantize_nf4(W, W_quant, transpose=True, use_global_buffer=True)   # [Kin, N]
-        else:
-            Wt = W.to(dtype).t().contiguous()
-        if out is None:
-            out = torch.empty((M, Kin), dtype=dtype, device=dY.device)
-        if Wt.dtype != dtype:
-            raise TypeError(f"quant_state.dtype {Wt.dtype} != activation dtype {dtype}: the dequantised weight "
-                            "would be misread by the GEMM (set quant_state.dtype to the compute dtype)")
-        kw = {}
-        if A is not None:
-            rp = xa.shape[1]
-            xk = getattr(xa, "_uamd_xk", None)
-            if xk is not None and _use_gemm256(M, N, [Kin]):
-                bk = rank_block_bk([(A, xk[1], s)], Kin, xk[0].shape[1], True, dtype)     # s A^T at its rank columns
-                kw = dict(xa=xa, ld_xa=xa.stride(0), R=rp, scale=s, xk=xk[0], bk=bk)
-            else:
-                if A.shape[0] == rp:
-                    lb = _cached_cast(A, "T", dtype, lambda A=A, dtype=dtype: A.to(dtype).t().contiguous())    # A^T [Kin, r]
-                else:
-                    lb = _pad_rank(A.to(dtype).t(), rp, dtype)
-                kw = dict(xa=xa, ld_xa=xa.stride(0), lb=lb, R=rp, scale=s)
-        g = _group(Wt, out, Kin, Wt.stride(0), **kw)
-        _launch_gemm(dY2d, [g], nf4=False, accumulate=not first)
-        first = False
+    for gi, (dY, proj, xa) in enumerate(zip(dYs, projs, terms)):
+        out = _dx_gemm(_rows2d(dY), [proj], [xa], xa, out, accumulate=gi > 0)
     return out
 
 
@@ -937,15 +925,12 @@ def lora_tn(problems, targets=None):
                                             out_nr=int(bool(out_nr)) | (2 if tgt is not None else 0),
                                             scale=float(scale)))
     S = (M + 127) // 128            # upper bound on the row chunks the kernel may choose
-    L = _lib.lib()
     for i in range(0, len(descs), 8):
         chunk = descs[i:i + 8]
         need = sum(S * 16 * ((d.N + 127) // 128) * 128 for d in chunk)
         ws = _nf4.scratch(dev, need, torch.float32, slot=40)
         arr = (_lib.LoraTnProblem * len(chunk))(*chunk)
-        with _lib.device_ctx(ws):
-            rc = L.uamd_lora_tn(arr, len(chunk), M, _lib.ptr(ws), need, _lib.dtype_code(dtype), _lib.stream_of(ws))
-        _lib.check(rc, "uamd_lora_tn")
+        _lib.call("uamd_lora_tn", ws, arr, len(chunk), M, _lib.ptr(ws), need, _lib.dtype_code(dtype), _lib.stream_of(ws))
     return outs
 
 
@@ -1031,9 +1016,8 @@ def glu_fwd_xa(act, e, g, down, n_out_cols_hint=None):
     r = A.shape[0]
     W, q = down[0], down[1]
     N = q.shape[0] if q is not None else W.shape[0]
-    fused_nf4 = q is not None and FUSED_NF4 and M < FUSED_NF4_MAX_M and q.blocksize == 64 and K % 64 == 0
-    want_k = (not fused_nf4) and _use_gemm256(M, K, [N])
-    Ac = _cached_cast(A, "rowmajor", dtype, lambda: A.to(dtype).contiguous())
+    want_k = (not _fused_nf4(q, M, K)) and _use_gemm256(M, K, [N])
+    Ac = cast_lora(A, dtype)
     h = alloc_rows(M, K, dtype, e.device, ld=e.stride(0))          # (one `ld` for e, g and h)
     xa = torch.empty((M, r), dtype=torch.float32, device=e.device)
     xk = torch.empty((M, _rank_width(r)), dtype=dtype, device=e.device) if want_k else None
@@ -1062,8 +1046,7 @@ def glu_bwd_terms(act, DW, e, g, up, gate):
     ru, rg = Au.shape[0], Ag.shape[0]
     Kin = [(p[1].shape[1] if p[1] is not None else p[0].shape[1]) for p in (up, gate)]
     want_k = all(_use_gemm256(M, 64, [k]) for k in Kin)
-    But = _cached_cast(Bu, "T", dtype, lambda: Bu.to(dtype).t().contiguous())        # [r, K]
-    Bgt = _cached_cast(Bg, "T", dtype, lambda: Bg.to(dtype).t().contiguous())
+    But, Bgt = cast_lora_t(Bu, dtype), cast_lora_t(Bg, dtype)                        # [r, K]
     shared = torch.empty((M, ru + rg), dtype=torch.float32, device=e.device)
     xk = torch.empty((M, _rank_width(ru + rg)), dtype=dtype, device=e.device) if want_k else None
     pu, pg = shared[:, :ru], shared[:, ru:]
@@ -1118,18 +1101,12 @@ def dense_dw(dY, X, out=None, accumulate=False):
     # both operands have the contracted token dimension as rows: past GEMM_SPAN_LIMIT the tokens go in chunks (multiples of
     # 64), each launch after the first accumulating into `out` -- one more rounding of a 16-bit `out` per extra chunk
     item = X2d.element_size()
-    row_bytes = max(dY2d.stride(0), X2d.stride(0)) * item
-    step = T if T * row_bytes < GEMM_SPAN_LIMIT else _chunk_rows(row_bytes, 64)
-    with _lib.device_ctx(X2d):
-        for t0 in range(0, T, step):
-            g = _group(X2d, out, N_in, X2d.stride(0))
-            g.B += t0 * X2d.stride(0) * item
-            g.ldc = out.stride(0)
-            arr = (GemmGroup * 1)(g)
-            rc = _lib.lib().uamd_gemm_tn_256(ctypes.c_void_p(dY2d.data_ptr() + t0 * dY2d.stride(0) * item), dY2d.stride(0),
-                                            N_out, min(step, T - t0), arr, 1, int(bool(accumulate) or t0 > 0),
-                                            _lib.dtype_code(dtype), _lib.stream_of(X2d))
-            _lib.check(rc, "uamd_gemm_tn_256")
+    for t0, rows in _row_spans(T, max(dY2d.stride(0), X2d.stride(0)) * item, 64):
+        g = _group(X2d, out, N_in, X2d.stride(0))
+        g.B += t0 * X2d.stride(0) * item
+        _lib.call("uamd_gemm_tn_256", X2d, ctypes.c_void_p(dY2d.data_ptr() + t0 * dY2d.stride(0) * item), dY2d.stride(0),
+                  N_out, rows, (GemmGroup * 1)(g), 1, int(bool(accumulate) or t0 > 0), _lib.dtype_code(dtype),
+                  _lib.stream_of(X2d))
     return out
 
 

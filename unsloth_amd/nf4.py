@@ -135,11 +135,8 @@ def absmax_f32(quant_state):
         n = qs.absmax.numel()
         out = torch.empty(n, dtype=torch.float32, device=qs.absmax.device)
         offset = float(qs.offset)  # one-time sync per weight (cached afterwards)
-        with _lib.device_ctx(out):
-            rc = _lib.lib().uamd_dequantize_absmax(
-                _lib.ptr(qs.state2.code), _lib.ptr(qs.absmax), _lib.ptr(qs.state2.absmax), offset,
-                _lib.ptr(out), qs.state2.blocksize, n, _lib.stream_of(out))
-        _lib.check(rc, "uamd_dequantize_absmax")
+        _lib.call("uamd_dequantize_absmax", out, _lib.ptr(qs.state2.code), _lib.ptr(qs.absmax), _lib.ptr(qs.state2.absmax),
+                  offset, _lib.ptr(out), qs.state2.blocksize, n, _lib.stream_of(out))
         qs._absmax_f32 = out
     return qs._absmax_f32
 
@@ -169,10 +166,8 @@ def quantize_nf4(W, blocksize=64, compress_statistics=True):
         raise ValueError(f"numel {n} is not a multiple of blocksize {blocksize}")
     packed = torch.empty((n // 2, 1), dtype=torch.uint8, device=W.device)
     absmax = torch.empty(n // blocksize, dtype=torch.float32, device=W.device)
-    with _lib.device_ctx(W):
-        rc = _lib.lib().uamd_nf4_quantize(_lib.ptr(W), _lib.ptr(packed), _lib.ptr(absmax), n, blocksize,
-                                          _lib.dtype_code(W.dtype), _lib.stream_of(W))
-    _lib.check(rc, "uamd_nf4_quantize")
+    _lib.call("uamd_nf4_quantize", W, _lib.ptr(W), _lib.ptr(packed), _lib.ptr(absmax), n, blocksize, _lib.dtype_code(W.dtype),
+              _lib.stream_of(W))
     code = torch.tensor(NF4_CODE, dtype=torch.float32, device=W.device)
     if compress_statistics:
         offset = absmax.mean()
@@ -372,21 +367,15 @@ def dequantize_nf4(packed, quant_state, out=None, transpose=False, use_global_bu
         assert transpose or out.is_contiguous(), "a strided destination is only supported by the transposing kernel"
     ld_out = out.stride(0)
     lut = qs.code
-    with _lib.device_ctx(packed):
-        if qs.nested and not cache_absmax:
-            if getattr(qs, "_offset_f", None) is None:
-                qs._offset_f = float(qs.offset)   # one device sync per weight, then cached
-            rc = _lib.lib().uamd_nf4_dequantize(
-                _lib.ptr(packed), None, _lib.ptr(qs.absmax), _lib.ptr(qs.state2.code),
-                _lib.ptr(qs.state2.absmax), qs._offset_f, qs.state2.blocksize, _lib.ptr(lut),
-                _lib.ptr(out), rows, cols, qs.blocksize, _lib.dtype_code(dtype), int(transpose), ld_out,
-                _lib.stream_of(packed))
-        else:
-            rc = _lib.lib().uamd_nf4_dequantize(
-                _lib.ptr(packed), _lib.ptr(absmax_f32(qs)), None, None, None, 0.0, 0, _lib.ptr(lut),
-                _lib.ptr(out), rows, cols, qs.blocksize, _lib.dtype_code(dtype), int(transpose), ld_out,
-                _lib.stream_of(packed))
-    _lib.check(rc, "uamd_nf4_dequantize")
+    if qs.nested and not cache_absmax:
+        if getattr(qs, "_offset_f", None) is None:
+            qs._offset_f = float(qs.offset)   # one device sync per weight, then cached
+        absmax = (None, _lib.ptr(qs.absmax), _lib.ptr(qs.state2.code), _lib.ptr(qs.state2.absmax), qs._offset_f,
+                  qs.state2.blocksize)
+    else:
+        absmax = (_lib.ptr(absmax_f32(qs)), None, None, None, 0.0, 0)
+    _lib.call("uamd_nf4_dequantize", packed, _lib.ptr(packed), *absmax, _lib.ptr(lut), _lib.ptr(out), rows, cols, qs.blocksize,
+              _lib.dtype_code(dtype), int(transpose), ld_out, _lib.stream_of(packed))
     if mirror_here:
         qs._resident = out
         _MIRRORED.add(qs)
@@ -409,20 +398,17 @@ def dequantize_nf4_group(packed_list, qs_list, outs):
             dequantize_nf4(pk, q, out=o)
         return outs
     _lib.require_gpu(packed_list[0])
-    L = _lib.lib()
-    with _lib.device_ctx(packed_list[0]):
-        for i in range(0, len(qs_list), 4):
-            pk, qs, os_ = packed_list[i:i + 4], qs_list[i:i + 4], outs[i:i + 4]
-            n = len(qs)
-            vp = _lib.ctypes.c_void_p
-            a_pk = (vp * n)(*[_lib.ptr(x) for x in pk])
-            a_am = (vp * n)(*[_lib.ptr(absmax_f32(q)) for q in qs])
-            a_out = (vp * n)(*[_lib.ptr(o) for o in os_])
-            a_n = (_lib.ctypes.c_int64 * n)(*[q.shape[0] * q.shape[1] for q in qs])
-            a_lut = (vp * n)(*[_lib.ptr(q.code) for q in qs])
-            rc = L.uamd_nf4_dequantize_multi(n, a_pk, a_am, a_out, a_n, a_lut, first.blocksize,
-                                             _lib.dtype_code(first.dtype), _lib.stream_of(pk[0]))
-            _lib.check(rc, "uamd_nf4_dequantize_multi")
+    for i in range(0, len(qs_list), 4):
+        pk, qs, os_ = packed_list[i:i + 4], qs_list[i:i + 4], outs[i:i + 4]
+        n = len(qs)
+        vp = _lib.ctypes.c_void_p
+        a_pk = (vp * n)(*[_lib.ptr(x) for x in pk])
+        a_am = (vp * n)(*[_lib.ptr(absmax_f32(q)) for q in qs])
+        a_out = (vp * n)(*[_lib.ptr(o) for o in os_])
+        a_n = (_lib.ctypes.c_int64 * n)(*[q.shape[0] * q.shape[1] for q in qs])
+        a_lut = (vp * n)(*[_lib.ptr(q.code) for q in qs])
+        _lib.call("uamd_nf4_dequantize_multi", pk[0], n, a_pk, a_am, a_out, a_n, a_lut, first.blocksize,
+                  _lib.dtype_code(first.dtype), _lib.stream_of(pk[0]))
     return outs
 
 
