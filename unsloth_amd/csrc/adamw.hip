@@ -115,12 +115,7 @@ extern "C" int uamd_adamw_shard(float* p32, const void* g16, void* p16, float* m
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks < 1) blocks = 1;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UAMD_BF16)
-        hipLaunchKernelGGL((adamw_shard_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 0, st, a, (const bf16_t*)g16, (bf16_t*)p16);
-    else if (dtype == UAMD_F16)
-        hipLaunchKernelGGL((adamw_shard_kernel<f16_t>), dim3((unsigned)blocks), dim3(256), 0, st, a, (const f16_t*)g16, (f16_t*)p16);
-    else
-        return UAMD_ERR_DTYPE;
+    UAMD_DISPATCH_HALF(dtype, hipLaunchKernelGGL((adamw_shard_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, a, (const T*)g16, (T*)p16))
     return uamd_launch_status();
 }
 

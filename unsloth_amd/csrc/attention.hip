@@ -1806,17 +1806,6 @@ extern "C" int uamd_debug_attn_trace(unsigned* buf) {
 }
 #endif
 
-template <typename K_>
-int set_lds_attr(K_ kernel, int bytes, bool* done) {
-    if (!*done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return (int)e;
-        *done = true;
-    }
-    return 0;
-}
-
 extern "C" int uamd_attn_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO,
                              const float* LSE, void* dQ, void* dK, void* dV, float* Delta,
                              const int64_t* strides, int B, int T, int Hq, int Hk, int D, int lse_stride,
@@ -1862,40 +1851,18 @@ extern "C" int uamd_attn_bwd(const void* Q, const void* K, const void* V, const 
     AttnBwdArgs ak = a;                                       // dK / dV: the real KV heads, all G query heads of each
     ak.Hk = Hk; ak.G = G; ak.kvm = 1;
     hipStream_t st = (hipStream_t)stream;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int rc;
     // two launches: dQ (+ Delta, LSE log2 e) with the forward's tiling, then dK / dV with one wave per SIMD x 64 keys
-    auto run = [&](auto tag) -> int {
-        typedef decltype(tag) T;
-        constexpr int ti = std::is_same<T, bf16_t>::value ? 0 : 1;
-        static bool done_dq[2][2][3][64] = {}, done_kd[2][64] = {};
-        int rc_;
+    UAMD_DISPATCH_HALF(dtype,
         // head-dim class of the dQ kernel: 64 / 96 / 128 columns computed (attn_fwd_kernel's DC)
-        auto dq = [&](auto band_c, auto dc_c) -> int {
-            constexpr bool BAND_ = decltype(band_c)::value;
-            constexpr int DC_ = decltype(dc_c)::value;
-            int r_;
-            if ((r_ = set_lds_attr(&attn_bwd_dq_kernel<T, BAND_, DC_>, ATTN_LDS, &done_dq[ti][BAND_][DC_ / 32 - 2][dev]))) return r_;
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, BAND_, DC_>), grid_q, dim3(512), ATTN_LDS, st, a);
-            return 0;
+        auto dq = [&](auto band_c) -> int {
+            constexpr bool BAND = decltype(band_c)::value;
+            if (D > 96) return uamd_launch_lds<&attn_bwd_dq_kernel<T, BAND, 128>>(grid_q, dim3(512), ATTN_LDS, st, a);
+            if (D > 64) return uamd_launch_lds<&attn_bwd_dq_kernel<T, BAND, 96>>(grid_q, dim3(512), ATTN_LDS, st, a);
+            return uamd_launch_lds<&attn_bwd_dq_kernel<T, BAND, 64>>(grid_q, dim3(512), ATTN_LDS, st, a);
         };
-        auto dq_b = [&](auto band_c) -> int {
-            if (D > 96) return dq(band_c, std::integral_constant<int, 128>{});
-            if (D > 64) return dq(band_c, std::integral_constant<int, 96>{});
-            return dq(band_c, std::integral_constant<int, 64>{});
-        };
-        if ((rc_ = lo ? dq_b(std::true_type{}) : dq_b(std::false_type{}))) return rc_;
-        if ((rc_ = uamd_launch_status())) return rc_;
-        if ((rc_ = set_lds_attr(&attn_bwd_dkdv4_kernel<T>, KD4_LDS, &done_kd[ti][dev]))) return rc_;
-        hipLaunchKernelGGL((attn_bwd_dkdv4_kernel<T>), grid_k, dim3(256), KD4_LDS, st, ak);
-        return 0;
-    };
-    if (dtype == UAMD_BF16) rc = run(bf16_t{});
-    else if (dtype == UAMD_F16) rc = run(f16_t{});
-    else return UAMD_ERR_DTYPE;
-    if (rc) return rc;
-    return uamd_launch_status();
+        if (int rc = lo ? dq(std::true_type{}) : dq(std::false_type{})) return rc;
+        return uamd_launch_lds<&attn_bwd_dkdv4_kernel<T>>(grid_k, dim3(256), KD4_LDS, st, ak))
+    return UAMD_ERR_DTYPE;
 }
 
 // {claim counter, finished workgroups} pairs of the persistent forward's dynamic deal: a pool per device, handed out round-robin
@@ -1953,14 +1920,7 @@ static int attn_fwd_impl(const void* Q, const void* K, const void* V, void* O, f
     a.nqt = (T + QT - 1) / QT;
     dim3 grid((unsigned)(a.nqt * a.Hk * B));
     hipStream_t st = (hipStream_t)stream;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int rc;
-    static int ncu[64] = {};
-    if (!ncu[dev]) {
-        hipDeviceProp_t pr;
-        ncu[dev] = (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-    }
+    const int n_cu = uamd_cu_count_or_256();
     // Plain causal batches with at least two work items per CU take the PERSISTENT kernel (one workgroup per CU walks the items,
     // dealt statically: +2-3 % at 4 x 2048 / 2 x 4096 tokens, profiles/r04_attn_ab_persistent.jsonl); packed / windowed batches,
     // small grids and non-causal bands take one block per item. For packed / windowed batches the persistent kernel exists in two
@@ -1973,40 +1933,25 @@ static int attn_fwd_impl(const void* Q, const void* K, const void* V, void* O, f
     // launches: claimed items), bit 3 = band launches keep the static deal. 32-bit Q row offsets: T * q_st < 2^31.
     const int var = uamd_tuning_get(UAMD_TUNE_ATTN_VAR);
     bool persistent = !(var & 1) && D == AD && !hi && (int64_t)T * strides[1] < (1ll << 31) &&
-                      ((var & 2) || (!lo && (int)grid.x >= 2 * ncu[dev]));
+                      ((var & 2) || (!lo && (int)grid.x >= 2 * n_cu));
     a.ctr = nullptr;
-    if (persistent && lo && !(var & 8)) a.ctr = attn_ctr_slot(dev, (hipStream_t)stream);    // (nullptr inside a capture: static deal)
-    auto run = [&](auto tag) -> int {
-        typedef decltype(tag) T;
-        constexpr int ti = std::is_same<T, bf16_t>::value ? 0 : 1;
-        static bool done[2][2][2][64] = {}, done_dyn[2][64] = {};
-        auto go = [&](auto kernel, int nblk, int lds, bool* d) -> int {
-            int r_;
-            if ((r_ = set_lds_attr(kernel, lds, d))) return r_;
-            hipLaunchKernelGGL(kernel, dim3(nblk), dim3(512), lds, st, a);
-            return 0;
-        };
+    if (persistent && lo && !(var & 8)) a.ctr = attn_ctr_slot(uamd_device_slot(), st);    // (nullptr inside a capture: static deal)
+    UAMD_DISPATCH_HALF(dtype,
         if (persistent) {
-            const int nwg = (int)grid.x < ncu[dev] ? (int)grid.x : ncu[dev];
-            if (a.ctr) return go(&attn_fwd_ps_kernel<T, true, true>, nwg, ATTN_PS_LDS, &done_dyn[ti][dev]);
-            return lo ? go(&attn_fwd_ps_kernel<T, true, false>, nwg, ATTN_PS_LDS, &done[ti][1][1][dev])
-                      : go(&attn_fwd_ps_kernel<T, false, false>, nwg, ATTN_PS_LDS, &done[ti][0][1][dev]);
+            const dim3 nwg((unsigned)((int)grid.x < n_cu ? (int)grid.x : n_cu));
+            if (a.ctr) return uamd_launch_lds<&attn_fwd_ps_kernel<T, true, true>>(nwg, dim3(512), ATTN_PS_LDS, st, a);
+            return lo ? uamd_launch_lds<&attn_fwd_ps_kernel<T, true, false>>(nwg, dim3(512), ATTN_PS_LDS, st, a)
+                      : uamd_launch_lds<&attn_fwd_ps_kernel<T, false, false>>(nwg, dim3(512), ATTN_PS_LDS, st, a);
         }
-        static bool done_dc[2][2][2][64] = {};          // the head-dim classes 64 / 96 (128: `done` above)
-        if (D > 96)
-            return lo ? go(&attn_fwd_kernel<T, true, 128>, (int)grid.x, ATTN_LDS, &done[ti][1][0][dev])
-                      : go(&attn_fwd_kernel<T, false, 128>, (int)grid.x, ATTN_LDS, &done[ti][0][0][dev]);
-        if (D > 64)
-            return lo ? go(&attn_fwd_kernel<T, true, 96>, (int)grid.x, ATTN_LDS, &done_dc[ti][1][1][dev])
-                      : go(&attn_fwd_kernel<T, false, 96>, (int)grid.x, ATTN_LDS, &done_dc[ti][0][1][dev]);
-        return lo ? go(&attn_fwd_kernel<T, true, 64>, (int)grid.x, ATTN_LDS, &done_dc[ti][1][0][dev])
-                  : go(&attn_fwd_kernel<T, false, 64>, (int)grid.x, ATTN_LDS, &done_dc[ti][0][0][dev]);
-    };
-    if (dtype == UAMD_BF16) rc = run(bf16_t{});
-    else if (dtype == UAMD_F16) rc = run(f16_t{});
-    else return UAMD_ERR_DTYPE;
-    if (rc) return rc;
-    return uamd_launch_status();
+        // one block per item, by head-dim class: 64 / 96 / 128 columns computed
+        auto fwd = [&](auto band_c) -> int {
+            constexpr bool BAND = decltype(band_c)::value;
+            if (D > 96) return uamd_launch_lds<&attn_fwd_kernel<T, BAND, 128>>(grid, dim3(512), ATTN_LDS, st, a);
+            if (D > 64) return uamd_launch_lds<&attn_fwd_kernel<T, BAND, 96>>(grid, dim3(512), ATTN_LDS, st, a);
+            return uamd_launch_lds<&attn_fwd_kernel<T, BAND, 64>>(grid, dim3(512), ATTN_LDS, st, a);
+        };
+        return lo ? fwd(std::true_type{}) : fwd(std::false_type{}))
+    return UAMD_ERR_DTYPE;
 }
 
 extern "C" int uamd_attn_fwd(const void* Q, const void* K, const void* V, void* O, float* LSE,

@@ -191,11 +191,71 @@ static inline int uamd_launch_status() {
     return e == hipSuccess ? UAMD_OK : (int)e;
 }
 
+// The per-device host caches below hold UAMD_DEVICE_SLOTS entries; a device index outside them shares slot 0.
+#define UAMD_DEVICE_SLOTS 64
+
+// current device index if it has a slot of its own, else -1 (query failed or index out of range): for the callers that
+// answer "no" rather than assume device 0
+static inline int uamd_device_slot_or_neg() {
+    int dev = 0;
+    return (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < UAMD_DEVICE_SLOTS) ? dev : -1;
+}
+static inline int uamd_device_slot() {
+    const int dev = uamd_device_slot_or_neg();
+    return dev < 0 ? 0 : dev;
+}
+
+// Opt `Kernel` into `bytes` of dynamic LDS (more than 48 KiB needs the attribute), once per device. Keyed by the kernel
+// itself: every instantiation owns its flags. UAMD_OK or the HIP error.
+template <auto Kernel>
+static int uamd_lds_optin(int bytes) {
+    static bool done[UAMD_DEVICE_SLOTS] = {false};
+    const int dev = uamd_device_slot();
+    if (!done[dev]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return (int)e;
+        done[dev] = true;
+    }
+    return UAMD_OK;
+}
+
+// opt in, launch, report: the whole host side of a kernel that takes `lds` bytes of dynamic LDS above 48 KiB
+template <auto Kernel, typename... Args>
+static int uamd_launch_lds(dim3 grid, dim3 block, int lds, hipStream_t st, const Args&... args) {
+    if (int rc = uamd_lds_optin<Kernel>(lds)) return rc;
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    return uamd_launch_status();
+}
+
+// Compute units of the current device, cached per device slot (a failed query too); 0 when the query fails. The GEMM
+// and the attention forward size persistent grids with it and take 256 (an MI355X) for 0; the decode's fused attention
+// needs the real number for its co-residency proof and takes 0 as "do not take the fused path".
+static inline int uamd_cu_count() {
+    static int n[UAMD_DEVICE_SLOTS] = {0};      // 0 = not asked yet, -1 = the query failed
+    const int dev = uamd_device_slot();
+    if (n[dev] == 0) {
+        int v = 0;
+        n[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : -1;
+    }
+    return n[dev] > 0 ? n[dev] : 0;
+}
+static inline int uamd_cu_count_or_256() {
+    const int n = uamd_cu_count();
+    return n > 0 ? n : 256;
+}
+
 // dispatch helper over the three activation dtypes
 #define UAMD_DISPATCH_FLOAT(dtype, ...)                       \
     switch (dtype) {                                          \
         case UAMD_F32: { using T = float; __VA_ARGS__; break; }  \
         case UAMD_F16: { using T = f16_t; __VA_ARGS__; break; }  \
         case UAMD_BF16: { using T = bf16_t; __VA_ARGS__; break; } \
+        default: return UAMD_ERR_DTYPE;                       \
+    }
+// ... and over the two 16-bit ones (the MFMA kernels)
+#define UAMD_DISPATCH_HALF(dtype, ...)                        \
+    switch (dtype) {                                          \
+        case UAMD_BF16: { using T = bf16_t; __VA_ARGS__; break; } \
+        case UAMD_F16: { using T = f16_t; __VA_ARGS__; break; }  \
         default: return UAMD_ERR_DTYPE;                       \
     }

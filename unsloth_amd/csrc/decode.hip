@@ -679,15 +679,8 @@ template <typename T, bool NF4, int NIT, int RB>
 int launch_gemv_n(const GemvArgs& a0, hipStream_t st) {
     constexpr int ELEMS = NF4 ? 32 : 8;
     const int lds = NIT * 64 * ELEMS * (int)sizeof(T) + UAMD_GEMV_MAX_GROUPS * 256 * 4 + (NF4 ? 256 * 32 * 4 : 0) + (256 + 16) * 4;
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (lds > 48 * 1024 && !attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_kernel<T, NF4, NIT, RB>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev] = true;
-    }
+    if (lds > 48 * 1024)
+        if (int rc = uamd_lds_optin<&gemv_kernel<T, NF4, NIT, RB>>(lds)) return rc;
     if (a0.pro.glu && RB < 2) return UAMD_ERR_ARG;                // a wave needs the gate row and the up row in one trip
     GemvArgs a = a0;
     int trips = 0;
@@ -1277,8 +1270,7 @@ static int gemv_entry(const void* x, int K, const uamd_gemv_group* groups, int n
         for (int i = 0; i < UAMD_GEMV_MAX_GROUPS; ++i) a.pro.t_off[i] = 0;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UAMD_BF16) return nf4 ? launch_gemv<bf16_t, true>(a, st) : launch_gemv<bf16_t, false>(a, st);
-    if (dtype == UAMD_F16) return nf4 ? launch_gemv<f16_t, true>(a, st) : launch_gemv<f16_t, false>(a, st);
+    UAMD_DISPATCH_HALF(dtype, return nf4 ? launch_gemv<T, true>(a, st) : launch_gemv<T, false>(a, st))
     return UAMD_ERR_DTYPE;
 }
 
@@ -1309,16 +1301,9 @@ extern "C" int uamd_rope_kv_append(void* qkv, int64_t ld_qkv, const void* cos_t,
     if (!qkv || !cos_t || !sin_t || !kv_len || !k_cache || !v_cache || B <= 0 || Hq <= 0 || Hk <= 0 || D <= 0 || (D & 1))
         return UAMD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UAMD_BF16)
-        hipLaunchKernelGGL((rope_append_kernel<bf16_t>), dim3(Hq + 2 * Hk, B), dim3(64), 0, st, (bf16_t*)qkv, ld_qkv, (const bf16_t*)cos_t,
-                           (const bf16_t*)sin_t, ld_cs, kv_len, rope_pos, (bf16_t*)k_cache, (bf16_t*)v_cache, cache_sb,
-                           cache_sh, Hq, Hk, D, s_max);
-    else if (dtype == UAMD_F16)
-        hipLaunchKernelGGL((rope_append_kernel<f16_t>), dim3(Hq + 2 * Hk, B), dim3(64), 0, st, (f16_t*)qkv, ld_qkv, (const f16_t*)cos_t,
-                           (const f16_t*)sin_t, ld_cs, kv_len, rope_pos, (f16_t*)k_cache, (f16_t*)v_cache, cache_sb,
-                           cache_sh, Hq, Hk, D, s_max);
-    else
-        return UAMD_ERR_DTYPE;
+    UAMD_DISPATCH_HALF(dtype, hipLaunchKernelGGL((rope_append_kernel<T>), dim3(Hq + 2 * Hk, B), dim3(64), 0, st, (T*)qkv, ld_qkv,
+                                                 (const T*)cos_t, (const T*)sin_t, ld_cs, kv_len, rope_pos, (T*)k_cache,
+                                                 (T*)v_cache, cache_sb, cache_sh, Hq, Hk, D, s_max))
     return uamd_launch_status();
 }
 
@@ -1348,21 +1333,12 @@ extern "C" int uamd_attn_decode(const void* q, int64_t q_sb, const void* k_cache
         case 7: UAMD_DECODE_LAUNCH(TT, 7); break; case 8: UAMD_DECODE_LAUNCH(TT, 8); break;           \
         default: return UAMD_ERR_ARG;                                                                 \
     }
-    if (dtype == UAMD_BF16) {
-        UAMD_DECODE_G(bf16_t)
-    } else if (dtype == UAMD_F16) {
-        UAMD_DECODE_G(f16_t)
-    } else {
-        return UAMD_ERR_DTYPE;
-    }
+    UAMD_DISPATCH_HALF(dtype,
+        UAMD_DECODE_G(T)
+        if (int rc = uamd_launch_status()) return rc;
+        hipLaunchKernelGGL((attn_decode_combine_kernel<T>), dim3(Hq, B), dim3(DD), 0, st, partials, (T*)out, out_sb, Hq, nsplit))
 #undef UAMD_DECODE_G
 #undef UAMD_DECODE_LAUNCH
-    int rc = uamd_launch_status();
-    if (rc) return rc;
-    if (dtype == UAMD_BF16)
-        hipLaunchKernelGGL((attn_decode_combine_kernel<bf16_t>), dim3(Hq, B), dim3(DD), 0, st, partials, (bf16_t*)out, out_sb, Hq, nsplit);
-    else
-        hipLaunchKernelGGL((attn_decode_combine_kernel<f16_t>), dim3(Hq, B), dim3(DD), 0, st, partials, (f16_t*)out, out_sb, Hq, nsplit);
     return uamd_launch_status();
 }
 
@@ -1373,17 +1349,17 @@ namespace {
 // that starts only after another exits would be waited for in vain: 2^18 polls, then NaN). Cached per device.
 template <typename T, int G>
 int attn_fused_resident_blocks() {
-    static int cap[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    static int cap[UAMD_DEVICE_SLOTS];
+    const int dev = uamd_device_slot_or_neg();
+    if (dev < 0) return 0;
     if (cap[dev] == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_decode_fused_kernel<T, G>, 256, 0) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+        int per_cu = 0;
+        const int cus = uamd_cu_count();
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_decode_fused_kernel<T, G>, 256, 0) != hipSuccess || cus == 0) {
             (void)hipGetLastError();
             return 0;
         }
-        cap[dev] = per_cu >= 1 && cus >= 1 ? cus : -1;
+        cap[dev] = per_cu >= 1 ? cus : -1;
     }
     return cap[dev] > 0 ? cap[dev] : 0;
 }
@@ -1427,13 +1403,7 @@ extern "C" int uamd_attn_decode_fused(const void* qkv, int64_t ld_qkv, const voi
         case 7: UAMD_DECODE_LAUNCH(TT, 7); break; case 8: UAMD_DECODE_LAUNCH(TT, 8); break;           \
         default: return UAMD_ERR_ARG;                                                                 \
     }
-    if (dtype == UAMD_BF16) {
-        UAMD_DECODE_G(bf16_t)
-    } else if (dtype == UAMD_F16) {
-        UAMD_DECODE_G(f16_t)
-    } else {
-        return UAMD_ERR_DTYPE;
-    }
+    UAMD_DISPATCH_HALF(dtype, UAMD_DECODE_G(T))
 #undef UAMD_DECODE_G
 #undef UAMD_DECODE_LAUNCH
     return uamd_launch_status();

@@ -334,18 +334,7 @@ __global__ void __launch_bounds__(256) lora_xa_kernel(const T* __restrict__ X, i
 template <typename T, bool NF4>
 int launch_gemm(const GemmArgs& a, int total_tiles, hipStream_t st) {
     const int smem = SMEM_BYTES + (NF4 ? 64 : 0);
-    static bool attr_set[64] = {false};   // >48 KiB dynamic LDS needs the opt-in attribute, per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<T, NF4>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL((gemm_nt_kernel<T, NF4>), dim3((unsigned)total_tiles), dim3(256), smem, st, a);
-    return uamd_launch_status();
+    return uamd_launch_lds<&gemm_nt_kernel<T, NF4>>(dim3((unsigned)total_tiles), dim3(256), smem, st, a);
 }
 
 int gemm_entry(const void* A, int64_t lda, int M, int K, const uamd_gemm_group* groups, int n_groups,
@@ -380,8 +369,7 @@ int gemm_entry(const void* A, int64_t lda, int M, int K, const uamd_gemm_group* 
     const int64_t total = (int64_t)tn * a.tiles_m;
     if (total > 0x7fffffffLL) return UAMD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UAMD_BF16) return nf4 ? launch_gemm<bf16_t, true>(a, (int)total, st) : launch_gemm<bf16_t, false>(a, (int)total, st);
-    if (dtype == UAMD_F16) return nf4 ? launch_gemm<f16_t, true>(a, (int)total, st) : launch_gemm<f16_t, false>(a, (int)total, st);
+    UAMD_DISPATCH_HALF(dtype, return nf4 ? launch_gemm<T, true>(a, (int)total, st) : launch_gemm<T, false>(a, (int)total, st))
     return UAMD_ERR_DTYPE;
 }
 
@@ -437,8 +425,6 @@ extern "C" int uamd_lora_xa(const void* X, int64_t ldx, const void* A, int64_t l
     if (M < 0 || K <= 0 || R <= 0 || out_cols < R || R > 192 || out_cols > 256) return UAMD_ERR_ARG;
     if (M == 0) return UAMD_OK;
     if ((K & 7) || (ldx & 7) || (lda & 7) || !aligned16(X) || !aligned16(A)) return UAMD_ERR_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == UAMD_BF16) return launch_xa<bf16_t>(X, ldx, A, lda, out, ld_out, M, K, R, out_cols, st);
-    if (dtype == UAMD_F16) return launch_xa<f16_t>(X, ldx, A, lda, out, ld_out, M, K, R, out_cols, st);
+    UAMD_DISPATCH_HALF(dtype, return launch_xa<T>(X, ldx, A, lda, out, ld_out, M, K, R, out_cols, (hipStream_t)stream))
     return UAMD_ERR_DTYPE;
 }

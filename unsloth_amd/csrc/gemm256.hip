@@ -1322,35 +1322,13 @@ __global__ void __launch_bounds__(512, 2) gemm_nt256h_kernel(G256Args p) {
 
 template <typename T, bool BNN>
 int launch256h(const G256Args& a, hipStream_t st) {
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt256h_kernel<T, BNN>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_H);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL((gemm_nt256h_kernel<T, BNN>), dim3((unsigned)a.total_tiles), dim3(512), LDS_H, st, a);
-    return uamd_launch_status();
+    return uamd_launch_lds<&gemm_nt256h_kernel<T, BNN>>(dim3((unsigned)a.total_tiles), dim3(512), LDS_H, st, a);
 }
 
 template <typename T, bool BNN, int VAR, bool PERSIST>
 int launch256s_(const G256Args& a, hipStream_t st, int grid) {
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt256s_kernel<T, BNN, VAR, PERSIST>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL((gemm_nt256s_kernel<T, BNN, VAR, PERSIST>), dim3((unsigned)grid), dim3(256), LDS_BYTES, st, a);
-    return uamd_launch_status();
+    return uamd_launch_lds<&gemm_nt256s_kernel<T, BNN, VAR, PERSIST>>(dim3((unsigned)grid), dim3(256), LDS_BYTES, st, a);
 }
-
-int cu_count();
 
 // UAMD_TUNE_GEMM_S: 1 = by tile count (the persistent walk when every CU gets at least FOUR output tiles, one workgroup per tile
 // otherwise), 2 = one workgroup per tile always, 9 = the walk from two tiles per CU on (tests), 0 = the 8-wave kernels
@@ -1370,60 +1348,40 @@ int launch256s(const G256Args& a, hipStream_t st) {
         if (v == 8) return launch256s_<T, false, 7, false>(a, st, a.total_tiles);
     }
 #endif
-    const int n_cu = cu_count();
+    const int n_cu = uamd_cu_count_or_256();
     if (v != 2 && (n_cu & 7) == 0 && a.total_tiles >= (v == 9 ? 2 : 4) * n_cu) return launch256s_<T, BNN, 0, true>(a, st, n_cu);
     return launch256s_<T, BNN, 0, false>(a, st, a.total_tiles);
 }
 
 template <typename T, bool BNN, bool ATN = false>
 int launch256(const G256Args& a, hipStream_t st) {
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt256_kernel<T, BNN, ATN>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL((gemm_nt256_kernel<T, BNN, ATN>), dim3((unsigned)a.total_tiles), dim3(512), LDS_BYTES, st, a);
-    return uamd_launch_status();
+    return uamd_launch_lds<&gemm_nt256_kernel<T, BNN, ATN>>(dim3((unsigned)a.total_tiles), dim3(512), LDS_BYTES, st, a);
 }
 
-template <typename T, bool BNN, bool PLAIN>
-int launch256p_(const G256Args& a, hipStream_t st, int n_cu) {
-    static bool attr_set[64] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt256p_kernel<T, BNN, PLAIN>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-        attr_set[dev] = true;
-    }
-    const int grid = a.total_tiles < n_cu ? a.total_tiles : n_cu;
-    hipLaunchKernelGGL((gemm_nt256p_kernel<T, BNN, PLAIN>), dim3((unsigned)grid), dim3(512), LDS_BYTES, st, a);
-    return uamd_launch_status();
-}
-
+// one persistent block per compute unit (128 KiB of the CU's 160 KiB LDS)
 template <typename T, bool BNN>
 int launch256p(const G256Args& a, hipStream_t st, int n_cu) {
     bool plain = !a.accumulate && uamd_tuning_get(UAMD_TUNE_GEMM_PLAIN) != 0;
     for (int i = 0; i < a.n_groups; ++i) plain = plain && a.g[i].bias == nullptr;
-    return plain ? launch256p_<T, BNN, true>(a, st, n_cu) : launch256p_<T, BNN, false>(a, st, n_cu);
+    const dim3 grid((unsigned)(a.total_tiles < n_cu ? a.total_tiles : n_cu));
+    return plain ? uamd_launch_lds<&gemm_nt256p_kernel<T, BNN, true>>(grid, dim3(512), LDS_BYTES, st, a)
+                 : uamd_launch_lds<&gemm_nt256p_kernel<T, BNN, false>>(grid, dim3(512), LDS_BYTES, st, a);
 }
 
-// compute units of the current device (one persistent block each: 128 KiB of the CU's 160 KiB LDS)
-int cu_count() {
-    static int n[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (n[dev] == 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        n[dev] = v;
+// which kernel family a launch takes (gemm256_entry decides, launch256_as runs it for the dtype and B layout)
+enum G256Path { G256_ATN, G256_HALF, G256_S, G256_PERSIST, G256_PLAIN };
+
+template <typename T, bool BNN>
+int launch256_as(G256Path path, const G256Args& a, hipStream_t st, int n_cu) {
+    switch (path) {
+        case G256_ATN:
+            if constexpr (BNN) return launch256<T, true, true>(a, st);
+            else return UAMD_ERR_ARG;           // A^T takes B [K, N] only (checked by the entry point)
+        case G256_HALF: return launch256h<T, BNN>(a, st);
+        case G256_S: return launch256s<T, BNN>(a, st);
+        case G256_PERSIST: return launch256p<T, BNN>(a, st, n_cu);
+        default: return launch256<T, BNN>(a, st);
     }
-    return n[dev];
 }
 
 }  // namespace
@@ -1433,6 +1391,15 @@ extern "C" int uamd_debug_g256_trace(unsigned* buf) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_trace256), &buf, sizeof(buf));
 }
 #endif
+
+// every group whole 256-column tiles, with C rows (and bias) that take 16-byte stores
+static bool whole_tiles(const uamd_gemm_group* groups, int n_groups) {
+    bool whole = true;
+    for (int i = 0; i < n_groups; ++i)
+        whole = whole && (groups[i].N & (TN - 1)) == 0 && (groups[i].ldc & 7) == 0 && aligned16(groups[i].C) &&
+                (groups[i].bias == nullptr || (reinterpret_cast<uintptr_t>(groups[i].bias) & 7) == 0);
+    return whole;
+}
 
 // Same contract as uamd_gemm_nt (dense B), 256x256x64 tiles. Requires K % 64 == 0. The LoRA term comes as the
 // rank block lora_xk / lora_bk (extra K tiles); a group that only carries lora_xa / lora_b is rejected.
@@ -1496,42 +1463,27 @@ static int gemm256_entry(const void* A, int64_t lda, int M, int K, const uamd_ge
         const int gm = uamd_tuning_get(UAMD_TUNE_GROUP_M);
         a.group_m = gm < 1 ? 1 : (gm < a.tiles_m ? gm : a.tiles_m);
     }
-    hipStream_t st = (hipStream_t)stream;
+    // the kernel family
+    G256Path path = G256_PLAIN;
+    int n_cu = 0;
     if (atn) {
-        if (dtype == UAMD_BF16) return launch256<bf16_t, true, true>(a, st);
-        if (dtype == UAMD_F16) return launch256<f16_t, true, true>(a, st);
-        return UAMD_ERR_DTYPE;
+        path = G256_ATN;
+    } else if (half) {
+        path = G256_HALF;
+    } else if (K >= 3 * TK && (M & (TM - 1)) == 0 && uamd_tuning_get(UAMD_TUNE_GEMM_S) != 0 && whole_tiles(groups, n_groups)) {
+        path = G256_S;                          // whole-tile NT / NN launches: the one-wave-per-SIMD kernel (UAMD_TUNE_GEMM_S)
+    } else {
+        // persistent walk (UAMD_TUNE_GEMM_PERSIST: 1 = when every CU gets >= 4 tiles (default), 2 = whenever it gets more
+        // than one, 0 = never). Measured (profiles/r02i_gemm_persist_ab.txt): +0.5 % at 7 tiles per CU, -2.5 % .. 0 at 2
+        // tiles per CU (static assignment loses the dispatcher's balancing) -- the kernel is power-limited, idle slots it
+        // removes come back as clock.
+        n_cu = uamd_cu_count_or_256();
+        const int persist = uamd_tuning_get(UAMD_TUNE_GEMM_PERSIST);
+        if (persist && K >= 4 * TK && (n_cu & 7) == 0 && a.total_tiles > n_cu && (persist >= 2 || a.total_tiles >= 4 * n_cu))
+            path = G256_PERSIST;
     }
-    if (half) {
-        if (dtype == UAMD_BF16) return bnn ? launch256h<bf16_t, true>(a, st) : launch256h<bf16_t, false>(a, st);
-        if (dtype == UAMD_F16) return bnn ? launch256h<f16_t, true>(a, st) : launch256h<f16_t, false>(a, st);
-        return UAMD_ERR_DTYPE;
-    }
-    // whole-tile NT / NN launches: the one-wave-per-SIMD kernel (UAMD_TUNE_GEMM_S)
-    if (K >= 3 * TK && (M & (TM - 1)) == 0 && uamd_tuning_get(UAMD_TUNE_GEMM_S) != 0) {
-        bool whole = true;                      // ... and C rows that take 16-byte stores
-        for (int i = 0; i < n_groups; ++i)
-            whole = whole && (groups[i].N & (TN - 1)) == 0 && (groups[i].ldc & 7) == 0 && aligned16(groups[i].C) &&
-                    (groups[i].bias == nullptr || (reinterpret_cast<uintptr_t>(groups[i].bias) & 7) == 0);
-        if (whole) {
-            if (dtype == UAMD_BF16) return bnn ? launch256s<bf16_t, true>(a, st) : launch256s<bf16_t, false>(a, st);
-            if (dtype == UAMD_F16) return bnn ? launch256s<f16_t, true>(a, st) : launch256s<f16_t, false>(a, st);
-            return UAMD_ERR_DTYPE;
-        }
-    }
-    // persistent walk (UAMD_TUNE_GEMM_PERSIST: 1 = when every CU gets >= 4 tiles (default), 2 = whenever it gets more than
-    // one, 0 = never). Measured (profiles/r02i_gemm_persist_ab.txt): +0.5 % at 7 tiles per CU, -2.5 % .. 0 at 2 tiles per CU
-    // (static assignment loses the dispatcher's balancing) -- the kernel is power-limited, idle slots it removes come back
-    // as clock.
-    const int n_cu = cu_count();
-    const int persist = uamd_tuning_get(UAMD_TUNE_GEMM_PERSIST);
-    if (persist && K >= 4 * TK && (n_cu & 7) == 0 && a.total_tiles > n_cu && (persist >= 2 || a.total_tiles >= 4 * n_cu)) {
-        if (dtype == UAMD_BF16) return bnn ? launch256p<bf16_t, true>(a, st, n_cu) : launch256p<bf16_t, false>(a, st, n_cu);
-        if (dtype == UAMD_F16) return bnn ? launch256p<f16_t, true>(a, st, n_cu) : launch256p<f16_t, false>(a, st, n_cu);
-        return UAMD_ERR_DTYPE;
-    }
-    if (dtype == UAMD_BF16) return bnn ? launch256<bf16_t, true>(a, st) : launch256<bf16_t, false>(a, st);
-    if (dtype == UAMD_F16) return bnn ? launch256<f16_t, true>(a, st) : launch256<f16_t, false>(a, st);
+    hipStream_t st = (hipStream_t)stream;
+    UAMD_DISPATCH_HALF(dtype, return bnn ? launch256_as<T, true>(path, a, st, n_cu) : launch256_as<T, false>(path, a, st, n_cu))
     return UAMD_ERR_DTYPE;
 }
 

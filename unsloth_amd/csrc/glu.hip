@@ -611,9 +611,9 @@ glu_xa_kernel(T* __restrict__ DW, T* __restrict__ E, T* __restrict__ G, T* __res
 // buys nothing (launch_xa), so "the order of the sweep" is the mechanism for Llama-3-8B's MLP width, not a law.
 // is the current device one whose ISA the fence-free split hand-off was written for (see launch_xa)?
 inline bool split_handoff_ok() {
-    static int ok[64] = {0};            // 0 = unknown, 1 = yes, 2 = no
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+    static int ok[UAMD_DEVICE_SLOTS] = {0};   // 0 = unknown, 1 = yes, 2 = no
+    const int dev = uamd_device_slot_or_neg();
+    if (dev < 0) return false;
     if (ok[dev] == 0) {
         hipDeviceProp_t pr;
         bool y = false;
@@ -704,16 +704,11 @@ int glu_xa_entry(int act, void* dw, void* e, void* g, void* h, int M, int K, int
     if (NS > 1 && (rc = check_xa_out(o1, K))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (ws != nullptr && ws_floats < xa_ws_floats(M, K, NS, NS > 1 ? (o0.R > o1.R ? o0.R : o1.R) : o0.R)) return UAMD_ERR_ARG;
-#define GLU_XA_CASE(TT, DC)                                                                          \
-    if (dtype == DC) {                                                                              \
-        if (act == ACT_SWIGLU) return launch_xa<TT, ACT_SWIGLU, NS>(dw, e, g, h, M, K, ld, o0, o1, st, ws, counters);          \
-        if (act == ACT_GEGLU_EXACT) return launch_xa<TT, ACT_GEGLU_EXACT, NS>(dw, e, g, h, M, K, ld, o0, o1, st, ws, counters); \
-        if (act == ACT_GEGLU_APPROX) return launch_xa<TT, ACT_GEGLU_APPROX, NS>(dw, e, g, h, M, K, ld, o0, o1, st, ws, counters); \
-        return UAMD_ERR_ARG;                                                                        \
-    }
-    GLU_XA_CASE(bf16_t, UAMD_BF16)
-    GLU_XA_CASE(f16_t, UAMD_F16)
-#undef GLU_XA_CASE
+    UAMD_DISPATCH_HALF(dtype,
+        if (act == ACT_SWIGLU) return launch_xa<T, ACT_SWIGLU, NS>(dw, e, g, h, M, K, ld, o0, o1, st, ws, counters);
+        if (act == ACT_GEGLU_EXACT) return launch_xa<T, ACT_GEGLU_EXACT, NS>(dw, e, g, h, M, K, ld, o0, o1, st, ws, counters);
+        if (act == ACT_GEGLU_APPROX) return launch_xa<T, ACT_GEGLU_APPROX, NS>(dw, e, g, h, M, K, ld, o0, o1, st, ws, counters);
+        return UAMD_ERR_ARG)
     return UAMD_ERR_DTYPE;
 }
 

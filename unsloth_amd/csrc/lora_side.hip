@@ -435,18 +435,8 @@ __global__ void __launch_bounds__(256) lora_xa2_kernel(const T* __restrict__ X, 
 template <typename T, int NT>
 int launch_xa2(const void* X, int64_t ldx, const void* W, int64_t ldw, float* out, int64_t ld_out, void* out_k,
                int64_t ld_k, int k_cols, int M, int K, int R, int out_cols, hipStream_t st) {
-    static bool done[64] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lora_xa2_kernel<T, NT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, XaCfg<NT>::LDS);
-        if (e != hipSuccess) return (int)e;
-        done[dev] = true;
-    }
-    hipLaunchKernelGGL((lora_xa2_kernel<T, NT>), dim3((unsigned)((M + 31) / 32)), dim3(256), XaCfg<NT>::LDS, st,
-                       (const T*)X, ldx, (const T*)W, ldw, out, ld_out, (T*)out_k, ld_k, k_cols, M, K, R, out_cols);
-    return uamd_launch_status();
+    return uamd_launch_lds<&lora_xa2_kernel<T, NT>>(dim3((unsigned)((M + 31) / 32)), dim3(256), XaCfg<NT>::LDS, st, (const T*)X, ldx,
+                                                    (const T*)W, ldw, out, ld_out, (T*)out_k, ld_k, k_cols, M, K, R, out_cols);
 }
 
 template <typename T>
@@ -458,17 +448,6 @@ int xa2_dispatch(const void* X, int64_t ldx, const void* W, int64_t ldw, float* 
     if (nt <= 3) return launch_xa2<T, 3>(X, ldx, W, ldw, out, ld_out, out_k, ld_k, k_cols, M, K, R, out_cols, st);
     if (nt <= 4) return launch_xa2<T, 4>(X, ldx, W, ldw, out, ld_out, out_k, ld_k, k_cols, M, K, R, out_cols, st);
     return UAMD_ERR_ARG;
-}
-
-template <typename K_>
-int tn_set_attr(K_ kernel, bool* done) {
-    if (!*done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TN_WAVE_LDS);
-        if (e != hipSuccess) return (int)e;
-        *done = true;
-    }
-    return 0;
 }
 
 }  // namespace
@@ -515,20 +494,8 @@ extern "C" int uamd_lora_tn(const uamd_lora_tn_problem* probs, int n_probs, int 
     const int64_t blocks = ((int64_t)slabs * a.S + 3) / 4;
     if (blocks > 0x7fffffffLL) return UAMD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    static bool attr_set[2][64] = {{false}};
-    int dev = 0, rc;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (dtype == UAMD_BF16) {
-        if ((rc = tn_set_attr(&lora_tn_kernel<bf16_t>, &attr_set[0][dev]))) return rc;
-        hipLaunchKernelGGL((lora_tn_kernel<bf16_t>), dim3((unsigned)blocks), dim3(256), 4 * TN_WAVE_LDS, st, a);
-    } else if (dtype == UAMD_F16) {
-        if ((rc = tn_set_attr(&lora_tn_kernel<f16_t>, &attr_set[1][dev]))) return rc;
-        hipLaunchKernelGGL((lora_tn_kernel<f16_t>), dim3((unsigned)blocks), dim3(256), 4 * TN_WAVE_LDS, st, a);
-    } else {
-        return UAMD_ERR_DTYPE;
-    }
-    rc = uamd_launch_status();
-    if (rc) return rc;
+    UAMD_DISPATCH_HALF(dtype,
+        if (int rc = uamd_launch_lds<&lora_tn_kernel<T>>(dim3((unsigned)blocks), dim3(256), 4 * TN_WAVE_LDS, st, a)) return rc)
     hipLaunchKernelGGL(lora_tn_reduce_kernel, dim3((unsigned)max_rn_blocks, (unsigned)n_probs), dim3(256), 0, st, a);
     return uamd_launch_status();
 }
@@ -544,11 +511,7 @@ extern "C" int uamd_lora_xa2k(const void* X, int64_t ldx, const void* W, int64_t
     if (M == 0) return UAMD_OK;
     if ((K & 7) || (ldx & 7) || (ldw & 7) || !aligned16(X) || !aligned16(W)) return UAMD_ERR_ALIGN;
     if (out_k && ((k_cols & 7) || (ld_k & 7) || !aligned16(out_k))) return UAMD_ERR_ALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == UAMD_BF16)
-        return xa2_dispatch<bf16_t>(X, ldx, W, ldw, out, ld_out, out_k, ld_k, k_cols, M, K, R, out_cols, st);
-    if (dtype == UAMD_F16)
-        return xa2_dispatch<f16_t>(X, ldx, W, ldw, out, ld_out, out_k, ld_k, k_cols, M, K, R, out_cols, st);
+    UAMD_DISPATCH_HALF(dtype, return xa2_dispatch<T>(X, ldx, W, ldw, out, ld_out, out_k, ld_k, k_cols, M, K, R, out_cols, (hipStream_t)stream))
     return UAMD_ERR_DTYPE;
 }
 
@@ -616,11 +579,7 @@ extern "C" int uamd_lora_prepare(const uamd_lora_prep_desc* descs_dev, const int
     if (!descs_dev || !tile_prefix_dev || n_mats <= 0 || total_tiles < 0) return UAMD_ERR_ARG;
     if (total_tiles == 0) return UAMD_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == UAMD_BF16)
-        hipLaunchKernelGGL((lora_prepare_kernel<bf16_t>), dim3((unsigned)total_tiles), dim3(256), 0, st, descs_dev, n_mats, tile_prefix_dev);
-    else if (dtype == UAMD_F16)
-        hipLaunchKernelGGL((lora_prepare_kernel<f16_t>), dim3((unsigned)total_tiles), dim3(256), 0, st, descs_dev, n_mats, tile_prefix_dev);
-    else
-        return UAMD_ERR_DTYPE;
+    UAMD_DISPATCH_HALF(dtype, hipLaunchKernelGGL((lora_prepare_kernel<T>), dim3((unsigned)total_tiles), dim3(256), 0, st, descs_dev, n_mats,
+                                                 tile_prefix_dev))
     return uamd_launch_status();
 }

@@ -455,9 +455,7 @@ int dequant_entry(const uint8_t* packed, const AbsmaxSrc& am, const float* lut, 
     if (!aligned16(out) || (reinterpret_cast<uintptr_t>(packed) & 3)) return UAMD_ERR_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     if (transpose) {
-        if (out_dtype == UAMD_BF16) return launch_dequant<bf16_t>(packed, am, lut, out, rows, cols, blocksize, 1, ld_out, st);
-        if (out_dtype == UAMD_F16) return launch_dequant<f16_t>(packed, am, lut, out, rows, cols, blocksize, 1, ld_out, st);
-        return UAMD_ERR_DTYPE;
+        UAMD_DISPATCH_HALF(out_dtype, return (launch_dequant<T>(packed, am, lut, out, rows, cols, blocksize, 1, ld_out, st)))
     }
     UAMD_DISPATCH_FLOAT(out_dtype, return (launch_dequant<T>(packed, am, lut, out, rows, cols, blocksize, 0, ld_out, st)))
     return UAMD_ERR_DTYPE;
