@@ -137,6 +137,53 @@ __device__ unsigned* g_trace256 = nullptr;
 #define STAMP(KT, I) do { } while (0)
 #endif
 
+// ------------------------------------------------------------------------------------------------------------
+// Device helpers shared by the kernel families below: one definition each, and each inlines to exactly the
+// instructions the kernels used to spell out.
+
+// a wave-uniform pointer as a value the compiler keeps in SGPRs
+__device__ __forceinline__ uint64_t sgpr64(const void* q) {
+    const uint64_t u = (uint64_t)(uintptr_t)q;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// XCD-aware, bijective remap of a (virtual) block id (block b runs on XCD b % 8): each XCD gets a contiguous run of
+// tiles, so the A/B panels it re-reads stay in ITS 4 MiB L2.
+__device__ __forceinline__ int g256_xcd_remap(int v, int total) {
+    const int q = total >> 3, r = total & 7, x = v & 7, j = v >> 3;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
+}
+
+// DMA lane geometry. One wave-instruction of a piece fills a sub-tile [8 rows x 64 k] = 8 FULL 128-byte lines. Full
+// lines matter: the L2 serves requests, not bytes -- [16 rows x 64 B] half-line pieces deliver 36 B/clk/CU with all
+// CUs streaming, full-line pieces 59 (tools/probes/dma_probe.hip, profiles/r01_dma_probe.txt).
+// lane -> (row = lane>>3, 16-byte slot position q = lane&7) in LDS (the DMA destination is lane-linear); the bank
+// swizzle is applied on the SOURCE: position q of row r holds k-slot q ^ f(r), f = (r16>>1)&7 with r16 the row
+// inside its 16-row MFMA tile (conflict-free for all four ds_read_b128 lane groups). Sub-tiles alternate between
+// the halves of a 16-row tile with the issuing wave, hence (wave & 1) << 2.
+__device__ __forceinline__ int g256_sub_row(int lane) { return lane >> 3; }
+__device__ __forceinline__ int g256_sub_slot(int lane, int wave) {
+    return (lane & 7) ^ (((wave & 1) << 2) | (g256_sub_row(lane) >> 1));
+}
+
+// One MFMA slot of an 8-wave kernel: quadrant (mq, nq) of the wave's tile = 4 m-tiles x 2 n-tiles x 2 k-halves out of
+// the fragments in af / bf (operands are passed swapped, so a lane's accumulator quad is C[m][n..n+3]). MT = 16-row
+// tiles per wave group: 8, or 4 in the 128-row kernel (mq = 0).
+template <typename T, int MT>
+__device__ __forceinline__ void g256_mma(f32x4_t (&acc)[MT][4], const typename Mfma2<T>::frag (&af)[4][2],
+                                         const typename Mfma2<T>::frag (&bf)[4][2], int mq, int nq) {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                acc[mq * 4 + i][nq * 2 + j] = Mfma2<T>::run(bf[nq * 2 + j][ks], af[i][ks], acc[mq * 4 + i][nq * 2 + j]);
+    __builtin_amdgcn_s_setprio(0);
+}
+
 // BNN = false: B_g is [N, K] (K contiguous, the forward's weight layout): C = A @ B^T.
 // BNN = true : B_g is [K, N] (N contiguous): C = A @ B -- the dX products contract over the weight's ROWS, so they
 //              read the SAME row-major decode as the forward and no transposed copy of W is ever written. The B
@@ -158,13 +205,8 @@ __global__ void __launch_bounds__(512, 2) gemm_nt256_kernel(G256Args p) {
     const int grp = wave >> 2, wn = wave & 3;      // group owns rows grp*128.., wave owns cols wn*64..
     const int l15 = lane & 15, l4 = lane >> 4;
 
-    // ---- tile mapping with an XCD-aware, bijective remap (block b runs on XCD b % 8): each XCD gets a
-    //      contiguous run of tiles, so the A/B panels it re-reads stay in ITS 4 MiB L2.
-    int tile = blockIdx.x;
-    {
-        const int nt = p.total_tiles, q = nt >> 3, r = nt & 7, x = tile & 7, j = tile >> 3;
-        tile = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-    }
+    // ---- tile mapping: the XCD-aware remap, then a grouped raster inside the XCD's run
+    const int tile = g256_xcd_remap(blockIdx.x, p.total_tiles);
     // Grouped raster inside the run: 32 consecutive tiles (= the tiles one XCD's 32 CUs work on together) cover
     // group_m row panels x 32/group_m column panels instead of 32 x 1, so every A panel is shared by 32/group_m
     // co-running tiles and every B panel by group_m: ~2.7x less L2-miss (fabric) traffic than m-fastest order,
@@ -194,20 +236,9 @@ __global__ void __launch_bounds__(512, 2) gemm_nt256_kernel(G256Args p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-    // ---- DMA source pointers. Piece c (0..7) of a tile, issued by wave w, fills sub-tile u = c*8 + w =
-    //      [8 rows x 64 k] = 8 FULL 128-byte lines (u < 32: A rows u*8.., u >= 32: B rows (u-32)*8..). Full lines
-    //      matter: the L2 serves requests, not bytes -- [16 rows x 64 B] half-line pieces deliver 36 B/clk/CU with
-    //      all CUs streaming, full-line pieces 59 (tools/probes/dma_probe.hip, profiles/r01_dma_probe.txt).
-    //      lane -> (row = lane>>3, 16-byte slot position q = lane&7) in LDS (the DMA destination is lane-linear);
-    //      the bank swizzle is applied on the SOURCE: position q of row r holds k-slot q ^ f(r), f = (r16>>1)&7
-    //      with r16 the row inside its 16-row MFMA tile (conflict-free for all four ds_read_b128 lane groups).
-    const int sub_row = lane >> 3;
-    const int sub_slot = (lane & 7) ^ (((wave & 1) << 2) | (sub_row >> 1));
-    auto sgpr64 = [](const void* q) {               // a wave-uniform pointer as a value the compiler keeps in SGPRs
-        const uint64_t u = (uint64_t)(uintptr_t)q;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-        return ((uint64_t)hi << 32) | lo;
-    };
+    // ---- DMA source pointers. Piece c (0..7) of a tile, issued by wave w, fills sub-tile u = c*8 + w (u < 32: A
+    //      rows u*8.., u >= 32: B rows (u-32)*8..); lane -> row and swizzled slot: g256_sub_row / g256_sub_slot
+    const int sub_row = g256_sub_row(lane), sub_slot = g256_sub_slot(lane, wave);
     const uint64_t a_gbase = sgpr64(p.A), b_gbase = sgpr64(g.B);
     unsigned a_off[4], b_off[4];                    // byte offsets of this lane's row / slot (host: < 4 GiB)
     // BNN: lane -> (k-row of the piece's pair = lane >> 5, physical 16-byte slot = lane & 31 of the 512-byte row)
@@ -331,17 +362,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt256_kernel(G256Args p) {
                 }
             }
     };
-    auto mma = [&](int mq, int nq) {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[mq * 4 + i][nq * 2 + j] = Mfma2<T>::run(bf[nq * 2 + j][ks], af[i][ks], acc[mq * 4 + i][nq * 2 + j]);
-        __builtin_amdgcn_s_setprio(0);
-    };
+    auto mma = [&](int mq, int nq) { g256_mma<T, 8>(acc, af, bf, mq, nq); };
 #ifdef UAMD_G256_TRACE
     unsigned ts[32];
 #pragma unroll
@@ -464,13 +485,9 @@ __global__ void __launch_bounds__(512, 2) gemm_nt256p_kernel(G256Args p) {
     const int M = p.M, total = p.total_tiles;
     const int nk_main = __builtin_amdgcn_readfirstlane(p.K / TK);
 
-    // virtual block id -> (first row, first column inside its group, group): see gemm_nt256_kernel
+    // virtual block id -> (first row, first column inside its group, group): the raster of gemm_nt256_kernel
     auto decode = [&](int v, int& m0, int& n0, int& gi) {
-        int tile;
-        {
-            const int q = total >> 3, r = total & 7, x = v & 7, j = v >> 3;
-            tile = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-        }
+        const int tile = g256_xcd_remap(v, total);
         const int gm = p.group_m, tiles_n = p.tile_start[UAMD_G256_MAX_GROUPS];
         const int per_group = gm * tiles_n;
         const int rg = tile / per_group;
@@ -500,14 +517,8 @@ __global__ void __launch_bounds__(512, 2) gemm_nt256p_kernel(G256Args p) {
 
     // ---- the ISSUE context: where DMA pieces come from. It belongs to the output tile being multiplied until its
     //      last pieces are issued (L1 of its second-to-last K tile), then to the next one.
-    const int sub_row = lane >> 3;
-    const int sub_slot = (lane & 7) ^ (((wave & 1) << 2) | (sub_row >> 1));
+    const int sub_row = g256_sub_row(lane), sub_slot = g256_sub_slot(lane, wave);
     const int nn_krow = lane >> 5;
-    auto sgpr64 = [](const void* q) {
-        const uint64_t u = (uint64_t)(uintptr_t)q;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-        return ((uint64_t)hi << 32) | lo;
-    };
     const uint64_t a_gbase = sgpr64(p.A);
     int i_m0 = 0, i_n0 = 0, i_N = 0, ld_xk = 0, ld_bk = 0;
     uint64_t b_gbase = 0, b_tile_step = 0, xk_base = 0, bk_base = 0;
@@ -589,6 +600,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt256p_kernel(G256Args p) {
             // across the whole K loop
             int ln = lane;
             asm volatile("" : "+v"(ln));
+            // (g256_sub_row / g256_sub_slot spelled out: called here, they change the BNN instances' emitted code)
             const int sub_row = ln >> 3, nn_krow = ln >> 5;
             const int sub_slot = (ln & 7) ^ (((wave & 1) << 2) | (sub_row >> 1));
             if (BNN && c >= 4) {
@@ -635,17 +647,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt256p_kernel(G256Args p) {
                 }
             }
     };
-    auto mma = [&](int mq, int nq) {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[mq * 4 + i][nq * 2 + j] = Mfma2<T>::run(bf[nq * 2 + j][ks], af[i][ks], acc[mq * 4 + i][nq * 2 + j]);
-        __builtin_amdgcn_s_setprio(0);
-    };
+    auto mma = [&](int mq, int nq) { g256_mma<T, 8>(acc, af, bf, mq, nq); };
     auto store_tile = [&](int m0, int n0, int gi) {
         const uamd_gemm_group& g = p.g[gi];
         T* Cg = (T*)g.C;
@@ -795,13 +797,9 @@ __global__ void __launch_bounds__(256) gemm_nt256s_kernel(G256Args p) {
     const int l15 = lane & 15, l4 = lane >> 4;
     const int M = p.M, total = p.total_tiles;
 
-    // virtual block id -> (first row, first column inside its group, group): see gemm_nt256_kernel
+    // virtual block id -> (first row, first column inside its group, group): the raster of gemm_nt256_kernel
     auto decode = [&](int v, int& m0, int& n0, int& gi) {
-        int tile;
-        {
-            const int q = total >> 3, r = total & 7, x = v & 7, j = v >> 3;
-            tile = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-        }
+        const int tile = g256_xcd_remap(v, total);
         const int gm = p.group_m, tiles_n = p.tile_start[UAMD_G256_MAX_GROUPS];
         const int per_group = gm * tiles_n;
         const int rg = tile / per_group;
@@ -832,17 +830,12 @@ __global__ void __launch_bounds__(256) gemm_nt256s_kernel(G256Args p) {
 
     // ---- DMA sources. A-operand (and the NT B-operand): piece c (0..7) issued by wave w fills sub-tile c*4 + w = rows
     //      (c*4 + w)*8 .. +7 of the tile, [8 rows x 64 k] = 8 full lines; lane -> (row = lane >> 3, swizzled 16-byte slot) as
-    //      everywhere in this file. The per-lane part (row inside the first piece, slot) is ONE 32-bit offset per operand; the
+    //      everywhere in this file (g256_sub_slot). The per-lane part (row inside the first piece, slot) is ONE 32-bit offset per operand; the
     //      piece (c * 32 rows) rides in the eight scalar offsets so[c], the K tile in the descriptor's base.
     //      NN B-operand ([K, N], a [64 k][256 n] LDS image): piece = two k-rows x 512 B, sub-tile order chosen so that the bank
     //      swizzle does not depend on c (gen_gemm256s.py PIECE_LDS_NN): k-row of (w, c, h = lane >> 5) = 2 (w & 1) + 8 (w >> 1)
     //      + h + 4 (c & 1) + 16 (c >> 1), f = h | (w & 1) << 1 | (w >> 1) << 2.
     auto u32 = [](int64_t v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uint64_t)v); };
-    auto sgpr64 = [](const void* q, int64_t byte_off) {      // a wave-uniform address as a value the compiler keeps in SGPRs
-        const uint64_t u = (uint64_t)(uintptr_t)q + (uint64_t)byte_off;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-        return ((uint64_t)hi << 32) | lo;
-    };
     // bases of the two buffer descriptors (tile origin + the K tiles fetched so far), as 32-bit halves
     unsigned curAlo = 0, curAhi = 0, curBlo = 0, curBhi = 0;
     unsigned voffA = 0, voffB = 0, soA[8], soB[8], stepA = TK * sizeof(T), stepB = TK * sizeof(T);
@@ -855,7 +848,7 @@ __global__ void __launch_bounds__(256) gemm_nt256s_kernel(G256Args p) {
     auto set_sources = [&](const void* Ap, int ld_a, const void* Bp, int ld_b, int m0, int n0, int ahead) {
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        const int sr = ln >> 3, ss = (ln & 7) ^ (((wave & 1) << 2) | (sr >> 1));
+        const int sr = g256_sub_row(ln), ss = g256_sub_slot(ln, wave);
         uint64_t baseA = (uint64_t)(uintptr_t)Ap + (uint64_t)((int64_t)m0 * ld_a * (int64_t)sizeof(T)) +
                          (uint64_t)ahead * (TK * sizeof(T));
         uint64_t baseB;
@@ -1110,11 +1103,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt256h_kernel(G256Args p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wn = wave & 3;      // group owns rows grp*64.., wave owns cols wn*64..
     const int l15 = lane & 15, l4 = lane >> 4;
-    int tile = blockIdx.x;
-    {
-        const int nt = p.total_tiles, q = nt >> 3, r = nt & 7, x = tile & 7, j = tile >> 3;
-        tile = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + j;
-    }
+    const int tile = g256_xcd_remap(blockIdx.x, p.total_tiles);     // raster as in gemm_nt256_kernel
     int tm, tn_lin;
     {
         const int gm = p.group_m, tiles_n = p.tile_start[UAMD_G256_MAX_GROUPS];
@@ -1141,13 +1130,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt256h_kernel(G256Args p) {
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     // piece c (0..5) of a tile, issued by wave w, fills sub-tile u = c*8 + w: u < 16 -> A rows u*8.., else B rows (u-16)*8..
-    const int sub_row = lane >> 3;
-    const int sub_slot = (lane & 7) ^ (((wave & 1) << 2) | (sub_row >> 1));
-    auto sgpr64 = [](const void* q) {
-        const uint64_t u = (uint64_t)(uintptr_t)q;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-        return ((uint64_t)hi << 32) | lo;
-    };
+    const int sub_row = g256_sub_row(lane), sub_slot = g256_sub_slot(lane, wave);
     const uint64_t a_gbase = sgpr64(p.A), b_gbase = sgpr64(g.B);
     unsigned a_off[2], b_off[4];
     const int nn_krow = lane >> 5;                  // BNN: see gemm_nt256_kernel
@@ -1239,17 +1222,7 @@ __global__ void __launch_bounds__(512, 2) gemm_nt256h_kernel(G256Args p) {
                 }
             }
     };
-    auto mma = [&](int nq) {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][nq * 2 + j] = Mfma2<T>::run(bf[nq * 2 + j][ks], af[i][ks], acc[i][nq * 2 + j]);
-        __builtin_amdgcn_s_setprio(0);
-    };
+    auto mma = [&](int nq) { g256_mma<T, 4>(acc, af, bf, 0, nq); };      // one row quarter per wave group
     // ---- prologue: tiles 0 and 1 completely
 #pragma unroll
     for (int c = 0; c < 6; ++c) issue_main(c, 0, 0);
