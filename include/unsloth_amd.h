@@ -545,6 +545,25 @@ int uamd_adamw_shard(float* p32, const void* g16, void* p16, float* m, float* v,
                      double beta2, double eps, double weight_decay, double bias_correction1,
                      double bias_correction2_sqrt, double grad_scale, int dtype, void* stream);
 
+/* 8-bit moments (bitsandbytes' block-wise 2-state AdamW, the reference's optim="adamw_8bit"): exp_avg / exp_avg_sq are one
+ * uint8 code per element (m8, v8) + one fp32 absmax per 256-element block (absmax_m, absmax_v: ceil(n / 256) entries),
+ * value = code[idx] * absmax[blk]; code_m / code_v are sorted 256-entry fp32 maps on the device (signed / unsigned dynamic
+ * map). Blocks count from element 0 of the pointers passed in; the last one may be partial. Per block: decode, the
+ * arithmetic of uamd_adamw_flat (the parameter moves with the new fp32 moments), new absmax = max |m| / max v, re-encode
+ * as the nearest map entry to m / absmax (an exact tie takes the lower index; absmax 0 stores the code of 0.0). p / g
+ * 16-byte aligned, m8 / v8 4-byte aligned. */
+int uamd_adamw8_flat(float* p, float* g, uint8_t* m8, uint8_t* v8, float* absmax_m, float* absmax_v, const float* code_m,
+                     const float* code_v, int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
+                     double bias_correction1, double bias_correction2_sqrt, double grad_scale, int zero_grad, void* stream);
+/* uamd_adamw8_shard: uamd_adamw_shard with the 8-bit moments above. weight_decay applies to the elements in
+ * [decay_begin, decay_end) (relative to the pointers passed in) and 0 elsewhere: ONE launch per shard, because a quant
+ * block may straddle the boundary between decaying and one-dimensional parameters and must be updated exactly once.
+ * p32 16-byte aligned, g16 / p16 8-byte aligned, m8 / v8 4-byte aligned. */
+int uamd_adamw8_shard(float* p32, const void* g16, void* p16, uint8_t* m8, uint8_t* v8, float* absmax_m, float* absmax_v,
+                      const float* code_m, const float* code_v, int64_t n, int64_t decay_begin, int64_t decay_end, double lr,
+                      double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
+                      double bias_correction2_sqrt, double grad_scale, int dtype, void* stream);
+
 /* debug: (lane,reg) -> (row,col) map of v_mfma_f32_16x16x32_bf16; out = float[2][64][4] */
 int uamd_debug_mfma_probe(float* out, void* stream);
 

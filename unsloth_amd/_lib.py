@@ -147,6 +147,8 @@ SIGNATURES = {
                            + [c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     "uamd_adamw_shard": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + [ctypes.c_double] * 8
                          + [c_int, c_void_p]),
+    "uamd_adamw8_flat": (c_int, [c_void_p] * 8 + [c_int64] + [ctypes.c_double] * 8 + [c_int, c_void_p]),
+    "uamd_adamw8_shard": (c_int, [c_void_p] * 9 + [c_int64] * 3 + [ctypes.c_double] * 8 + [c_int, c_void_p]),
     "uamd_lora_tn": (c_int, [ctypes.POINTER(LoraTnProblem), c_int, c_int, c_void_p, c_int64, c_int, c_void_p]),
     "uamd_attn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_int,
                               c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p]),

@@ -286,9 +286,19 @@ class ShardedAdamW(torch.optim.Optimizer):
     the flat shards (step count, fp32 masters, both moments) is saved and loaded under the extra `uamd_sharded` key of
     state_dict(), per rank. Weight decay follows HF Trainer's rule for the reference's full_finetuning path
     (`get_decay_parameter_names`: no decay on biases and on LayerNorm / RMSNorm weights): one-dimensional parameters are
-    updated with decay 0 -- they sit at the end of every per-layer bucket, so a bucket is two launches instead of one."""
+    updated with decay 0 -- they sit at the end of every per-layer bucket, so a bucket is two launches instead of one.
 
-    def __init__(self, model_or_buckets, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, process_group=None):
+    `optim_bits=8` (the reference's optim="adamw_8bit"): the fp32 masters stay, both moments of every shard become one uint8
+    code per element + one fp32 absmax per 256-element block (optim.py, `uamd_adamw8_shard`): 2 B + 8 B / 256 per parameter
+    instead of 8 B. Quant blocks tile each shard from its element 0 and a bucket is ONE launch that carries the decaying
+    range -- a block may straddle the boundary to the one-dimensional parameters and must be re-encoded exactly once. On CPU
+    tensors the same rule runs in torch (optim.adam8_step_host)."""
+
+    def __init__(self, model_or_buckets, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, process_group=None,
+                 optim_bits=32):
+        from .optim import QBLOCK, _check_bits, adam8_maps, adam8_zero_code
+        _check_bits(optim_bits)
+        self.optim_bits = optim_bits
         self.buckets = model_or_buckets if isinstance(model_or_buckets, FullGradBuckets) else \
             FullGradBuckets(model_or_buckets, process_group=process_group)
         super().__init__(list(self.buckets.params), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -296,8 +306,19 @@ class ShardedAdamW(torch.optim.Optimizer):
         self.master, self.exp_avg, self.exp_avg_sq = [], [], []
         for bi, b in enumerate(B.buckets):
             self.master.append(B.param_shard(bi).to(torch.float32))            # (a copy: the shard changes dtype)
-            self.exp_avg.append(torch.zeros(b["shard"], dtype=torch.float32, device=B.device))
-            self.exp_avg_sq.append(torch.zeros(b["shard"], dtype=torch.float32, device=B.device))
+            if optim_bits == 32:
+                self.exp_avg.append(torch.zeros(b["shard"], dtype=torch.float32, device=B.device))
+                self.exp_avg_sq.append(torch.zeros(b["shard"], dtype=torch.float32, device=B.device))
+        if optim_bits == 8:
+            # exp_avg / exp_avg_sq hold the uint8 codes (zero moments: absmax 0 and the code of 0.0), absmax_* the scales
+            self.code_m, self.code_v = adam8_maps(B.device)
+            self.absmax_m, self.absmax_v = [], []
+            for b in B.buckets:
+                nblk = (b["shard"] + QBLOCK - 1) // QBLOCK
+                self.exp_avg.append(torch.full((b["shard"],), adam8_zero_code(self.code_m), dtype=torch.uint8, device=B.device))
+                self.exp_avg_sq.append(torch.full((b["shard"],), adam8_zero_code(self.code_v), dtype=torch.uint8, device=B.device))
+                self.absmax_m.append(torch.zeros(nblk, dtype=torch.float32, device=B.device))
+                self.absmax_v.append(torch.zeros(nblk, dtype=torch.float32, device=B.device))
         # [start, end, decays) runs of this rank's shard of every bucket, in shard-local elements
         self._runs = []
         for bi, b in enumerate(B.buckets):
@@ -316,6 +337,15 @@ class ShardedAdamW(torch.optim.Optimizer):
                 else:
                     runs.append([a - lo, e - lo, dec])
             self._runs.append(runs)
+        if optim_bits == 8:
+            # ONE launch per bucket: the decaying elements of the shard as one [begin, end) range
+            self._decay = []
+            for bi, runs in enumerate(self._runs):
+                dec = [(a, e) for a, e, d in runs if d]
+                if any(x[1] != y[0] for x, y in zip(dec, dec[1:])):
+                    raise NotImplementedError(f"ShardedAdamW(optim_bits=8): the decaying parameters of bucket {bi} "
+                                              f"({B.buckets[bi]['names'][0]} ...) are not one contiguous range of the shard")
+                self._decay.append((dec[0][0], dec[-1][1]) if dec else (0, 0))
         self._t = 0
 
     @property
@@ -350,7 +380,9 @@ class ShardedAdamW(torch.optim.Optimizer):
             B.wait(bi)
             g16, p16 = B.grad_shard(bi), B.param_shard(bi)
             p32, m, v = self.master[bi], self.exp_avg[bi], self.exp_avg_sq[bi]
-            for a, e, decays in self._runs[bi]:
+            if self.optim_bits == 8:
+                self._step8(bi, g16, p16, grp, bc1, bc2_sqrt, grad_scale)
+            for a, e, decays in self._runs[bi] if self.optim_bits == 32 else ():
                 wd = float(grp["weight_decay"]) if decays else 0.0
                 if p32.is_cuda:
                     from . import _lib
@@ -373,6 +405,31 @@ class ShardedAdamW(torch.optim.Optimizer):
             h.wait()
         return loss
 
+    def moment_bytes(self):
+        """Bytes both moments of this rank's shards take, block scales included."""
+        t = self.exp_avg + self.exp_avg_sq + ((self.absmax_m + self.absmax_v) if self.optim_bits == 8 else [])
+        return sum(x.numel() * x.element_size() for x in t)
+
+    def _step8(self, bi, g16, p16, grp, bc1, bc2_sqrt, grad_scale):
+        """8-bit moments: the whole shard of bucket `bi` in one launch (one torch pass on the CPU)."""
+        p32, m, v = self.master[bi], self.exp_avg[bi], self.exp_avg_sq[bi]
+        b1, b2 = grp["betas"]
+        d0, d1 = self._decay[bi]
+        hyper = (float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]), bc1, bc2_sqrt,
+                 float(grad_scale))
+        if p32.is_cuda:
+            from . import _lib
+            _lib.call("uamd_adamw8_shard", p32, p32.data_ptr(), g16.data_ptr(), p16.data_ptr(), m.data_ptr(),
+                      v.data_ptr(), self.absmax_m[bi].data_ptr(), self.absmax_v[bi].data_ptr(),
+                      self.code_m.data_ptr(), self.code_v.data_ptr(), p32.numel(), d0, d1, *hyper,
+                      _lib.dtype_code(g16.dtype), _lib.stream_of(p32))
+        else:
+            from .optim import adam8_step_host
+            i = torch.arange(p32.numel())
+            adam8_step_host(p32, g16, m, v, self.absmax_m[bi], self.absmax_v[bi], self.code_m, self.code_v,
+                            (i >= d0) & (i < d1), *hyper)
+            p16.copy_(p32)
+
     def zero_grad(self, set_to_none=True):
         self.buckets.zero_grad()
 
@@ -381,6 +438,10 @@ class ShardedAdamW(torch.optim.Optimizer):
         sd["uamd_sharded"] = dict(step=self._t, rank=self.buckets.rank, world_size=self.buckets.world_size,
                                   master=[t.clone() for t in self.master], exp_avg=[t.clone() for t in self.exp_avg],
                                   exp_avg_sq=[t.clone() for t in self.exp_avg_sq])
+        if self.optim_bits == 8:             # exp_avg / exp_avg_sq are the uint8 codes; their scales and the block size
+            from .optim import QBLOCK
+            sd["uamd_sharded"].update(optim_bits=8, blocksize=QBLOCK, absmax1=[t.clone() for t in self.absmax_m],
+                                      absmax2=[t.clone() for t in self.absmax_v])
         return sd
 
     def load_state_dict(self, state_dict):
@@ -390,9 +451,16 @@ class ShardedAdamW(torch.optim.Optimizer):
             return
         if sh["world_size"] != self.buckets.world_size or sh["rank"] != self.buckets.rank:
             raise ValueError("ShardedAdamW state was saved by another rank / world size: every rank loads its own shard")
+        saved_bits = sh.get("optim_bits", 32)
+        if saved_bits != self.optim_bits:
+            raise ValueError(f"ShardedAdamW: the state was saved with optim_bits={saved_bits} ({saved_bits}-bit moments), "
+                             f"this optimizer has optim_bits={self.optim_bits}: the two do not convert into each other")
         self._t = int(sh["step"])
         with torch.no_grad():
-            for dst, src in ((self.master, sh["master"]), (self.exp_avg, sh["exp_avg"]), (self.exp_avg_sq, sh["exp_avg_sq"])):
+            pairs = [(self.master, sh["master"]), (self.exp_avg, sh["exp_avg"]), (self.exp_avg_sq, sh["exp_avg_sq"])]
+            if self.optim_bits == 8:
+                pairs += [(self.absmax_m, sh["absmax1"]), (self.absmax_v, sh["absmax2"])]
+            for dst, src in pairs:
                 for d, s_ in zip(dst, src):
                     d.copy_(s_)
             for bi in range(len(self.buckets.buckets)):

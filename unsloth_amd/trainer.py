@@ -121,10 +121,21 @@ def _patch_trl_trainer():
 FLAT_ADAMW = True              # one-launch AdamW over flat arenas (optim.FlatAdamW); False = torch's fused AdamW
 
 
-def make_optimizer(model, lr=None, weight_decay=0.01, betas=(0.9, 0.999), arena=None, flat=None):
+OPTIM_32BIT = ("adamw_torch", "adamw_torch_fused")
+OPTIM_8BIT = ("adamw_8bit", "adamw_bnb_8bit", "paged_adamw_8bit")
+
+
+def make_optimizer(model, lr=None, weight_decay=0.01, betas=(0.9, 0.999), arena=None, flat=None, optim=None):
     """AdamW on the trainable (LoRA) parameters. On the GPU with fp32 parameters: optim.FlatAdamW -- parameters,
     gradients and moments in flat arenas, ONE launch per step (`arena`: the dp.LoRAGradArena of a data-parallel run, else
-    the optimizer creates its own). `flat=False` (or UNSLOTH_AMD_FLAT_ADAMW=0) keeps torch's fused AdamW."""
+    the optimizer creates its own). `flat=False` (or UNSLOTH_AMD_FLAT_ADAMW=0) keeps torch's fused AdamW.
+    `optim`: HF TrainingArguments' spelling. None / "adamw_torch" / "adamw_torch_fused": fp32 moments. "adamw_8bit" /
+    "adamw_bnb_8bit" / "paged_adamw_8bit" (the reference notebooks' default): block-wise 8-bit moments, `optim_bits=8` of
+    FlatAdamW / ShardedAdamW ("paged" has no meaning without host paging: the same optimizer); needs the HIP path -- CPU
+    parameters or `flat=False` raise instead of substituting fp32 state."""
+    if optim is not None and optim not in OPTIM_32BIT + OPTIM_8BIT:
+        raise ValueError(f"make_optimizer: unknown optim={optim!r}; accepted: None, " + ", ".join(OPTIM_32BIT + OPTIM_8BIT))
+    bits = 8 if optim in OPTIM_8BIT else 32
     params = [p for p in model.parameters() if p.requires_grad]
     base = model.get_base_model() if hasattr(model, "get_base_model") else model
     if lr is None:             # LoRA factors: 2e-4 (the reference notebooks' rate); every weight of the model: 2e-5
@@ -133,12 +144,15 @@ def make_optimizer(model, lr=None, weight_decay=0.01, betas=(0.9, 0.999), arena=
         # full fine-tuning: flat per-layer buckets + AdamW sharded over the data-parallel group (full_finetune.py)
         from .full_finetune import FullGradBuckets, ShardedAdamW
         return ShardedAdamW(arena if isinstance(arena, FullGradBuckets) else model, lr=lr, betas=betas,
-                            weight_decay=weight_decay)
+                            weight_decay=weight_decay, optim_bits=bits)
     if flat is None:
         flat = FLAT_ADAMW
     if flat and params and all(p.is_cuda and p.dtype == torch.float32 for p in params):
         from .optim import FlatAdamW
-        return FlatAdamW(model, lr=lr, betas=betas, weight_decay=weight_decay, arena=arena)
+        return FlatAdamW(model, lr=lr, betas=betas, weight_decay=weight_decay, arena=arena, optim_bits=bits)
+    if bits == 8:
+        raise NotImplementedError(f"make_optimizer: optim={optim!r} runs on the flat HIP path only (fp32 LoRA parameters on "
+                                  "the GPU, flat=True); there is no fp32 substitute for it")
     fused = params[0].is_cuda
     return torch.optim.AdamW(params, lr=lr, weight_decay=weight_decay, betas=betas, fused=fused)
 
