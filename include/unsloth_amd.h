@@ -182,6 +182,11 @@ int uamd_glu_bwd_xa_ws(int act, void* DW, void* e, void* g, int M, int K, int64_
  *   forward : logsumexp[row], loss[row] = logsumexp - x[label]  (0 when label == -100)
  *   backward: logits <- dloss[row] * (softmax - onehot) (x scale, x (1 - tanh^2) for softcap),
  *             IN PLACE over logits (:276, :413-418); rows with label == -100 become zeros.
+ *   logprob_entropy_forward (the RL log-prob path): the forward's one pass, writing
+ *             logprob[row] = x[index] - logsumexp (0 when index == -100 or out of range), logsumexp[row]
+ *             exactly as forward writes it (backward consumes it unchanged), and
+ *             entropy[row] = logsumexp - sum softmax(x) * x over the transformed logits (scale, then soft
+ *             cap), for every row whatever its index; a -inf logit contributes 0.
  * logit_softcapping / logit_scaling == 0 disable the transform. labels are int64.
  */
 int uamd_cross_entropy_forward(const void* logits, int64_t logits_row_stride, float* loss,
@@ -193,6 +198,9 @@ int uamd_cross_entropy_backward(void* logits, int64_t logits_row_stride, const f
                                 const int64_t* labels, int64_t n_rows, int vocab_size,
                                 float logit_softcapping, float logit_scaling, int dtype,
                                 void* stream);
+int uamd_logprob_entropy_forward(const void* logits, int64_t logits_row_stride, float* logprob, float* logsumexp,
+                                 float* entropy, const int64_t* index, int64_t n_rows, int vocab_size,
+                                 float logit_softcapping, float logit_scaling, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * bitsandbytes-compatible symbols (exact bitsandbytes signatures; bound by the reference at

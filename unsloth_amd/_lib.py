@@ -99,6 +99,8 @@ SIGNATURES = {
                                            c_int, c_float, c_float, c_int, c_void_p]),
     "uamd_cross_entropy_backward": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                             c_int64, c_int, c_float, c_float, c_int, c_void_p]),
+    "uamd_logprob_entropy_forward": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                             c_int, c_float, c_float, c_int, c_void_p]),
     "cdequantize_blockwise_fp32": (None, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "cdequantize_blockwise_bf16_nf4": (None, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "cdequantize_blockwise_fp16_nf4": (None, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),

@@ -1,4 +1,4 @@
-// Cross-entropy forward (loss + logsumexp per row) and in-place backward.
+// Cross-entropy forward (loss + logsumexp per row, optionally the row's entropy) and in-place backward.
 //
 // Replaces the Triton kernels of the reference:
 //   unsloth/kernels/cross_entropy_loss.py:35-111   _cross_entropy_forward          (V <= 65536)
@@ -11,6 +11,11 @@
 // block streams a row of any length once with an online (max, sum) pair per lane, then a
 // wave64 shuffle + 4-entry LDS combine: no vocab limit, no second launch, logits read once.
 // Backward is a pure streaming kernel over (row, 8192-column chunk).
+//
+// ENTROPY (uamd_logprob_entropy_forward, the RL log-prob path) carries a third running sum in that same pass,
+// u = sum exp(t - m) (t - m): every term <= 0, nothing cancels against a large max. When the max moves from m to M,
+// u <- e^(m-M) (u + (m - M) s). At the end H = log(S) - U / S = logsumexp(t) - sum softmax(t) t. The (m, s) arithmetic
+// is the same expressions in both instantiations: lse and the selected logit are the same bits with or without it.
 //
 // Integer semantics that must stay exact: label == -100 -> loss 0 and zero gradient row;
 // the "- 1" lands exactly on column == label.
@@ -32,16 +37,30 @@ __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float
     m = M;
 }
 
-template <typename T, bool SOFTCAP, bool SCALE, bool VECTOR>
+// (m, s, u) <- (m, s, u) + (m2, s2, u2). A side whose weight e^(m_i - M) is 0 adds nothing to u: for m_i == -inf (a masked
+// logit, an untouched lane) the product (m_i - M) s_i would be -inf * 0.
+__device__ __forceinline__ void online_merge(float& m, float& s, float& u, float m2, float s2, float u2) {
+    const float M = fmaxf(m, m2);
+    if (M == -INFINITY) { m = M; s = 0.f; u = 0.f; return; }
+    const float e1 = __expf(m - M), e2 = __expf(m2 - M);
+    const float a = (e1 == 0.f) ? 0.f : e1 * (u + (m - M) * s);
+    const float b = (e2 == 0.f) ? 0.f : e2 * (u2 + (m2 - M) * s2);
+    u = a + b;
+    s = s * __expf(m - M) + s2 * __expf(m2 - M);
+    m = M;
+}
+
+// ENTROPY: `loss` receives the log-prob t[label] - lse instead of lse - t[label], `entropy` the row's entropy.
+template <typename T, bool SOFTCAP, bool SCALE, bool VECTOR, bool ENTROPY>
 __global__ void __launch_bounds__(256)
 ce_fwd_kernel(const T* __restrict__ logits, int64_t row_stride, float* __restrict__ loss,
-              float* __restrict__ lse, const int64_t* __restrict__ labels, int vocab, float softcap,
-              float scale) {
+              float* __restrict__ lse, float* __restrict__ entropy, const int64_t* __restrict__ labels, int vocab,
+              float softcap, float scale) {
     constexpr int VEC = Vec16<T>::N;
-    __shared__ float red_m[4], red_s[4];
+    __shared__ float red_m[4], red_s[4], red_u[ENTROPY ? 4 : 1];
     const int64_t row = blockIdx.x;
     const T* x = logits + row * row_stride;
-    float m = -INFINITY, s = 0.f;
+    float m = -INFINITY, s = 0.f, u = 0.f;
     if (VECTOR) {
         const int nvec = vocab / VEC;
         auto absorb = [&](const Vec16<T>& v) {
@@ -55,8 +74,20 @@ ce_fwd_kernel(const T* __restrict__ logits, int64_t row_stride, float* __restric
             const float M = fmaxf(m, lm);
             if (M != -INFINITY) {
                 float acc = s * __expf(m - M);
+                if constexpr (ENTROPY) {
+                    const float e0 = __expf(m - M);
+                    float uacc = (e0 == 0.f) ? 0.f : e0 * (u + (m - M) * s);
 #pragma unroll
-                for (int j = 0; j < VEC; ++j) acc += __expf(t[j] - M);
+                    for (int j = 0; j < VEC; ++j) {
+                        const float d = t[j] - M, e = __expf(d);
+                        acc += e;
+                        uacc += (e == 0.f) ? 0.f : e * d;      // t == -inf: 0, not 0 * -inf
+                    }
+                    u = uacc;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) acc += __expf(t[j] - M);
+                }
                 s = acc;
                 m = M;
             }
@@ -73,34 +104,46 @@ ce_fwd_kernel(const T* __restrict__ logits, int64_t row_stride, float* __restric
         if (i < nvec) absorb(ld16(x + (int64_t)i * VEC));
         for (int c = nvec * VEC + threadIdx.x; c < vocab; c += 256) {
             const float t = ce_transform<SOFTCAP, SCALE>(to_f32(x[c]), softcap, scale);
-            online_merge(m, s, t, 1.f);
+            if constexpr (ENTROPY) online_merge(m, s, u, t, 1.f, 0.f); else online_merge(m, s, t, 1.f);
         }
     } else {
         for (int c = threadIdx.x; c < vocab; c += 256) {
             const float t = ce_transform<SOFTCAP, SCALE>(to_f32(x[c]), softcap, scale);
-            online_merge(m, s, t, 1.f);
+            if constexpr (ENTROPY) online_merge(m, s, u, t, 1.f, 0.f); else online_merge(m, s, t, 1.f);
         }
     }
     // wave combine
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-        online_merge(m, s, m2, s2);
+        if constexpr (ENTROPY) {
+            const float u2 = __shfl_xor(u, o, 64);
+            online_merge(m, s, u, m2, s2, u2);
+        } else {
+            online_merge(m, s, m2, s2);
+        }
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { red_m[w] = m; red_s[w] = s; }
+    if (lane == 0) {
+        red_m[w] = m; red_s[w] = s;
+        if constexpr (ENTROPY) red_u[w] = u;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        float M = red_m[0], S = red_s[0];
+        float M = red_m[0], S = red_s[0], U = red_u[0];
 #pragma unroll
-        for (int i = 1; i < 4; ++i) online_merge(M, S, red_m[i], red_s[i]);
+        for (int i = 1; i < 4; ++i) {
+            if constexpr (ENTROPY) online_merge(M, S, U, red_m[i], red_s[i], red_u[i]);
+            else online_merge(M, S, red_m[i], red_s[i]);
+        }
         const float l = M + logf(S);                  // c + log(sum(exp(x - c)))
         lse[row] = l;
+        if constexpr (ENTROPY) entropy[row] = logf(S) - U / S;        // every row, whatever its label
         const int64_t label = labels[row];
         float out = 0.f;                              // label == -100 -> 0
         if (label != -100 && label >= 0 && label < vocab) {
             const float xl = ce_transform<SOFTCAP, SCALE>(to_f32(x[label]), softcap, scale);
-            out = l - xl;
+            out = ENTROPY ? xl - l : l - xl;
         }
         loss[row] = out;
     }
@@ -176,13 +219,13 @@ bool rows_vectorizable(const void* p, int64_t row_stride) {
     return aligned16(p) && (row_stride % Vec16<T>::N == 0);
 }
 
-template <typename T>
-int launch_fwd(const void* logits, int64_t rs, float* loss, float* lse, const int64_t* labels,
+template <typename T, bool ENT>
+int launch_fwd(const void* logits, int64_t rs, float* loss, float* lse, float* entropy, const int64_t* labels,
                int64_t n_rows, int vocab, float softcap, float scale, hipStream_t st) {
     const bool vec = rows_vectorizable<T>(logits, rs);
     const bool sc = softcap != 0.f, ls = scale != 0.f;
     dim3 grid((unsigned)n_rows), block(256);
-#define L(SC, LS, V) hipLaunchKernelGGL((ce_fwd_kernel<T, SC, LS, V>), grid, block, 0, st, (const T*)logits, rs, loss, lse, labels, vocab, softcap, scale)
+#define L(SC, LS, V) hipLaunchKernelGGL((ce_fwd_kernel<T, SC, LS, V, ENT>), grid, block, 0, st, (const T*)logits, rs, loss, lse, entropy, labels, vocab, softcap, scale)
 #define L2(SC, LS) do { if (vec) L(SC, LS, true); else L(SC, LS, false); } while (0)
     if (sc && ls) L2(true, true); else if (sc) L2(true, false); else if (ls) L2(false, true); else L2(false, false);
 #undef L2
@@ -216,9 +259,24 @@ extern "C" int uamd_cross_entropy_forward(const void* logits, int64_t logits_row
                                           float logit_scaling, int dtype, void* stream) {
     if (n_rows < 0 || vocab_size <= 0 || n_rows > 0x7fffffffLL) return UAMD_ERR_ARG;
     if (n_rows == 0) return UAMD_OK;
-    UAMD_DISPATCH_FLOAT(dtype, return (launch_fwd<T>(logits, logits_row_stride, loss, logsumexp, labels,
-                                                     n_rows, vocab_size, logit_softcapping,
-                                                     logit_scaling, (hipStream_t)stream)))
+    UAMD_DISPATCH_FLOAT(dtype, return (launch_fwd<T, false>(logits, logits_row_stride, loss, logsumexp, nullptr, labels,
+                                                            n_rows, vocab_size, logit_softcapping,
+                                                            logit_scaling, (hipStream_t)stream)))
+    return UAMD_ERR_DTYPE;
+}
+
+// The forward's one pass over the row, for the RL log-prob path: logprob[row] = x[index] - logsumexp(row) (0 when index is
+// -100 or out of range), logsumexp[row] as uamd_cross_entropy_forward writes it (uamd_cross_entropy_backward takes it),
+// entropy[row] = logsumexp - sum softmax(x) x over the transformed logits, for every row whatever its index.
+extern "C" int uamd_logprob_entropy_forward(const void* logits, int64_t logits_row_stride, float* logprob,
+                                            float* logsumexp, float* entropy, const int64_t* index,
+                                            int64_t n_rows, int vocab_size, float logit_softcapping,
+                                            float logit_scaling, int dtype, void* stream) {
+    if (n_rows < 0 || vocab_size <= 0 || n_rows > 0x7fffffffLL) return UAMD_ERR_ARG;
+    if (n_rows == 0) return UAMD_OK;
+    UAMD_DISPATCH_FLOAT(dtype, return (launch_fwd<T, true>(logits, logits_row_stride, logprob, logsumexp, entropy, index,
+                                                           n_rows, vocab_size, logit_softcapping,
+                                                           logit_scaling, (hipStream_t)stream)))
     return UAMD_ERR_DTYPE;
 }
 

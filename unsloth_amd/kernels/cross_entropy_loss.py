@@ -4,6 +4,8 @@ the fused linear + cross-entropy entry point the reference imports from unsloth_
 
   Fast_CrossEntropyLoss     (:288-418)  per-row loss, saves (logits, logsumexp, labels), backward
                                         overwrites logits with the gradient and returns that buffer
+  Fast_LogProbEntropy                   its sibling for the RL log-prob path: (log-prob, entropy) per row from the same
+                                        single pass (uamd_logprob_entropy_forward), same in-place backward
   fast_cross_entropy_loss   (:421-449)  sum / n_items
   patch_loss_functions      (:459-473)  installs the fast loss into transformers' LOSS_MAPPING
 
@@ -25,6 +27,20 @@ def _ce_forward(logits2d, labels, softcap, scale):
               _lib.ptr(labels), n_rows, vocab, float(softcap), float(scale), _lib.dtype_code(logits2d.dtype),
               _lib.stream_of(logits2d))
     return losses, lse
+
+
+def _logprob_entropy_forward(logits2d, index, softcap, scale):
+    """(log-prob of `index`, logsumexp, entropy) per row, fp32, from the forward kernel's one pass over the logits: the
+    log-prob is -loss of `_ce_forward` and `lse` the same bits (`_ce_backward_` takes it); entropy = lse - sum softmax(z) z
+    over the transformed logits z, for every row (index -100 too)."""
+    n_rows, vocab = logits2d.shape
+    logprobs = torch.empty(n_rows, dtype=torch.float32, device=logits2d.device)
+    lse = torch.empty(n_rows, dtype=torch.float32, device=logits2d.device)
+    entropy = torch.empty(n_rows, dtype=torch.float32, device=logits2d.device)
+    _lib.call("uamd_logprob_entropy_forward", logits2d, _lib.ptr(logits2d), logits2d.stride(0), _lib.ptr(logprobs),
+              _lib.ptr(lse), _lib.ptr(entropy), _lib.ptr(index), n_rows, vocab, float(softcap), float(scale),
+              _lib.dtype_code(logits2d.dtype), _lib.stream_of(logits2d))
+    return logprobs, lse, entropy
 
 
 def _ce_backward_(logits2d, dlosses, lse, labels, softcap, scale):
@@ -56,6 +72,33 @@ class Fast_CrossEntropyLoss(torch.autograd.Function):
             dlosses = dlosses.expand(logits.shape[0]).contiguous()
         # in place over the saved logits, returned as the gradient (:413-418)
         _ce_backward_(logits, dlosses, lse, labels, ctx.logit_softcapping, ctx.logit_scaling)
+        return logits, None, None, None
+
+
+class Fast_LogProbEntropy(torch.autograd.Function):
+    """Sibling of Fast_CrossEntropyLoss for the RL path: (log-prob of `index`, entropy) per row from one pass. The log-prob's
+    backward is Fast_CrossEntropyLoss's (in place over the saved logits, with the sign of -loss); the entropy has none."""
+
+    @staticmethod
+    def forward(ctx, logits, index, logit_softcapping=0, logit_scaling=0):
+        _lib.require_gpu(logits)
+        if logits.stride(1) != 1:
+            logits = logits.contiguous()
+        index = index.to(device=logits.device, dtype=torch.int64).contiguous()
+        logprobs, lse, entropy = _logprob_entropy_forward(logits, index, logit_softcapping or 0, logit_scaling or 0)
+        ctx.save_for_backward(logits, lse, index)
+        ctx.logit_softcapping = logit_softcapping or 0
+        ctx.logit_scaling = logit_scaling or 0
+        ctx.mark_non_differentiable(entropy)
+        return logprobs, entropy
+
+    @staticmethod
+    def backward(ctx, dlogprobs, _dentropy):
+        logits, lse, index = ctx.saved_tensors
+        dlosses = -dlogprobs.to(torch.float32)                      # log-prob = -loss
+        if dlosses.dim() == 0 or dlosses.stride(0) == 0:
+            dlosses = dlosses.expand(logits.shape[0]).contiguous()
+        _ce_backward_(logits, dlosses, lse, index, ctx.logit_softcapping, ctx.logit_scaling)
         return logits, None, None, None
 
 

@@ -9,24 +9,27 @@ formula `log_softmax(f(h @ W^T))[index]` (parity unpinned, like unsloth_fused_ce
     logits  = cap * tanh(logits / cap)         (if logit_softcapping != 0)
     logits /= temperature                      (if != 1)
     out[b, l] = logits[b, l, index[b, l]] - logsumexp(logits[b, l, :])            (fp32)
+    H[b, l]   = logsumexp(z) - sum_v softmax(z)_v * z_v,  z = logits[b, l, :]     (fp32, return_entropy=True; no gradient)
 Built from the same pieces as the fused linear cross-entropy: row chunks, MFMA GEMM into a transient chunk of
 logits, the single-pass CE kernel (log-prob = -loss), d(hidden) computed in the forward because lm_head is frozen
-and a log-prob depends on its own row only (the backward is a row-wise scale)."""
+and a log-prob depends on its own row only (the backward is a row-wise scale). The entropy is a third running sum of
+that same pass over the chunk (uamd_logprob_entropy_forward): no second GEMM, no fp32 logits, no fp32 lm_head."""
 import torch
 
 from .. import _lib
 from ..kernels import utils as _u
-from ..kernels.cross_entropy_loss import (Fast_CrossEntropyLoss, _ce_backward_, _ce_forward, _dhidden, _logits_chunk,
-                                          _nn_ok, _transposed_weight)
+from ..kernels.cross_entropy_loss import (Fast_CrossEntropyLoss, Fast_LogProbEntropy, _ce_backward_, _ce_forward, _dhidden,
+                                          _logits_chunk, _logprob_entropy_forward, _nn_ok, _transposed_weight)
 
 
 class _ChunkedLogProbs(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, hidden2d, weight, weight_t, index, softcap, scale, chunk_rows):
+    def forward(ctx, hidden2d, weight, weight_t, index, softcap, scale, chunk_rows, want_entropy):
         T, H = hidden2d.shape
         V = weight.shape[0]
         dev = hidden2d.device
         out = torch.empty(T, dtype=torch.float32, device=dev)
+        ent = torch.empty(T, dtype=torch.float32, device=dev) if want_entropy else None
         need_grad = hidden2d.requires_grad
         dh = torch.empty_like(hidden2d) if need_grad else None
         for r0 in range(0, T, chunk_rows):
@@ -35,22 +38,30 @@ class _ChunkedLogProbs(torch.autograd.Function):
             logits = chunk[:, :V]
             _u._launch_gemm(hidden2d[r0:r1], [_u._group(weight, logits, V, weight.stride(0))], nf4=False)
             idx = index[r0:r1]
-            losses, lse = _ce_forward(logits, idx, softcap, scale)
-            out[r0:r1] = -losses
+            if want_entropy:
+                lp, lse, e = _logprob_entropy_forward(logits, idx, softcap, scale)
+                out[r0:r1] = lp
+                ent[r0:r1] = e
+            else:
+                losses, lse = _ce_forward(logits, idx, softcap, scale)
+                out[r0:r1] = -losses
             if need_grad:
                 dl = torch.full((r1 - r0,), -1.0, dtype=torch.float32, device=dev)      # d(logprob) = -d(loss)
                 _ce_backward_(logits, dl, lse, idx, softcap, scale)                     # logits <- d logprob / d logits
                 _dhidden(chunk, logits, weight, weight_t, dh[r0:r1])
         ctx.save_for_backward(dh)
-        return out
+        if not want_entropy:
+            return out
+        ctx.mark_non_differentiable(ent)
+        return out, ent
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, *_):
         (dh,) = ctx.saved_tensors
         if dh is None:
-            return None, None, None, None, None, None, None
+            return (None,) * 8
         # row-wise upstream scale applied in fp32, one rounding (not g rounded to bf16 first)
-        return (dh.to(torch.float32) * g.to(torch.float32).unsqueeze(1)).to(dh.dtype), None, None, None, None, None, None
+        return ((dh.to(torch.float32) * g.to(torch.float32).unsqueeze(1)).to(dh.dtype),) + (None,) * 7
 
 
 def _effective_scale(mult, div, softcap, temperature):
@@ -68,8 +79,10 @@ def _effective_scale(mult, div, softcap, temperature):
 
 
 def chunked_hidden_states_selective_log_softmax(hidden_states, lm_head, index, chunks=4, logit_scale_multiply=0.0,
-                                                logit_scale_divide=0.0, logit_softcapping=0.0, temperature=1.0):
-    """hidden_states [B, L, H] (activation dtype), lm_head [V, H] frozen, index [B, L] int -> log-probs [B, L] fp32."""
+                                                logit_scale_divide=0.0, logit_softcapping=0.0, temperature=1.0,
+                                                return_entropy=False):
+    """hidden_states [B, L, H] (activation dtype), lm_head [V, H] frozen, index [B, L] int -> log-probs [B, L] fp32.
+    `return_entropy`: (log-probs, entropy [B, L] fp32 of each position's distribution, no gradient) from the same pass."""
     _lib.require_gpu(hidden_states, lm_head, index)
     if lm_head.requires_grad:
         raise NotImplementedError("frozen lm_head only (LoRA fine-tuning keeps it frozen)")
@@ -86,17 +99,23 @@ def chunked_hidden_states_selective_log_softmax(hidden_states, lm_head, index, c
     nn = _nn_ok(min(chunk_rows, T), W.shape[0], H) and W.stride(1) == 1 and W.stride(0) % 8 == 0
     Wt = None if nn else _transposed_weight(W, lm_head if W.dtype == lm_head.dtype else None)
     scale = _effective_scale(logit_scale_multiply, logit_scale_divide, logit_softcapping, temperature)
-    out = _ChunkedLogProbs.apply(h2d, W, Wt, index.reshape(-1).to(torch.int64).contiguous(),
-                                 float(logit_softcapping or 0), scale, int(chunk_rows))
+    idx = index.reshape(-1).to(torch.int64).contiguous()
+    out = _ChunkedLogProbs.apply(h2d, W, Wt, idx, float(logit_softcapping or 0), scale, int(chunk_rows), bool(return_entropy))
+    if return_entropy:
+        return out[0].view(B, L), out[1].view(B, L)
     return out.view(B, L)
 
 
-def chunked_selective_log_softmax(logits, index, temperature=1.0, chunks=4):
+def chunked_selective_log_softmax(logits, index, temperature=1.0, chunks=4, return_entropy=False):
     """logits [B, L, V] already produced by the model (scaling / soft cap applied there) -> log-probs [B, L] fp32.
-    The CE backward writes d(logits) in place over `logits`, like the reference's Fast_CrossEntropyLoss."""
+    The CE backward writes d(logits) in place over `logits`, like the reference's Fast_CrossEntropyLoss.
+    `return_entropy`: (log-probs, entropy [B, L] fp32, no gradient) from the same pass over the logits."""
     _lib.require_gpu(logits, index)
     B, L, V = logits.shape
     scale = _effective_scale(0, 0, 0, temperature)
+    if return_entropy:
+        lp, ent = Fast_LogProbEntropy.apply(logits.reshape(B * L, V), index.reshape(-1).to(torch.int64), 0, scale)
+        return lp.view(B, L), ent.view(B, L)
     losses = Fast_CrossEntropyLoss.apply(logits.reshape(B * L, V), index.reshape(-1).to(torch.int64), 0, scale)
     return (-losses).view(B, L)
 
@@ -136,7 +155,8 @@ def _packed_completion_index(input_ids, attention_mask, logits_to_keep):
 
 def get_per_token_logps_and_entropies(model, input_ids, attention_mask, logits_to_keep, temperature=1.0, chunks=4,
                                       compute_entropy=False):
-    """log p(token | prefix) of the last `logits_to_keep` columns: [B, logits_to_keep] fp32, 0 at padding. ONE packed
+    """(log p(token | prefix) of the last `logits_to_keep` columns: [B, logits_to_keep] fp32, 0 at padding; with
+    `compute_entropy` the entropy of each of those positions' distributions, same shape, 0 at padding, else None). ONE packed
     forward over the non-padding tokens (block-diagonal causal attention through the band kernels, position ids restarting
     per row -- no left-pad RoPE error), hidden states instead of logits, lm_head + log-softmax only on the completion
     positions, in row chunks. Differentiable w.r.t. the model's trainable parameters."""
@@ -163,25 +183,12 @@ def get_per_token_logps_and_entropies(model, input_ids, attention_mask, logits_t
     ent = None
     if rows.shape[1]:
         lp = chunked_hidden_states_selective_log_softmax(rows, lm_head, tgt_ids.unsqueeze(0), chunks, mult, div, cap,
-                                                         temperature)[0]
-        out = out.index_put((dst_r, dst_c), lp)
+                                                         temperature, return_entropy=compute_entropy)
         if compute_entropy:
-            # (diagnostic path, no gradient: plain torch over row chunks -- the kernels keep no per-row entropy)
-            ent = torch.zeros_like(out)
-            with torch.no_grad():
-                W = lm_head.float()
-                for r0 in range(0, rows.shape[1], 2048):
-                    lg = rows[0, r0:r0 + 2048].float() @ W.t()
-                    if mult:
-                        lg = lg * mult
-                    if div:
-                        lg = lg / div
-                    if cap:
-                        lg = cap * torch.tanh(lg / cap)
-                    lg = lg / temperature
-                    p = torch.softmax(lg, dim=-1)
-                    e = torch.logsumexp(lg, dim=-1) - (p * lg).sum(-1)
-                    ent.index_put_((dst_r[r0:r0 + 2048], dst_c[r0:r0 + 2048]), e)
+            # the entropy of each completion position, from the log-prob kernel's own pass over its logits (no gradient)
+            lp, e = lp
+            ent = torch.zeros_like(out).index_put_((dst_r, dst_c), e[0])
+        out = out.index_put((dst_r, dst_c), lp[0])
     return out, ent
 
 
