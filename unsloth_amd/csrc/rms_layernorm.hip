@@ -455,11 +455,13 @@ int launch_add_bwd(const void* dY, const void* dRes, void* dX, const void* X, co
 // [column blocks] x [row chunks], thread = one 16-byte vector of columns, fp32 partial sums over the chunk's rows
 // -> workspace[chunk][col]; (2) one thread per column adds the chunks in order. No atomics: bit-stable.
 namespace {
-template <typename T>
+// V: a thread owns one 16-byte vector of columns; !V (a width, a row stride or a pointer that is no multiple of 16 bytes): one
+// column per thread, scalar loads, the same sums in the same order.
+template <typename T, bool V>
 __global__ void __launch_bounds__(256)
 rms_dw_partial(const T* __restrict__ dY, const T* __restrict__ X, const float* __restrict__ R,
                float* __restrict__ part, int64_t n_rows, int n_cols, int64_t dys, int64_t xs, int rows_per_chunk) {
-    constexpr int VEC = Vec16<T>::N;
+    constexpr int VEC = V ? Vec16<T>::N : 1;
     const int c = (blockIdx.x * 256 + threadIdx.x) * VEC;
     if (c >= n_cols) return;
     const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk;
@@ -468,11 +470,15 @@ rms_dw_partial(const T* __restrict__ dY, const T* __restrict__ X, const float* _
 #pragma unroll
     for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
     for (int64_t row = r0; row < r1; ++row) {
-        const Vec16<T> g = ld16(dY + row * dys + c);
-        const Vec16<T> x = ld16(X + row * xs + c);
         const float inv = R[row];
+        if constexpr (V) {
+            const Vec16<T> g = ld16(dY + row * dys + c);
+            const Vec16<T> x = ld16(X + row * xs + c);
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) acc[j] += to_f32(g.e[j]) * (to_f32(x.e[j]) * inv);
+            for (int j = 0; j < VEC; ++j) acc[j] += to_f32(g.e[j]) * (to_f32(x.e[j]) * inv);
+        } else {
+            acc[0] += to_f32(dY[row * dys + c]) * (to_f32(X[row * xs + c]) * inv);
+        }
     }
     float* out = part + (int64_t)blockIdx.y * n_cols + c;
 #pragma unroll
@@ -494,8 +500,9 @@ template <typename T, typename WT>
 int launch_dw(const void* dY, const void* X, const float* r, void* dW, float* ws, int64_t ws_elems, int64_t n_rows,
               int n_cols, int64_t dys, int64_t xs, int accumulate, hipStream_t st) {
     constexpr int VEC = Vec16<T>::N;
-    if ((n_cols % VEC) || (dys % VEC) || (xs % VEC) || !aligned16(dY) || !aligned16(X)) return UAMD_ERR_ALIGN;
-    const int col_blocks = (n_cols / VEC + 255) / 256;
+    const bool vec_ok = !((n_cols % VEC) || (dys % VEC) || (xs % VEC) || !aligned16(dY) || !aligned16(X));
+    // the row chunks are those of the vector grid on either path
+    const int col_blocks = ((n_cols + VEC - 1) / VEC + 255) / 256;
     // ~2048 blocks in flight (8 per CU), at least 8 rows per chunk, bounded by the workspace
     int64_t chunks = (2048 + col_blocks - 1) / col_blocks;
     if (chunks > (n_rows + 7) / 8) chunks = (n_rows + 7) / 8;
@@ -503,8 +510,12 @@ int launch_dw(const void* dY, const void* X, const float* r, void* dW, float* ws
     if (chunks < 1) return UAMD_ERR_ARG;
     const int rows_per_chunk = (int)((n_rows + chunks - 1) / chunks);
     chunks = (n_rows + rows_per_chunk - 1) / rows_per_chunk;
-    hipLaunchKernelGGL((rms_dw_partial<T>), dim3(col_blocks, (unsigned)chunks), dim3(256), 0, st, (const T*)dY, (const T*)X, r,
-                       ws, n_rows, n_cols, dys, xs, rows_per_chunk);
+    if (vec_ok)
+        hipLaunchKernelGGL((rms_dw_partial<T, true>), dim3(col_blocks, (unsigned)chunks), dim3(256), 0, st, (const T*)dY,
+                           (const T*)X, r, ws, n_rows, n_cols, dys, xs, rows_per_chunk);
+    else
+        hipLaunchKernelGGL((rms_dw_partial<T, false>), dim3((n_cols + 255) / 256, (unsigned)chunks), dim3(256), 0, st,
+                           (const T*)dY, (const T*)X, r, ws, n_rows, n_cols, dys, xs, rows_per_chunk);
     hipLaunchKernelGGL((rms_dw_reduce<WT>), dim3((n_cols + 255) / 256), dim3(256), 0, st, ws, (WT*)dW, n_cols, (int)chunks,
                        accumulate);
     return uamd_launch_status();
@@ -512,7 +523,8 @@ int launch_dw(const void* dY, const void* X, const float* r, void* dW, float* ws
 }  // namespace
 
 // dW[n_cols] (+)= sum over rows of dY * X * r. `workspace`: fp32 scratch of ws_elems >= n_cols elements (more = more row
-// chunks in flight: 2048 / ceil(n_cols / (256 * vec)) chunks x n_cols saturates the chip). dW in w_dtype.
+// chunks in flight: 2048 / ceil(n_cols / (256 * vec)) chunks x n_cols saturates the chip). dW in w_dtype. Any width, row
+// stride and pointer alignment: what is no multiple of 16 bytes takes scalar loads.
 extern "C" int uamd_rms_layernorm_dw(const void* dY, const void* X, const float* r, void* dW, float* workspace,
                                      int64_t ws_elems, int64_t n_rows, int n_cols, int64_t dy_row_stride,
                                      int64_t x_row_stride, int accumulate, int x_dtype, int w_dtype, void* stream) {

@@ -5,13 +5,14 @@ writes dX IN PLACE over dY, like the SwiGLU / GeGLU backward kernels of the lang
 import torch
 
 from .. import _lib
+from .swiglu import _flat16
 
 
 class Fast_QuickGELU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X):
         _lib.require_gpu(X)
-        Xc = X if X.is_contiguous() else X.contiguous()
+        Xc = _flat16(X)
         Y = torch.empty_like(Xc)
         _lib.call("uamd_quick_gelu_forward", Xc, _lib.ptr(Xc), _lib.ptr(Y), Xc.numel(), _lib.dtype_code(Xc.dtype),
                   _lib.stream_of(Xc))
@@ -22,8 +23,11 @@ class Fast_QuickGELU(torch.autograd.Function):
     def backward(ctx, dY):
         (X,) = ctx.saved_tensors
         d = dY if (dY.is_contiguous() and dY.dtype == X.dtype) else dY.to(X.dtype).contiguous()
-        _lib.call("uamd_quick_gelu_backward", d, _lib.ptr(X), _lib.ptr(d), X.numel(), _lib.dtype_code(X.dtype),
+        buf = _flat16(d)
+        _lib.call("uamd_quick_gelu_backward", d, _lib.ptr(X), _lib.ptr(buf), X.numel(), _lib.dtype_code(X.dtype),
                   _lib.stream_of(d))
+        if buf is not d:                        # dY off the 16-byte grid went through an aligned copy: back in place
+            d.copy_(buf)
         return d.view(dY.shape)
 
 

@@ -17,6 +17,16 @@ def _rows(X):
     return X2 if X2.stride(1) == 1 else X2.contiguous()
 
 
+def _vec_layout(*tensors):
+    """What the 16-byte vector kernels need of every operand: unit stride along the row, the base pointer and every other
+    stride a multiple of 16 bytes."""
+    for t in tensors:
+        vec = 16 // t.element_size()
+        if t.data_ptr() % 16 or t.stride(-1) != 1 or any(s % vec for s in t.stride()[:-1]):
+            return False
+    return True
+
+
 def rms_fwd(X, W, eps, gemma=False):
     """(Y, r) for X [..., dim]; Y [rows, dim]."""
     _lib.require_gpu(X, W)
@@ -55,7 +65,8 @@ def rms_dw(dY, X, r, W, out=None, accumulate=False):
         out = torch.empty(dim, dtype=W.dtype, device=W.device)
         accumulate = False
     assert out.is_contiguous() and out.numel() == dim and out.dtype == W.dtype
-    col_blocks = (dim // (16 // dY2.element_size()) + 255) // 256
+    vec = 16 // dY2.element_size()
+    col_blocks = ((dim + vec - 1) // vec + 255) // 256
     chunks = max(1, min((2048 + col_blocks - 1) // col_blocks, (n_rows + 7) // 8))
     ws = _nf4.scratch(dY2.device, chunks * dim, torch.float32, slot=41)
     _lib.call("uamd_rms_layernorm_dw", dY2, _lib.ptr(dY2), _lib.ptr(X2), _lib.ptr(r), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
@@ -85,6 +96,10 @@ def rms_bwd_(dY, H, W, r, dH=None, gemma=False):
     dY2, H2 = _rows(dY), _rows(H)
     n_rows, dim = dY2.shape
     dX = torch.empty_like(dY2) if gemma else dY2
+    if dH is not None and not (dim <= 64 * (16 // dY2.element_size()) * 8 and _vec_layout(dY2, H2, W, _rows(dH))):
+        # the fused kernel has no scalar form: the norm's backward (which has one), then the add, with the same two roundings
+        assert not gemma
+        return rms_bwd_(dY2, H2, W, r).add_(_rows(dH))
     if dH is None:
         _lib.call("uamd_rms_layernorm_bwd", dY2, _lib.ptr(dY2), _lib.ptr(dX), _lib.ptr(H2), _lib.ptr(W), _lib.ptr(r), n_rows,
                   dim, dY2.stride(0), dX.stride(0), H2.stride(0), int(gemma), _lib.dtype_code(dY2.dtype),
@@ -141,11 +156,12 @@ class Fast_Add_RMS_Layernorm(torch.autograd.Function):
         return dX, dX, dW, None
 
 
-def add_rms_supported(X, W):
-    """shapes the fused kernel takes (otherwise: torch add + fast_rms_layernorm)."""
+def add_rms_supported(X, W, residual=None):
+    """shapes and layouts the fused kernel takes (otherwise: torch add + fast_rms_layernorm)."""
     vec = 16 // X.element_size()
     return (X.is_cuda and X.dtype in (torch.bfloat16, torch.float16, torch.float32) and X.shape[-1] % vec == 0
-            and X.shape[-1] <= 64 * vec * 8 and W.dtype in (X.dtype, torch.float32))
+            and X.shape[-1] <= 64 * vec * 8 and W.dtype in (X.dtype, torch.float32)
+            and _vec_layout(X, W, *(() if residual is None else (residual,))))
 
 
 @torch.compiler.disable
@@ -153,7 +169,7 @@ def fast_add_rms_layernorm(layernorm, X, residual):
     """(residual + X, layernorm(residual + X)) -- the add of llama.py:833/:840 fused into the following norm."""
     W = layernorm.weight
     eps = layernorm.variance_epsilon if hasattr(layernorm, "variance_epsilon") else layernorm.eps
-    if not add_rms_supported(X, W):
+    if not add_rms_supported(X, W, residual):
         h = residual + X
         return h, Fast_RMS_Layernorm.apply(h, W, eps, False)
     return Fast_Add_RMS_Layernorm.apply(X, residual, W, eps)

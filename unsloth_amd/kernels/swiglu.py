@@ -4,10 +4,15 @@ import torch
 from .. import _lib
 
 
+def _flat16(t):
+    """`t` when it is contiguous and starts on a 16-byte boundary (what the streaming kernels take), else such a copy."""
+    return t if t.is_contiguous() and t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def _glu_fwd(name, e, g):
     _lib.require_gpu(e, g)
     assert e.shape == g.shape and e.dtype == g.dtype
-    e, g = e.contiguous(), g.contiguous()
+    e, g = _flat16(e), _flat16(g)
     h = torch.empty_like(e)
     _lib.call(name, e, _lib.ptr(e), _lib.ptr(g), _lib.ptr(h), e.numel(), _lib.dtype_code(e.dtype), _lib.stream_of(e))
     return h
@@ -20,7 +25,11 @@ def _glu_bwd(name, DW, e, g):
     if not (DW.is_contiguous() and e.is_contiguous() and g.is_contiguous()):
         raise ValueError("in-place GLU backward needs contiguous DW, e, g")
     assert DW.shape == e.shape == g.shape and DW.dtype == e.dtype == g.dtype
-    _lib.call(name, e, _lib.ptr(DW), _lib.ptr(e), _lib.ptr(g), e.numel(), _lib.dtype_code(e.dtype), _lib.stream_of(e))
+    bufs = [_flat16(t) for t in (DW, e, g)]
+    _lib.call(name, e, *(_lib.ptr(t) for t in bufs), e.numel(), _lib.dtype_code(e.dtype), _lib.stream_of(e))
+    for t, b in zip((DW, e, g), bufs):
+        if b is not t:                      # a buffer off the 16-byte grid went through an aligned copy: back in place
+            t.copy_(b)
     return DW, e, g
 
 
