@@ -244,11 +244,43 @@ def _launch_gemm(X2d, groups, nf4, accumulate=False, nn=False):
     return name
 
 
+def _aligned_rows(W):
+    """Can the kernels read W [rows, cols] in place? Unit column stride, a row stride of whole 16-byte vectors and a
+    16-byte aligned start (what every A / B / XK / BK operand of the C entry points must have)."""
+    return W.stride(1) == 1 and W.stride(0) % 8 == 0 and W.data_ptr() % 16 == 0
+
+
+def _aligned_copy(W, dtype=None):
+    """W [rows, cols] in `dtype` (default: its own), dense, in fresh storage. `.contiguous()` alone returns a dense view
+    that starts off the 16-byte grid as it is; a new allocation is aligned."""
+    Wc = W.to(dtype if dtype is not None else W.dtype).contiguous()
+    return Wc.clone() if Wc.data_ptr() % 16 else Wc
+
+
 def _rows2d(X):
     X2d = X.reshape(-1, X.shape[-1])
-    if X2d.stride(1) != 1 or (X2d.stride(0) % 8) or (X2d.data_ptr() % 16):
-        X2d = X2d.contiguous()
-    return X2d
+    return X2d if _aligned_rows(X2d) else _aligned_copy(X2d)
+
+
+def _out2d(C, M, N, dtype, name):
+    """The caller's output buffer `name` as the [M, N] matrix the GEMM epilogue addresses through `ldc = stride(0)`: the
+    activation dtype, unit column stride (any row stride and alignment: the epilogue has a scalar form). Leading dimensions
+    are folded when they are dense ([batch, seq, N] as matmul_lora's callers pass it). Anything else is refused here: the
+    kernel looks at the pointer and `ldc` alone and would write somewhere else."""
+    if not isinstance(C, torch.Tensor) or not C.is_cuda or C.dtype != dtype:
+        raise ValueError(f"{name}: expected a {dtype} tensor on the GPU, got {getattr(C, 'dtype', type(C))}")
+    C2 = C
+    if C.dim() != 2 and C.dim() >= 1 and C.shape[-1] == N and C.numel() == M * N:
+        try:
+            C2 = C.view(M, N)
+        except RuntimeError:
+            raise ValueError(f"{name}: shape {tuple(C.shape)} with strides {C.stride()} is no [{M}, {N}] row-major matrix") \
+                from None
+    if C2.dim() != 2 or tuple(C2.shape) != (M, N):
+        raise ValueError(f"{name}: shape {tuple(C.shape)}, expected [{M}, {N}]")
+    if N > 1 and C2.stride(1) != 1:
+        raise ValueError(f"{name}: column stride {C2.stride(1)}, the GEMM writes rows of unit column stride")
+    return C2
 
 
 # LoRA factors are fp32 parameters used in the activation dtype (utils.py:1166-1167). A training step reads each
@@ -616,7 +648,7 @@ def lora_linear_forward(X, projs, outs=None, return_xa=False, pre_xa=None):
         if W_quant is not None:
             assert W_quant.shape[1] == K, "weight/in_features mismatch"
         N = Ns[gi]
-        C = outs[gi] if outs is not None else torch.empty((M, N), dtype=dtype, device=X.device)
+        C = _out2d(outs[gi], M, N, dtype, f"outs[{gi}]") if outs is not None else torch.empty((M, N), dtype=dtype, device=X.device)
         kw = {}
         if biases[gi] is not None:
             bias = biases[gi].detach()
@@ -647,8 +679,8 @@ def lora_linear_forward(X, projs, outs=None, return_xa=False, pre_xa=None):
             elif W_quant is not None:
                 # one scratch slot per group member: the grouped launch reads all of them
                 Wd = _decoded_as(_nf4.dequantize_nf4(W, W_quant, use_global_buffer=True, slot=8 + gi), dtype)
-            elif Wd.dtype != dtype or Wd.stride(1) != 1 or Wd.stride(0) % 8:
-                Wd = Wd.to(dtype).contiguous()
+            elif Wd.dtype != dtype or not _aligned_rows(Wd):
+                Wd = _aligned_copy(Wd, dtype)
             keep.append(Wd)
             dense_groups.append(_group(Wd, C, N, Wd.stride(0), **kw))
         results.append(C)
@@ -767,7 +799,7 @@ def _dx_weight(projs, nn, dtype):
         Wd = _nf4.dequantize_nf4(Ws[0], qs[0], transpose=not nn, use_global_buffer=True)
     elif nn:
         W = Ws[0]
-        Wd = W if (W.dtype == dtype and W.stride(1) == 1 and W.stride(0) % 8 == 0) else W.to(dtype).contiguous()
+        Wd = W if (W.dtype == dtype and _aligned_rows(W)) else _aligned_copy(W, dtype)
     else:
         Wd = Ws[0].to(dtype).t().contiguous()
     return _decoded_as(Wd, dtype)
@@ -811,6 +843,8 @@ def _dx_gemm(dY2d, projs, terms, xa, out, accumulate):
     dtype = dY2d.dtype
     W0, q0 = projs[0][:2]
     Kin = q0.shape[1] if q0 is not None else W0.shape[1]
+    if out is not None:
+        out = _out2d(out, M, Kin, dtype, "out")
     # per adapter (A, s, (rank block its P was also written to, at column)) -- lora_dx_terms / glu_bwd_terms attach the latter
     lora = [(A, s, getattr(t, "_uamd_xk", None)) for (_, _, A, _, s), t in zip(projs, terms) if A is not None]
     have_xk = all(x is not None and x[0] is lora[0][2][0] for _, _, x in lora)         # ONE block shared by all of them
@@ -906,7 +940,17 @@ def lora_tn(problems, targets=None):
     outs, descs, keep = [], [], []
     for pi, (P, Z, R, out_nr, scale) in enumerate(problems):
         Z2 = _rows2d(Z)
-        assert Z2.shape[0] == M and P.shape[0] == M and P.dtype == torch.float32 and P.stride(1) == 1
+        if P.dim() != 2 or P.shape[0] != M or P.shape[1] < R or P.dtype != torch.float32:
+            raise ValueError(f"lora_tn: problem {pi}: P must be fp32 [{M}, >= {R}], got {P.dtype} {tuple(P.shape)}")
+        if Z2.shape[0] != M:
+            raise ValueError(f"lora_tn: problem {pi}: Z has {Z2.shape[0]} rows, P {M}")
+        if P.stride(1) != 1 or P.stride(0) % 4 or P.data_ptr() % 16:
+            # the kernel fetches P in 16-byte pieces: a row stride of whole float4s from an aligned start, else a copy (its
+            # width padded to whole float4s, which the fetch of the last ranks reads and drops)
+            Pc = torch.zeros((M, (R + 3) // 4 * 4), dtype=torch.float32, device=P.device)
+            Pc[:, :R] = P[:, :R]
+            P = Pc
+            keep.append(P)
         N = Z2.shape[1]
         tgt = targets[pi] if targets is not None else None
         if tgt is not None:
@@ -1090,14 +1134,12 @@ def dense_dw(dY, X, out=None, accumulate=False):
         dY2d = torch.nn.functional.pad(dY2d, (0, 0, 0, pad))
         X2d = torch.nn.functional.pad(X2d, (0, 0, 0, pad))
         T += pad
-    if dY2d.stride(1) != 1 or dY2d.stride(0) % 8 or dY2d.data_ptr() % 16:
-        dY2d = dY2d.contiguous()
-    if X2d.stride(1) != 1 or X2d.stride(0) % 8 or X2d.data_ptr() % 16:
-        X2d = X2d.contiguous()
     if out is None:
         out = torch.empty((N_out, N_in), dtype=dtype, device=X2d.device)
         accumulate = False
-    assert out.dtype == dtype and tuple(out.shape) == (N_out, N_in) and out.stride(1) == 1
+    if out.dtype != dtype or tuple(out.shape) != (N_out, N_in) or out.stride(1) != 1:
+        raise ValueError(f"dense_dw: out must be a {dtype} [{N_out}, {N_in}] matrix of unit column stride, got {out.dtype} "
+                         f"{tuple(out.shape)} with strides {out.stride()}")
     # both operands have the contracted token dimension as rows: past GEMM_SPAN_LIMIT the tokens go in chunks (multiples of
     # 64), each launch after the first accumulating into `out` -- one more rounding of a 16-bit `out` per extra chunk
     item = X2d.element_size()
