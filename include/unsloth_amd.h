@@ -470,13 +470,15 @@ int uamd_gemv_fused(const void* x, int K, const uamd_gemv_group* groups, int n_g
  * place in the fused row qkv [B, (Hq + 2 Hk) D], and append of k, v to the cache [B, Hk, s_max, D] at position
  * kv_len[b] (a DEVICE array: the step is replayable as a hipGraph). rope_pos (device, NULL = kv_len) indexes the
  * cos / sin tables [positions, >= D/2]. Replaces the six in-place torch ops + two permuted copies of
- * LlamaAttention_fast_forward_inference (unsloth/models/llama.py:468-497). */
+ * LlamaAttention_fast_forward_inference (unsloth/models/llama.py:468-497). Any even D. */
 int uamd_rope_kv_append(void* qkv, int64_t ld_qkv, const void* cos_t, const void* sin_t, int64_t ld_cs,
                         const int* kv_len, const int* rope_pos, void* k_cache, void* v_cache, int64_t cache_sb,
                         int64_t cache_sh, int B, int Hq, int Hk, int D, int s_max, int dtype, void* stream);
-/* Split-KV decode attention over the cache, D = 128, GQA by head index: out[b, h, :] = softmax(q[b, h] . K^T * scale) V
+/* Split-KV decode attention over the cache, D = 64 or 128 (any other D: UAMD_ERR_ARG), GQA by head index:
+ * out[b, h, :] = softmax(q[b, h] . K^T * scale) V
  * over keys [max(0, len - window), len), len = kv_len[b] + len_add. Grid (nsplit, Hk, B), split s owns keys
- * [s * split_keys, (s + 1) * split_keys) (split_keys % 16 == 0, nsplit * split_keys >= s_max); partials = fp32
+ * [s * split_keys, (s + 1) * split_keys) (split_keys a multiple of the 2048 / D keys one block-load covers: 16 at D = 128,
+ * 32 at D = 64; nsplit * split_keys >= s_max); partials = fp32
  * workspace [B, Hq, nsplit, D + 2]; a second launch combines them. Replaces llama.py:499-543 (expand + matmul +
  * softmax + matmul over the whole cache, or SDPA). */
 int uamd_attn_decode(const void* q, int64_t q_sb, const void* k_cache, const void* v_cache, int64_t cache_sb,
@@ -486,6 +488,7 @@ int uamd_attn_decode(const void* q, int64_t q_sb, const void* k_cache, const voi
 /* The three launches above (RoPE + append, split attention, combine) as ONE: every workgroup (split, kv head, batch) rotates
  * the G query heads it needs from the raw q|k|v row (qkv is NOT modified); the workgroup whose split owns position kv_len[b]
  * rotates the new k, appends k and v to the cache and uses them from LDS. Keys [max(0, len - window), len), len = kv_len[b] + 1.
+ * D and split_keys as for uamd_attn_decode.
  * The combine happens inside the launch, in split order (bit-identical to uamd_attn_decode's):
  *   nsplit * Hk * B <= 256 workgroups (all resident at once) and a launch tag given (tag / tag_dev as in uamd_gemv_prologue):
  *   partials travel as 8-byte {value, tag} granules and every workgroup combines its 1 / nsplit of the outputs; otherwise

@@ -1,7 +1,8 @@
-"""Single-stream decode throughput of the Llama-3-8B-shaped QLoRA model (NF4 r=16) with the hipGraph-replayed step
-(models/decode.py), and the GEMV kernels alone against the HBM roofline.
+"""Single-stream decode throughput of a Llama-shaped QLoRA model (NF4 r=16) with the hipGraph-replayed step
+(models/decode.py), and the GEMV and attention kernels alone against the HBM roofline. --shape llama3-8b (default; head_dim
+128) or tinyllama (TinyLlama-1.1B: hidden 2048, intermediate 5632, 22 layers, 32 / 4 heads, head_dim 64, vocab 32000).
 
-    python tools/decode_bench.py [--layers 32] [--context 2048] [--new 64] [--out gpurun_out/decode.jsonl]
+    python tools/decode_bench.py [--shape llama3-8b] [--layers 32] [--context 2048] [--new 64] [--out decode.jsonl]
 """
 import argparse
 import json
@@ -14,6 +15,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 HBM = 8.0e12
+# hidden, intermediate, layers, query heads, KV heads, head_dim, vocab
+SHAPES = {"llama3-8b": (4096, 14336, 32, 32, 8, 128, 128256), "tinyllama": (2048, 5632, 22, 32, 4, 64, 32000)}
 
 
 def timeit(fn, n=20, warm=3):
@@ -29,14 +32,50 @@ def timeit(fn, n=20, warm=3):
     return e0.elapsed_time(e1) * 1e3 / n          # us
 
 
+def attn_head_dim_ab(context, emit, rounds=7):
+    """The fused attention launch at head_dim 64 against head_dim 128 at EQUAL KV heads, batch and context, rounds interleaved
+    in one process: the D = 64 launch reads half the cache bytes, so it must not take longer."""
+    from unsloth_amd.kernels import decode as D
+    dev, bf, Hq, S = "cuda", torch.bfloat16, 32, context
+    for Hk in (8, 4):
+        fns = {}
+        for Dh in (128, 64):
+            kc = torch.randn(1, Hk, S, Dh, device=dev, dtype=bf)
+            vc = torch.randn(1, Hk, S, Dh, device=dev, dtype=bf)
+            qkv = torch.randn(1, (Hq + 2 * Hk) * Dh, device=dev, dtype=bf)
+            cos = torch.randn(S, Dh // 2, device=dev, dtype=bf)
+            sin = torch.randn(S, Dh // 2, device=dev, dtype=bf)
+            kvl = torch.full((1,), S - 1, dtype=torch.int32, device=dev)
+            fpart, cnt = D.fused_attn_workspace(1, Hq, Hk, S, Dh, 128, dev)
+            ao = torch.empty(1, Hq * Dh, device=dev, dtype=bf)
+            fns[Dh] = (lambda t=(qkv, cos, sin, kvl, kc, vc, ao, fpart, cnt), sc=1.0 / Dh ** 0.5:
+                       D.attn_decode_fused(*t, 128, sc, Hq))
+        us = {128: [], 64: []}
+        for _ in range(rounds):
+            for Dh in (128, 64):
+                us[Dh].append(timeit(fns[Dh], n=50))
+        for Dh in (128, 64):
+            byts = 2 * S * Hk * Dh * 2
+            v = sorted(us[Dh])
+            emit(dict(kernel="fused attention, head_dim A/B", head_dim=Dh, kv_heads=Hk, q_heads=Hq, context=S, rounds=rounds,
+                      us_median=round(v[len(v) // 2], 2), us_min=round(v[0], 2), us_max=round(v[-1], 2), bytes=byts,
+                      frac_hbm=round(byts / (v[len(v) // 2] * 1e-6) / HBM, 3)))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--shape", choices=sorted(SHAPES), default="llama3-8b")
+    ap.add_argument("--layers", type=int, default=None, help="default: the shape's own (32 / 22)")
     ap.add_argument("--context", type=int, default=2048)
     ap.add_argument("--new", type=int, default=64)
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="whole model, hipGraph step only (for a rocprofv3 kernel trace)")
+    ap.add_argument("--attn-ab", action="store_true", help="only the fused attention launch, head_dim 64 against 128")
     a = ap.parse_args()
+    H, I, L0, Hq, Hk, Dh, V = SHAPES[a.shape]
+    if a.layers is None:
+        a.layers = L0
+    QN, KVN = Hq * Dh, Hk * Dh
     out = open(a.out, "w") if a.out else None
 
     def emit(d):
@@ -44,12 +83,14 @@ def main():
         if out:
             out.write(json.dumps(d) + "\n")
 
+    if a.attn_ab:
+        return attn_head_dim_ab(a.context, emit)
     from unsloth_amd.kernels import decode as D
     from unsloth_amd.nf4 import quantize_nf4
     dev, bf = "cuda", torch.bfloat16
-    # ---- GEMV kernels alone (Llama-3-8B shapes)
-    for name, Ns, K in () if a.quick else (("q|k|v", (4096, 1024, 1024), 4096), ("o", (4096,), 4096), ("gate|up", (14336, 14336), 4096),
-                        ("down", (4096,), 14336)):
+    # ---- GEMV kernels alone (the shape's projections)
+    for name, Ns, K in () if a.quick else (("q|k|v", (QN, KVN, KVN), H), ("o", (H,), QN), ("gate|up", (I, I), H),
+                        ("down", (H,), I)):
         x = torch.randn(K, device=dev, dtype=bf)
         projs = []
         for N in Ns:
@@ -64,7 +105,6 @@ def main():
                   frac_hbm=round(byts / (us * 1e-6) / HBM, 3)))
     # ---- the five launches of one fused decoder-layer step, each alone (LoRA r=16 on every projection, t = A x inside)
     from unsloth_amd.kernels.decode import attn_decode_fused, attn_decode, rope_kv_append
-    H, I, Hq, Hk, Dh = 4096, 14336, 32, 8, 128
 
     def lora_projs(Ns, K):
         ps = []
@@ -80,10 +120,10 @@ def main():
     wn = torch.ones(H, device=dev, dtype=bf)
     hbuf = torch.empty(H, device=dev, dtype=bf)
     for name, Ns, K, fused, xin in () if a.quick else (
-            ("q|k|v  (add + RMSNorm in)", (4096, 1024, 1024), H, dict(mode=2, res=resid, norm_w=wn, eps=1e-5, h_out=hbuf), delta),
-            ("o", (4096,), H, dict(mode=0), delta),
+            ("q|k|v  (add + RMSNorm in)", (QN, KVN, KVN), H, dict(mode=2, res=resid, norm_w=wn, eps=1e-5, h_out=hbuf), delta),
+            ("o", (H,), QN, dict(mode=0), delta[:QN] if QN <= H else torch.randn(QN, device=dev, dtype=bf)),
             ("gate|up (add + RMSNorm in, SwiGLU out)", (I, I), H, dict(mode=2, res=resid, norm_w=wn, eps=1e-5, h_out=hbuf, glu=True), delta),
-            ("down", (4096,), I, dict(mode=0), torch.randn(I, device=dev, dtype=bf))):
+            ("down", (H,), I, dict(mode=0), torch.randn(I, device=dev, dtype=bf))):
         projs = lora_projs(Ns, K)
         outbuf = torch.empty(Ns[0] if fused.get("glu") else sum(Ns), device=dev, dtype=bf)
         us = timeit(lambda: D.linear_group(xin, projs, out=outbuf, fused=fused))
@@ -101,17 +141,18 @@ def main():
     part = torch.empty(1, Hq, S // 128, Dh + 2, dtype=torch.float32, device=dev)
     fpart, cnt = D.fused_attn_workspace(1, Hq, Hk, S, Dh, 128, dev)
     ao = torch.empty(1, Hq * Dh, device=dev, dtype=bf)
-    us = timeit(lambda: attn_decode_fused(qkv, cos, sin, kvl, kc, vc, ao, fpart, cnt, 128, 0.088, Hq))
+    sc = round(1.0 / Dh ** 0.5, 3)                       # 0.088 at head_dim 128
+    us = timeit(lambda: attn_decode_fused(qkv, cos, sin, kvl, kc, vc, ao, fpart, cnt, 128, sc, Hq))
 
     def three():
         rope_kv_append(qkv, cos, sin, kvl, kc, vc, Hq, Hk, Dh)
-        attn_decode(qkv[:, :Hq * Dh], kc, vc, kvl, ao, part, 128, 0.088)
+        attn_decode(qkv[:, :Hq * Dh], kc, vc, kvl, ao, part, 128, sc)
     us3 = timeit(three)
     byts = 2 * S * Hk * Dh * 2
     emit(dict(kernel=f"fused attention (rope + append + split-KV + combine), context {S}", us=round(us, 2),
               three_launches_us=round(us3, 2), bytes=byts, GBps=round(byts / us / 1e3, 1), frac_hbm=round(byts / (us * 1e-6) / HBM, 3)))
     del kc, vc
-    V, K = 128256, 4096
+    K = H
     W = (torch.randn(V, K, device=dev) * 0.02).to(bf)
     x = torch.randn(K, device=dev, dtype=bf)
     us = timeit(lambda: D.gemv(x, [dict(W=W, N=V, y_f32=True)], nf4=False))
@@ -126,7 +167,7 @@ def main():
     from unsloth_amd import FastLanguageModel
     from unsloth_amd.models import decode as MD
     from unsloth_amd.models.decode import DecodeEngine
-    cfg = B.llama3_8b_config(a.layers)
+    cfg = B.llama3_8b_config(a.layers) if a.shape == "llama3-8b" else B.tinyllama_1b_config(a.layers)
     model, _ = FastLanguageModel.from_pretrained(config=cfg, max_seq_length=a.context, dtype=torch.bfloat16, load_in_4bit=True,
                                                  device=torch.device(dev), random_state=3407, use_gradient_checkpointing=False)
     model = FastLanguageModel.get_peft_model(model, r=16, lora_alpha=16, lora_dropout=0.0, bias="none",

@@ -62,17 +62,21 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
 }
 
 // Reductions on the VALU only (DPP), no LDS round trips: a ds_bpermute-based __shfl_xor costs ~100+ cycles of latency per
-// step, and a decode step is nothing but latency. row16_sum: every lane ends with the sum over its 16-lane row
-// (quad swaps, then the two mirror patterns pair each lane with the partial sum it is missing).
+// step, and a decode step is nothing but latency. lanes_sum<16>: every lane ends with the sum over its 16-lane row
+// (quad swaps, then the two mirror patterns pair each lane with the partial sum it is missing); lanes_sum<8> stops after
+// row_half_mirror, where every lane holds the sum of its 8-lane half row.
 #define UAMD_DPP_ADD(v, CTRL) ((v) + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, (v)), (CTRL), 0xf, 0xf, true)))
-__device__ __forceinline__ float row16_sum(float v) {
+template <int LANES>
+__device__ __forceinline__ float lanes_sum(float v) {
+    static_assert(LANES == 8 || LANES == 16, "half a DPP row or a whole one");
     v = UAMD_DPP_ADD(v, 0xb1);      // quad_perm [1,0,3,2]
     v = UAMD_DPP_ADD(v, 0x4e);      // quad_perm [2,3,0,1]
     v = UAMD_DPP_ADD(v, 0x141);     // row_half_mirror
-    v = UAMD_DPP_ADD(v, 0x140);     // row_mirror
+    if constexpr (LANES == 16) v = UAMD_DPP_ADD(v, 0x140);     // row_mirror
     return v;
 }
-__device__ __forceinline__ float wave_sum_dpp(float v) {             // wave-uniform total of all 64 lanes
+__device__ __forceinline__ float row16_sum(float v) { return lanes_sum<16>(v); }
+__device__ __forceinline__ float wave_sum_dpp(float v) {            // wave-uniform total of all 64 lanes
     v = row16_sum(v);
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0)) +
            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16)) +
@@ -748,11 +752,17 @@ __global__ void __launch_bounds__(64) rope_append_kernel(T* __restrict__ qkv, in
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Split-KV decode attention, D = 128. Block (split, kvh, b) = 4 waves; a wave-load covers 4 keys (16 lanes x 16 B
-// per key); every 16-lane group keeps, for each of the G query heads, an online-softmax partial over its keys with
-// the output restricted to the lane's 8 head-dim columns. Partials: [B, Hq, nsplit, D + 2] fp32 (o[D], m, l).
-constexpr int DD = 128;
-template <typename T, int G>
+// Split-KV decode attention, head dim DD = 128 or 64. Block (split, kvh, b) = 4 waves; a key is DD / 8 lanes x 16 B, so a
+// wave-load (all 64 lanes, 1 KiB) covers 4 keys at DD = 128 and 8 at DD = 64; every such lane group keeps, for each of the G
+// query heads, an online-softmax partial over its keys with the output restricted to the lane's 8 head-dim columns.
+// Partials: [B, Hq, nsplit, DD + 2] fp32 (o[DD], m, l).
+template <int DD> struct DecGeo {
+    static_assert(DD == 64 || DD == 128, "decode attention: head dim 64 or 128");
+    static constexpr int LPK = DD / 8;          // lanes per key, 8 columns (16 B) each
+    static constexpr int KPW = 64 / LPK;        // keys per wave-load
+    static constexpr int KPB = 4 * KPW;         // keys per block-load: the loop stride and the alignment of a split's start
+};
+template <typename T, int G, int DD>
 __global__ void __launch_bounds__(256) attn_decode_kernel(const T* __restrict__ q, int64_t q_sb, const T* __restrict__ kc,
                                                           const T* __restrict__ vc, int64_t c_sb, int64_t c_sh,
                                                           const int* __restrict__ kv_len, float* __restrict__ part,
@@ -760,7 +770,8 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const T* __restrict__ 
                                                           float scale_log2, int len_add) {
     const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int grp = lane >> 4, l16 = lane & 15;           // key slot of the wave-load, 8-column slice
+    constexpr int LPK = DecGeo<DD>::LPK, KPW = DecGeo<DD>::KPW, KPB = DecGeo<DD>::KPB;
+    const int grp = lane / LPK, lc = lane % LPK;          // key slot of the wave-load, 8-column slice
     const int len = kv_len[b] + len_add;                  // keys 0 .. len-1 are valid (the new token included)
     const int first = (window > 0 && len > window) ? len - window : 0;
     const int s0 = split * split_keys, s1 = min(s0 + split_keys, len);
@@ -771,26 +782,26 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const T* __restrict__ 
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         m[g] = -INFINITY; l[g] = 0.f;
-        const T* qp = q + (int64_t)b * q_sb + (int64_t)(kvh * G + g) * DD + l16 * 8;
+        const T* qp = q + (int64_t)b * q_sb + (int64_t)(kvh * G + g) * DD + lc * 8;
         const Vec16<T> v = ld16(qp);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { qv[g][j] = to_f32(v.e[j]) * scale_log2; o[g][j] = 0.f; }
     }
     const T* kb = kc + (int64_t)b * c_sb + (int64_t)kvh * c_sh;
     const T* vb = vc + (int64_t)b * c_sb + (int64_t)kvh * c_sh;
-    for (int k0 = max(s0, first & ~15) + wave * 4; k0 < s1; k0 += 16) {
+    for (int k0 = max(s0, first & ~(KPB - 1)) + wave * KPW; k0 < s1; k0 += KPB) {
         const int key = k0 + grp;
         const bool valid = key < s1 && key >= first;
         const int kl = valid ? key : (len > 0 ? len - 1 : 0);
-        const Vec16<T> kk = ld16(kb + (int64_t)kl * DD + l16 * 8);
-        const Vec16<T> vv = ld16(vb + (int64_t)kl * DD + l16 * 8);
+        const Vec16<T> kk = ld16(kb + (int64_t)kl * DD + lc * 8);
+        const Vec16<T> vv = ld16(vb + (int64_t)kl * DD + lc * 8);
         float s[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             float a = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) a += qv[g][j] * to_f32(kk.e[j]);
-            a = row16_sum(a);                             // the key's 16 lanes all get q . k
+            a = lanes_sum<LPK>(a);                        // the key's lanes all get q . k
             s[g] = valid ? a : -INFINITY;
         }
 #pragma unroll
@@ -805,11 +816,11 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const T* __restrict__ 
             for (int j = 0; j < 8; ++j) o[g][j] = o[g][j] * alpha + pe * to_f32(vv.e[j]);
         }
     }
-    // combine: the 4 key slots of a wave by shuffles (lanes with the same column slice), then the 4 waves through LDS
+    // combine: the key slots of a wave by shuffles (lanes with the same column slice), then the 4 waves through LDS
 #pragma unroll
     for (int g = 0; g < G; ++g) {
 #pragma unroll
-        for (int off = 16; off <= 32; off <<= 1) {
+        for (int off = LPK; off <= 32; off <<= 1) {
             const float mo = __shfl_xor(m[g], off, 64), lo = __shfl_xor(l[g], off, 64);
             const float mn = fmaxf(m[g], mo);
             const float mr = mn == -INFINITY ? 0.f : mn;
@@ -819,10 +830,10 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const T* __restrict__ 
             for (int j = 0; j < 8; ++j) o[g][j] = o[g][j] * a + __shfl_xor(o[g][j], off, 64) * c;
             m[g] = mn;
         }
-        if (lane < 16) {
-            if (l16 == 0) { red[wave][g][0] = m[g]; red[wave][g][1] = l[g]; }
+        if (lane < LPK) {
+            if (lc == 0) { red[wave][g][0] = m[g]; red[wave][g][1] = l[g]; }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) red_o[wave][g][l16 * 8 + j] = o[g][j];
+            for (int j = 0; j < 8; ++j) red_o[wave][g][lc * 8 + j] = o[g][j];
         }
     }
     __syncthreads();
@@ -845,8 +856,8 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const T* __restrict__ 
     }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(128) attn_decode_combine_kernel(const float* __restrict__ part, T* __restrict__ out,
+template <typename T, int DD>
+__global__ void __launch_bounds__(DD) attn_decode_combine_kernel(const float* __restrict__ part, T* __restrict__ out,
                                                                   int64_t o_sb, int Hq, int nsplit) {
     const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
     const float* pp = part + ((int64_t)b * Hq + h) * nsplit * (DD + 2);
@@ -878,17 +889,17 @@ __global__ void __launch_bounds__(128) attn_decode_combine_kernel(const float* _
 // ---------------------------------------------------------------------------------------------------------------
 // RoPE + cache append + split-KV attention + combine as ONE launch (uamd_attn_decode_fused). Same RoPE arithmetic, key
 // partition and combine order as rope_append_kernel -> attn_decode_kernel -> attn_decode_combine_kernel; the keys of a
-// split are accumulated chunk-wise (one running-max rescale per 8 keys of a lane group instead of one per key), so the
+// split are accumulated chunk-wise (one running-max rescale per NI keys of a lane group instead of one per key), so the
 // result equals the three launches' to fp32 rounding, not bit for bit. What changes:
-//   * every block rotates the G query heads of its KV head itself from the raw q|k|v row (G x 64 pairs; qkv is not written);
+//   * every block rotates the G query heads of its KV head itself from the raw q|k|v row (G x D/2 pairs; qkv is not written);
 //   * the block whose split owns position len0 = kv_len[b] rotates the new k, appends k and v to the cache and takes both
 //     from LDS when its loop reaches that key (a store followed by a load of the same line in one kernel would depend on the
 //     vector cache's write policy);
-//   * all K / V loads of a split (8 wave-loads of each for 128 keys) are issued before the first one is used: the old loop
-//     paid one HBM round trip per 16 keys, eight in a row;
+//   * all K / V loads of a 128-key trip (NI wave-loads of each: 8 at D = 128, 4 at D = 64, where a wave-load covers twice the
+//     keys) are issued before the first one is used: the old loop paid one HBM round trip per block-load, eight in a row;
 //   * the combine. Launches of up to 256 blocks (context 4096 at 8 KV heads): partials travel as 8-byte {value, tag}
 //     granules (one device-scope store each, never torn, no fence; the caller's launch tag as in gemv_kernel) and every block
-//     combines ITS 1 / nsplit of the G x 128 outputs, polling the granules of all splits in split order. Larger launches
+//     combines ITS 1 / nsplit of the G x D outputs, polling the granules of all splits in split order. Larger launches
 //     (not certainly resident at once): plain partials, release fence, arrival counter; the last block of a (batch, KV head)
 //     combines everything after an acquire fence -- measured at 21 us for this tail (buffer_wbl2 4.5 us, the atomic's round
 //     trip 5.5 us, the cold re-read of the partials 9.5 us; profiles/r04u_decode_phase_trace.txt), the price of the two
@@ -906,12 +917,13 @@ struct AttnDecFusedArgs {
     unsigned tag;
     const int* tag_dev;
 };
-template <typename T, int G>
+template <typename T, int G, int DD>
 __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs a) {
-    constexpr int NI = 8;                                 // wave-loads of K (and of V) in flight: 128 keys per block trip
+    constexpr int NI = 128 / DecGeo<DD>::KPB;             // wave-loads of K (and of V) in flight: 128 keys per block trip
     const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int grp = lane >> 4, l16 = lane & 15;
+    constexpr int LPK = DecGeo<DD>::LPK, KPW = DecGeo<DD>::KPW, KPB = DecGeo<DD>::KPB;
+    const int grp = lane / LPK, lc = lane % LPK;
     const int len0 = a.kv_len[b];                         // keys already in the cache = index of the new one
     const int pos = a.rope_pos ? a.rope_pos[b] : len0;
     const int len = len0 + 1;
@@ -932,6 +944,7 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
     const T* cs = (const T*)a.cos_t + (int64_t)pos * a.ld_cs;
     const T* sn = (const T*)a.sin_t + (int64_t)pos * a.ld_cs;
     constexpr int HALF = DD / 2;
+    static_assert(HALF <= 64 && 64 + DD <= 256, "wave 0 rotates the new k, the lanes from wave 1 on copy the new v");
     // rounding points of rope_append_kernel (= the training kernel for 16-bit tables): every product and the sum rounded to T
     for (int i = tid; i < G * HALF; i += 256) {
         const int g = i / HALF, j = i - g * HALF;
@@ -972,20 +985,20 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
     for (int g = 0; g < G; ++g) {
         m[g] = -INFINITY; l[g] = 0.f;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { qv[g][j] = q_s[g][l16 * 8 + j]; o[g][j] = 0.f; }
+        for (int j = 0; j < 8; ++j) { qv[g][j] = q_s[g][lc * 8 + j]; o[g][j] = 0.f; }
     }
     const T* kb = (const T*)a.kc + (int64_t)b * a.c_sb + (int64_t)kvh * a.c_sh;
     const T* vb = (const T*)a.vc + (int64_t)b * a.c_sb + (int64_t)kvh * a.c_sh;
     const int safe = len0 > 0 ? len0 - 1 : 0;
-    for (int base = max(s0, first & ~15) + wave * 4; base < s1; base += 16 * NI) {
+    for (int base = max(s0, first & ~(KPB - 1)) + wave * KPW; base < s1; base += KPB * NI) {
         Vec16<T> kk[NI], vv[NI];
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            const int key = base + 16 * i + grp;
+            const int key = base + KPB * i + grp;
             const bool cached = key < s1 && key >= first && key != len0;
             const int kl = cached ? key : safe;
-            kk[i] = ld16(kb + (int64_t)kl * DD + l16 * 8);
-            vv[i] = ld16(vb + (int64_t)kl * DD + l16 * 8);
+            kk[i] = ld16(kb + (int64_t)kl * DD + lc * 8);
+            vv[i] = ld16(vb + (int64_t)kl * DD + lc * 8);
         }
         DSTAMP(3);
 #ifdef UAMD_DECODE_TRACE
@@ -998,18 +1011,18 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
         float sc[NI][G];
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            const int key = base + 16 * i + grp;
+            const int key = base + KPB * i + grp;
             const bool valid = key < s1 && key >= first;
             if (own && key == len0) {
-                kk[i] = *reinterpret_cast<const Vec16<T>*>(kn + l16 * 8);
-                vv[i] = *reinterpret_cast<const Vec16<T>*>(vn + l16 * 8);
+                kk[i] = *reinterpret_cast<const Vec16<T>*>(kn + lc * 8);
+                vv[i] = *reinterpret_cast<const Vec16<T>*>(vn + lc * 8);
             }
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 float acc = 0.f;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc += qv[g][j] * to_f32(kk[i].e[j]);
-                acc = row16_sum(acc);
+                acc = lanes_sum<LPK>(acc);
                 sc[i][g] = valid ? acc : -INFINITY;
             }
         }
@@ -1040,7 +1053,7 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
 #pragma unroll
     for (int g = 0; g < G; ++g) {
 #pragma unroll
-        for (int off = 16; off <= 32; off <<= 1) {
+        for (int off = LPK; off <= 32; off <<= 1) {
             const float mo = __shfl_xor(m[g], off, 64), lo = __shfl_xor(l[g], off, 64);
             const float mn = fmaxf(m[g], mo);
             const float mr = mn == -INFINITY ? 0.f : mn;
@@ -1050,10 +1063,10 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
             for (int j = 0; j < 8; ++j) o[g][j] = o[g][j] * aa + __shfl_xor(o[g][j], off, 64) * c;
             m[g] = mn;
         }
-        if (lane < 16) {
-            if (l16 == 0) { red[wave][g][0] = m[g]; red[wave][g][1] = l[g]; }
+        if (lane < LPK) {
+            if (lc == 0) { red[wave][g][0] = m[g]; red[wave][g][1] = l[g]; }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) red_o[wave][g][l16 * 8 + j] = o[g][j];
+            for (int j = 0; j < 8; ++j) red_o[wave][g][lc * 8 + j] = o[g][j];
         }
     }
     __syncthreads();
@@ -1086,7 +1099,7 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
         }
     }
     if (a.gran) {
-        // ---- every block of the (batch, KV head) combines ITS share of the G x 128 outputs from the granules of all splits, in
+        // ---- every block of the (batch, KV head) combines ITS share of the G x D outputs from the granules of all splits, in
         //      split order (the old combine kernel's arithmetic). All blocks of the launch are resident (the host checks), and
         //      each has published before it polls: nobody waits for a block that has not started. Polls are bounded.
         DSTAMP(6);
@@ -1307,6 +1320,18 @@ extern "C" int uamd_rope_kv_append(void* qkv, int64_t ld_qkv, const void* cos_t,
     return uamd_launch_status();
 }
 
+// keys per block-load of the decode attention kernels (DecGeo<D>::KPB): split_keys must be a multiple of it
+static int dec_block_keys(int D) { return D == 64 ? DecGeo<64>::KPB : DecGeo<128>::KPB; }
+
+#define UAMD_DECODE_G(TT, DV)                                                                                 \
+    switch (G) {                                                                                              \
+        case 1: UAMD_DECODE_LAUNCH(TT, 1, DV); break; case 2: UAMD_DECODE_LAUNCH(TT, 2, DV); break;           \
+        case 3: UAMD_DECODE_LAUNCH(TT, 3, DV); break; case 4: UAMD_DECODE_LAUNCH(TT, 4, DV); break;           \
+        case 5: UAMD_DECODE_LAUNCH(TT, 5, DV); break; case 6: UAMD_DECODE_LAUNCH(TT, 6, DV); break;           \
+        case 7: UAMD_DECODE_LAUNCH(TT, 7, DV); break; case 8: UAMD_DECODE_LAUNCH(TT, 8, DV); break;           \
+        default: return UAMD_ERR_ARG;                                                                         \
+    }
+
 // out[b, h, :] = softmax(q[b, h] . K[b, h / G, first..len) * scale) V  over the cache (len = kv_len[b] + len_add;
 // window > 0: only the last `window` keys). partials: fp32 workspace [B, Hq, nsplit, D + 2]. Replaces
 // llama.py:499-543 (expand + matmul + softmax + matmul, or SDPA).
@@ -1315,39 +1340,32 @@ extern "C" int uamd_attn_decode(const void* q, int64_t q_sb, const void* k_cache
                                 int64_t out_sb, int B, int Hq, int Hk, int D, int nsplit, int split_keys, int window,
                                 float scale, int dtype, void* stream) {
     if (!q || !k_cache || !v_cache || !kv_len || !partials || !out || B <= 0 || Hq <= 0 || Hk <= 0 || Hq % Hk) return UAMD_ERR_ARG;
-    if (D != DD || nsplit <= 0 || split_keys <= 0 || (split_keys & 15)) return UAMD_ERR_ARG;
+    if ((D != 64 && D != 128) || nsplit <= 0 || split_keys <= 0 || split_keys % dec_block_keys(D)) return UAMD_ERR_ARG;
     if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || (q_sb & 7) || (cache_sb & 7) || (cache_sh & 7)) return UAMD_ERR_ALIGN;
     const int G = Hq / Hk;
     const float sl2 = scale * 1.4426950408889634f;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)nsplit, (unsigned)Hk, (unsigned)B);
-#define UAMD_DECODE_LAUNCH(TT, GG)                                                                                       \
-    hipLaunchKernelGGL((attn_decode_kernel<TT, GG>), grid, dim3(256), 0, st, (const TT*)q, q_sb, (const TT*)k_cache,      \
+#define UAMD_DECODE_LAUNCH(TT, GG, DV)                                                                                   \
+    hipLaunchKernelGGL((attn_decode_kernel<TT, GG, DV>), grid, dim3(256), 0, st, (const TT*)q, q_sb, (const TT*)k_cache,  \
                        (const TT*)v_cache, cache_sb, cache_sh, kv_len, partials, Hq, nsplit, split_keys, window, sl2, len_add)
     // every group size up to 8 (the kernel loops over its G query heads; Qwen2.5-7B / Qwen2-VL-7B: G = 7)
-#define UAMD_DECODE_G(TT)                                                                             \
-    switch (G) {                                                                                      \
-        case 1: UAMD_DECODE_LAUNCH(TT, 1); break; case 2: UAMD_DECODE_LAUNCH(TT, 2); break;           \
-        case 3: UAMD_DECODE_LAUNCH(TT, 3); break; case 4: UAMD_DECODE_LAUNCH(TT, 4); break;           \
-        case 5: UAMD_DECODE_LAUNCH(TT, 5); break; case 6: UAMD_DECODE_LAUNCH(TT, 6); break;           \
-        case 7: UAMD_DECODE_LAUNCH(TT, 7); break; case 8: UAMD_DECODE_LAUNCH(TT, 8); break;           \
-        default: return UAMD_ERR_ARG;                                                                 \
-    }
-    UAMD_DISPATCH_HALF(dtype,
-        UAMD_DECODE_G(T)
-        if (int rc = uamd_launch_status()) return rc;
-        hipLaunchKernelGGL((attn_decode_combine_kernel<T>), dim3(Hq, B), dim3(DD), 0, st, partials, (T*)out, out_sb, Hq, nsplit))
-#undef UAMD_DECODE_G
+#define UAMD_DECODE_D(TT, DV)                                                                         \
+    UAMD_DECODE_G(TT, DV)                                                                             \
+    if (int rc = uamd_launch_status()) return rc;                                                     \
+    hipLaunchKernelGGL((attn_decode_combine_kernel<TT, DV>), dim3(Hq, B), dim3(DV), 0, st, partials, (TT*)out, out_sb, Hq, nsplit)
+    UAMD_DISPATCH_HALF(dtype, if (D == 128) { UAMD_DECODE_D(T, 128); } else { UAMD_DECODE_D(T, 64); })
+#undef UAMD_DECODE_D
 #undef UAMD_DECODE_LAUNCH
     return uamd_launch_status();
 }
 
 namespace {
-// How many blocks of attn_decode_fused_kernel<T, G> are CERTAINLY resident at once on the current device: one per compute
+// How many blocks of attn_decode_fused_kernel<T, G, DD> are CERTAINLY resident at once on the current device: one per compute
 // unit THIS device has (a CPX / SPX partition reports its own CU count), and none when a block does not fit a CU at all.
 // The granule combine below polls for the other splits' partials, so a launch larger than this must not take it (a block
-// that starts only after another exits would be waited for in vain: 2^18 polls, then NaN). Cached per device.
-template <typename T, int G>
+// that starts only after another exits would be waited for in vain: 2^18 polls, then NaN). Cached per device and instantiation.
+template <typename T, int G, int DD>
 int attn_fused_resident_blocks() {
     static int cap[UAMD_DEVICE_SLOTS];
     const int dev = uamd_device_slot_or_neg();
@@ -1355,7 +1373,7 @@ int attn_fused_resident_blocks() {
     if (cap[dev] == 0) {
         int per_cu = 0;
         const int cus = uamd_cu_count();
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_decode_fused_kernel<T, G>, 256, 0) != hipSuccess || cus == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, attn_decode_fused_kernel<T, G, DD>, 256, 0) != hipSuccess || cus == 0) {
             (void)hipGetLastError();
             return 0;
         }
@@ -1373,7 +1391,7 @@ extern "C" int uamd_attn_decode_fused(const void* qkv, int64_t ld_qkv, const voi
     if (!qkv || !cos_t || !sin_t || !kv_len || !k_cache || !v_cache || !partials || !counters || !out || B <= 0 || Hq <= 0 ||
         Hk <= 0 || Hq % Hk || s_max <= 0)
         return UAMD_ERR_ARG;
-    if (D != DD || nsplit <= 0 || split_keys <= 0 || (split_keys & 15)) return UAMD_ERR_ARG;
+    if ((D != 64 && D != 128) || nsplit <= 0 || split_keys <= 0 || split_keys % dec_block_keys(D)) return UAMD_ERR_ARG;
     if (!aligned16(k_cache) || !aligned16(v_cache) || (cache_sb & 7) || (cache_sh & 7)) return UAMD_ERR_ALIGN;
     const int G = Hq / Hk;
     AttnDecFusedArgs a;
@@ -1390,22 +1408,14 @@ extern "C" int uamd_attn_decode_fused(const void* qkv, int64_t ld_qkv, const voi
     a.tag_dev = tag_dev;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)nsplit, (unsigned)Hk, (unsigned)B);
-#define UAMD_DECODE_LAUNCH(TT, GG)                                                                     \
+#define UAMD_DECODE_LAUNCH(TT, GG, DV)                                                                 \
     do {                                                                                               \
-        a.gran = (want_gran && blocks <= attn_fused_resident_blocks<TT, GG>()) ? 1 : 0;                \
-        hipLaunchKernelGGL((attn_decode_fused_kernel<TT, GG>), grid, dim3(256), 0, st, a);             \
+        a.gran = (want_gran && blocks <= attn_fused_resident_blocks<TT, GG, DV>()) ? 1 : 0;            \
+        hipLaunchKernelGGL((attn_decode_fused_kernel<TT, GG, DV>), grid, dim3(256), 0, st, a);         \
     } while (0)
-#define UAMD_DECODE_G(TT)                                                                             \
-    switch (G) {                                                                                      \
-        case 1: UAMD_DECODE_LAUNCH(TT, 1); break; case 2: UAMD_DECODE_LAUNCH(TT, 2); break;           \
-        case 3: UAMD_DECODE_LAUNCH(TT, 3); break; case 4: UAMD_DECODE_LAUNCH(TT, 4); break;           \
-        case 5: UAMD_DECODE_LAUNCH(TT, 5); break; case 6: UAMD_DECODE_LAUNCH(TT, 6); break;           \
-        case 7: UAMD_DECODE_LAUNCH(TT, 7); break; case 8: UAMD_DECODE_LAUNCH(TT, 8); break;           \
-        default: return UAMD_ERR_ARG;                                                                 \
-    }
-    UAMD_DISPATCH_HALF(dtype, UAMD_DECODE_G(T))
-#undef UAMD_DECODE_G
+    UAMD_DISPATCH_HALF(dtype, if (D == 128) { UAMD_DECODE_G(T, 128) } else { UAMD_DECODE_G(T, 64) })
 #undef UAMD_DECODE_LAUNCH
+#undef UAMD_DECODE_G
     return uamd_launch_status();
 }
 

@@ -13,6 +13,14 @@ from .. import _lib
 from .._lib import GemvGroup, GemvPrologue
 
 MAX_GROUPS = 4
+HEAD_DIMS = (64, 128)                 # the head dims the attention kernels are instantiated for
+
+
+def block_keys(D):
+    """Keys one block-load of the decode attention kernels covers (4 waves x 64 lanes x 16 B over D 16-bit values per key):
+    `split_keys` must be a multiple of it."""
+    assert D in HEAD_DIMS
+    return 2048 // D
 _SYNC = {}
 
 

@@ -59,8 +59,8 @@ class DecodeEngine:
         self.S = int(math.ceil(max_seq_len / SPLIT_KEYS) * SPLIT_KEYS)
         self.Hq, self.Hk = cfg.num_attention_heads, cfg.num_key_value_heads
         self.D = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
-        if self.D != 128:
-            raise NotImplementedError("decode attention kernel: head_dim 128 only")
+        if self.D not in _dk.HEAD_DIMS:
+            raise NotImplementedError(f"decode attention kernels: head_dim 64 or 128 only (got {self.D})")
         if getattr(cfg, "hidden_act", "silu") != "silu":
             raise NotImplementedError("decode path: SwiGLU MLP only")
         self.window = int(getattr(cfg, "sliding_window", None) or 0)
@@ -83,7 +83,8 @@ class DecodeEngine:
         # profiles/r04_decode_split_keys_ab.txt), longer ones where 128 would mean more than 256 workgroups -- up to 256 of them
         # combine through granules, a larger launch pays the 21 us fence + arrival-counter tail: 256 keys at context 8192 with 8 KV
         # heads, 1024 at 32768
-        self.fsplit = max(SPLIT_KEYS, int(math.ceil(self.S * self.Hk * batch / 256 / 16) * 16))
+        bk = _dk.block_keys(self.D)                   # a split is whole block-loads of the kernel: 16 keys at D = 128, 32 at D = 64
+        self.fsplit = max(SPLIT_KEYS, int(math.ceil(self.S * self.Hk * batch / 256 / bk) * bk))
         self.fpartials, self.counters = _dk.fused_attn_workspace(batch, self.Hq, self.Hk, self.S, self.D, self.fsplit, self.dev,
                                                                   step_dev=self.step_ctr)
         self.sync = _dk.HandOff(self.dev, step_dev=self.step_ctr)                             # uamd_gemv_fused hand-off

@@ -787,7 +787,7 @@ class FastLlamaModel:
     def for_inference(model):
         """llama.py:3888-3929: eval mode, no checkpointing, and `model.generate` = the KV-cache decode engine
         (models/decode.py: unsloth_fast_generate, the counterpart of llama.py:2167-2259) for the architectures it covers
-        (head_dim 128, SwiGLU); the HF `generate` stays reachable as `model._old_generate`, as in the reference."""
+        (head_dim 64 or 128, SwiGLU); the HF `generate` stays reachable as `model._old_generate`, as in the reference."""
         from types import MethodType
         from . import decode as _decode
         base = model.get_base_model() if hasattr(model, "get_base_model") else model
@@ -797,7 +797,7 @@ class FastLlamaModel:
         model.eval()
         cfg = base.config
         head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
-        if head_dim == 128 and getattr(cfg, "hidden_act", "silu") == "silu" and not hasattr(model, "_old_generate"):
+        if head_dim in _decode._dk.HEAD_DIMS and getattr(cfg, "hidden_act", "silu") == "silu" and not hasattr(model, "_old_generate"):
             if hasattr(model, "generate"):
                 model._old_generate = model.generate
             model.generate = MethodType(_decode.unsloth_fast_generate, model)
