@@ -7,7 +7,8 @@
 import pytest
 import torch
 
-from tests._util import rel_fro
+from tests._util import adamw_ref64, assert_adamw_close, rel_fro
+from tests.test_gpu_optim_kernels import RATIO_BOUND
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -176,15 +177,22 @@ def test_config3_llama3_8b_widths_full_finetune_seq2048_step():
     # one optimizer step
     grads = {n: p.grad.detach().float().clone() for n, p in model.named_parameters()}
     opt.step()
-    worst_p = 0.0
     for n, p in model.named_parameters():
+        # (the operand scale of the fp64 first step from the same master and gradient: before torch steps m32 in place)
+        scale = adamw_ref64(masters[n], grads[n], torch.zeros_like(masters[n]), torch.zeros_like(masters[n]), 1e-3,
+                            (0.9, 0.999), 1e-8, 0.01 if p.dim() > 1 else 0.0, 1)[3]["p"]
         m32 = torch.nn.Parameter(masters[n])
         m32.grad = grads[n]
         # HF Trainer's rule (get_decay_parameter_names): no decay on biases and norm weights, i.e. on 1-D parameters
         torch.optim.AdamW([m32], lr=1e-3, weight_decay=0.01 if m32.dim() > 1 else 0.0).step()
         assert torch.equal(p.detach(), m32.detach().to(torch.bfloat16)) or \
             (p.detach().float() - m32.detach().to(torch.bfloat16).float()).abs().max() <= 2 ** -8 * m32.abs().max(), n
-        worst_p = max(worst_p, (p.detach().float() - m32.detach()).abs().max().item())
+        # the fp32 master itself, element by element, and the parameter as that master rounded once
+        bi, o = opt.buckets._where[id(p)]
+        master = opt.master[bi][o:o + p.numel()].view(p.shape)
+        assert_adamw_close(master, m32.detach().double(), scale, RATIO_BOUND["p"], f"master of {n}")
+        assert torch.equal(p.detach(), master.to(torch.bfloat16)), n
+        del scale
     opt.zero_grad()
     assert all(p.grad is None for p in model.parameters())
     opt.buckets.close()
@@ -232,3 +240,103 @@ def test_full_finetune_biased_projections_and_reentrant_checkpointing(arch, gc):
         assert worst < max(2.5e-2, 1.25 * yw) and total < max(1.5e-2, 1.25 * yt), (worst, wk, total, yw, yt)
     finally:
         buckets.close()
+
+
+# ---- ShardedAdamW(optim_bits=32) element by element ------------------------------------------------------------------------
+def _sharded_pair(dtype, device):
+    from tests.test_optim_ref_host import LR, WD, Awkward
+    from unsloth_amd.full_finetune import ShardedAdamW
+    model = Awkward().to(dtype).to(device)
+    return model, ShardedAdamW(model, lr=LR, weight_decay=WD, optim_bits=32)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_sharded_adamw_awkward_buckets_against_torch_adamw(dtype):
+    """uamd_adamw_shard through ShardedAdamW (one rank) on buckets with padding between the views and decaying and
+    non-decaying runs side by side, six steps with an lr change, against torch.optim.AdamW on fp32 copies in two groups
+    (decay for dim() > 1). Each step starts torch from the optimizer's own masters and moments, so the bound is the one of a
+    single step (tests/test_gpu_optim_kernels.py) -- two fp32 runs left alone drift apart by more than that; the state the
+    optimizer carries from step to step is its own."""
+    from tests.test_optim_ref_host import LR, STEPS, WD, backward_and_finish, layout, lr_at
+    model, opt = _sharded_pair(dtype, DEV)
+    B = opt.buckets
+    assert [b["numel"] for b in B.buckets] == [2624, 2688] and [len(r) for r in opt._runs] == [3, 4]
+    twin = {id(p): torch.nn.Parameter(p.detach().float().clone()) for p in model.parameters()}
+    ropt = torch.optim.AdamW([dict(params=[twin[id(p)] for p in model.parameters() if p.dim() > 1], weight_decay=WD),
+                              dict(params=[twin[id(p)] for p in model.parameters() if p.dim() <= 1], weight_decay=0.0)],
+                             lr=LR, foreach=False, fused=False)
+    worst = dict(p=0.0, m=0.0, v=0.0)
+    for step in range(1, STEPS + 1):
+        for grp in opt.param_groups + ropt.param_groups:
+            grp["lr"] = lr_at(step)
+        backward_and_finish(opt, model, step)
+        scales = {}
+        for bi in range(len(B.buckets)):
+            for p, o, k, dec in layout(B, bi)[0]:
+                r, sl = twin[id(p)], slice(o, o + k)
+                own = [t[bi][sl].view(p.shape).clone() for t in (opt.master, opt.exp_avg, opt.exp_avg_sq)]
+                r.data.copy_(own[0])
+                r.grad = p.grad.detach().float().clone()
+                if step > 1:
+                    ropt.state[r]["exp_avg"].copy_(own[1])
+                    ropt.state[r]["exp_avg_sq"].copy_(own[2])
+                scales[id(p)] = adamw_ref64(own[0], r.grad, own[1], own[2], lr_at(step), (0.9, 0.999), 1e-8,
+                                            WD if dec else 0.0, step)[3]
+        opt.step()
+        ropt.step()
+        opt.zero_grad()
+        for bi, b in enumerate(B.buckets):
+            items, pad = layout(B, bi)
+            for name, (p, o, k, dec) in zip(b["names"], items):
+                r, sl, what = twin[id(p)], slice(o, o + k), f"{dtype} step {step} {name}"
+                for key, got, want in (("p", opt.master[bi], r.data), ("m", opt.exp_avg[bi], ropt.state[r]["exp_avg"]),
+                                       ("v", opt.exp_avg_sq[bi], ropt.state[r]["exp_avg_sq"])):
+                    worst[key] = max(worst[key], assert_adamw_close(got[sl].view(p.shape), want.double(), scales[id(p)][key],
+                                                                    RATIO_BOUND[key], f"{what} {key}"))
+                assert torch.equal(p.detach(), opt.master[bi][sl].view(p.shape).to(dtype)), what
+                assert p.data_ptr() == b["flat_p"].data_ptr() + 2 * o
+            assert int(pad.sum()) > 0 and float(b["flat_p"][pad.to(DEV)].float().abs().max()) == 0.0, f"step {step}: padding moved"
+    print(f"{dtype}: worst ratios against torch.optim.AdamW", worst)
+    B.close()
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_sharded_adamw_kernel_matches_the_host_branch(dtype):
+    """The kernel branch of ShardedAdamW.step against its host branch on a CPU copy (pinned to the restated arithmetic by
+    tests/test_optim_ref_host.py), six steps, each from the device's own state: masters and moments within the bound,
+    parameters equal except where the two masters straddle a rounding boundary -- at most 1 element in 4096 per step."""
+    from tests.test_optim_ref_host import CAP, STEPS, backward_and_finish, count_straddles, lr_at, restated_bucket_step
+    host, oh = _sharded_pair(dtype, "cpu")
+    dev, og = _sharded_pair(dtype, DEV)
+    nb = len(oh.buckets.buckets)
+    for bi in range(nb):
+        assert torch.equal(og.master[bi].cpu(), oh.master[bi])
+    for step in range(1, STEPS + 1):
+        for grp in oh.param_groups + og.param_groups:
+            grp["lr"] = lr_at(step)
+        backward_and_finish(oh, host, step)
+        backward_and_finish(og, dev, step)
+        scales = []
+        for bi in range(nb):
+            bh, bg = oh.buckets.buckets[bi], og.buckets.buckets[bi]
+            assert torch.equal(bg["flat_g"].cpu(), bh["flat_g"])
+            bh["flat_p"].copy_(bg["flat_p"])
+            for dst, src in ((oh.master, og.master), (oh.exp_avg, og.exp_avg), (oh.exp_avg_sq, og.exp_avg_sq)):
+                dst[bi].copy_(src[bi])
+            scales.append(restated_bucket_step(oh.buckets, bi, (oh.master[bi], oh.exp_avg[bi], oh.exp_avg_sq[bi]),
+                                               bh["flat_g"], step)[1])
+        oh.step()
+        og.step()
+        straddles = 0
+        for bi in range(nb):
+            for key, got, want in (("p", og.master, oh.master), ("m", og.exp_avg, oh.exp_avg), ("v", og.exp_avg_sq, oh.exp_avg_sq)):
+                assert_adamw_close(got[bi].cpu(), want[bi].double(), scales[bi][key], RATIO_BOUND[key],
+                                   f"{dtype} step {step} bucket {bi} {key}")
+            straddles += count_straddles(og.buckets.param_shard(bi).cpu(), oh.buckets.param_shard(bi), og.master[bi].cpu(),
+                                         oh.master[bi], f"{dtype} step {step} bucket {bi}")
+        total = sum(b["numel"] for b in oh.buckets.buckets)
+        assert straddles * CAP <= total, f"step {step}: {straddles} straddles in {total} elements"
+        oh.zero_grad()
+        og.zero_grad()
+    oh.buckets.close()
+    og.buckets.close()

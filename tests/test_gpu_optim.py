@@ -125,3 +125,73 @@ def test_training_with_flat_adamw_tracks_torch_adamw():
     assert curves[0][-1] < curves[0][0] - 0.5                       # it learns
     for x, y in zip(*curves):
         assert abs(x - y) <= 2e-3 * abs(y), curves
+
+
+def _six_steps_against_torch(shapes, skip=None, skip_steps=()):
+    """Six steps (the lr halves after three) of FlatAdamW and torch.optim.AdamW on the same gradients, compared with the
+    bounds of test_flat_adamw_matches_torch_adamw. `skip`: name of a parameter that has `grad = None` on `skip_steps` in both
+    optimizers -- it is only required to stay untouched over those steps (from then on torch bias-corrects it with its own
+    step count, FlatAdamW with the run's: see FlatAdamW.load_state_dict), every other parameter must match torch."""
+    from unsloth_amd.optim import FlatAdamW
+    lr, wd = 5e-3, 0.1
+    ref_model = _Bag(shapes)
+    model = copy.deepcopy(ref_model)
+    ref = torch.optim.AdamW(ref_model.parameters(), lr=lr, weight_decay=wd, betas=(0.9, 0.999), foreach=False, fused=False)
+    opt = FlatAdamW(model, lr=lr, weight_decay=wd)
+    rp = dict(ref_model.named_parameters())
+    params = dict(model.named_parameters())
+    for step in range(6):
+        gen = torch.Generator().manual_seed(50 + step)
+        skipping = skip is not None and step in skip_steps
+        for n, p in params.items():
+            gr = (torch.randn(p.shape, generator=gen) * (0.05 + 0.3 * step)).to(DEV)
+            if skipping and n == skip:
+                p.grad = None
+                rp[n].grad = None
+                continue
+            rp[n].grad = gr.clone()
+            p.grad.add_(gr)
+            opt.arena.ready(p)
+        if step == 3:
+            for grp in opt.param_groups + ref.param_groups:
+                grp["lr"] = lr * 0.5
+        if skipping:
+            st = opt.state[params[skip]]
+            before = [t.clone() for t in (params[skip].data, st["exp_avg"], st["exp_avg_sq"])]
+            runs = opt._runs()
+            assert len(runs) == 2 and all(s % 4 == 0 for s, _ in runs), runs       # two launches at offset pointers
+        else:
+            assert opt._runs() == [[0, opt.flat_p.numel()]]
+        ref.step()
+        opt.step()
+        if skipping:
+            for t, b in zip((params[skip].data, st["exp_avg"], st["exp_avg_sq"]), before):
+                assert torch.equal(t.view(torch.int32), b.view(torch.int32)), f"step {step}: the skipped parameter was written"
+        opt.zero_grad()
+        ref.zero_grad(set_to_none=True)
+        assert float(opt.arena.arena.abs().max()) == 0.0                # every element, the ragged tail included
+    for n, p in params.items():
+        if n == skip:
+            continue
+        torch.testing.assert_close(p.data, rp[n].data, rtol=1e-5, atol=1e-6)
+        st, rst = opt.state[p], ref.state[rp[n]]
+        torch.testing.assert_close(st["exp_avg"], rst["exp_avg"], rtol=1e-5, atol=1e-6)
+        torch.testing.assert_close(st["exp_avg_sq"], rst["exp_avg_sq"], rtol=1e-5, atol=1e-10)
+    return opt
+
+
+def test_flat_adamw_ragged_arena_matches_torch_adamw():
+    """An arena whose numel is no multiple of 4: the last factor in arena order (the last layer's lora_B, 7 x 3) ends in the
+    n % 4 tail of adamw_flat_kernel."""
+    opt = _six_steps_against_torch([((16, 64), (64, 16)), ((8, 100), (36, 8)), ((4, 4), (7, 3))])
+    n = opt.flat_p.numel()
+    assert n % 4 == 1 and opt._views[-1][2] == 21 and opt._views[-1][1] % 4 == 0
+    opt.close()
+
+
+def test_flat_adamw_parameter_without_gradient_splits_the_arena_into_two_runs():
+    """A parameter in the middle of the arena has grad = None on two of the six steps: the step is two launches at offset
+    pointers (the second one ragged), and the skipped parameter's data and both moments keep their bits."""
+    opt = _six_steps_against_torch([((16, 64), (64, 16)), ((8, 100), (36, 8)), ((4, 4), (7, 3))],
+                                   skip="layers.1.lora_B", skip_steps=(1, 4))
+    opt.close()

@@ -25,14 +25,18 @@ struct AdamArgs {
     int zero_grad;
 };
 
+// x - d, with x kept bit for bit when d is +-0: IEEE gives (-0) - (-0) = +0, and lr_wd * (-0) is -0, so a weight stored as
+// -0.0 would come back as +0.0 from every step (torch's p.mul_(1 - lr * wd) keeps it). Every other value is unchanged.
+__device__ __forceinline__ float sub_keep(float x, float d) { return d == 0.f ? x : x - d; }
+
 __device__ __forceinline__ void adamw_one(float& p, float& g, float& m, float& v, const AdamArgs& a) {
     const float gr = g * a.grad_scale;
     // same association as torch's fused kernel (fused_adam_utils.cuh adam_math): ... - step_size * m / denom
-    p = p - a.lr_wd * p;
+    p = sub_keep(p, a.lr_wd * p);
     m = a.b1 * m + a.omb1 * gr;
     v = a.b2 * v + a.omb2 * gr * gr;
     const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    p = p - a.step_size * m / denom;
+    p = sub_keep(p, a.step_size * m / denom);
 }
 
 __global__ void __launch_bounds__(256) adamw_flat_kernel(AdamArgs a) {
