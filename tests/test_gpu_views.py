@@ -126,17 +126,20 @@ def tuning():
 
 # ---------------------------------------------------------------------------------------------------------------- RMSNorm
 # rms_layernorm.hip launch_fwd / launch_bwd, `vec_ok`:
-#   aligned, padded                         -> the 16-byte vector kernels (rms_*_wave with UAMD_TUNE_RMS_VAR 0, rms_*_rb with 1)
+#   aligned, padded                         -> the 16-byte vector kernels rms_*_rows (a row per wave, TPR 64, with
+#                                              UAMD_TUNE_RMS_VAR 0; a row per block, TPR 256, with 1)
 #   odd_stride (stride % VEC), offset and
 #   offset_padded (pointer), cols = 100     -> rms_fwd_block / rms_bwd_block, scalar loads
 #   cols 64 VEC 8 | 64 VEC 8 + VEC          -> the backward's width limit: vector | block, on aligned data too
 #   cols 64 VEC 16 + VEC                    -> past the forward's limit: block kernels both ways
+#   cols 64 VEC k + VEC, k = 1, 2, 4        -> 2, 3, 5 vectors per lane of a wave: with 1 (33 VEC), 8 and 9 every ITERS of the
+#                                              ladders 1, 2, 4, 8, 16 (a row per wave) and 1, 2, 4 (per block: a quarter) runs
 RMS_ROWS = 5                        # four rows per block in the wave kernels: one full group and a one-row group
 
 
 def rms_cols(dtype):
     v = vec_of(dtype)
-    return [33 * v, 64 * v * 8, 64 * v * 8 + v, 64 * v * 16 + v, 100]
+    return [33 * v, 64 * v * 8, 64 * v * 8 + v, 64 * v * 16 + v, 100, 64 * v + v, 64 * v * 2 + v, 64 * v * 4 + v]
 
 
 @functools.lru_cache(maxsize=None)
@@ -153,7 +156,7 @@ def rms_case(dtype, cols, gemma, wdtype):
 
 
 @pytest.mark.parametrize("gemma", [False, True], ids=["llama", "gemma"])
-@pytest.mark.parametrize("ci", range(5), ids=["33v", "64v8", "64v8+v", "64v16+v", "c100"])
+@pytest.mark.parametrize("ci", range(8), ids=["33v", "64v8", "64v8+v", "64v16+v", "c100", "64v+v", "64v2+v", "64v4+v"])
 @pytest.mark.parametrize("dtype,lay", DTYPE_LAYOUT)
 def test_rmsnorm_on_views(tuning, dtype, lay, ci, gemma):
     from unsloth_amd.kernels.rms_layernorm import rms_bwd_, rms_fwd
@@ -262,7 +265,7 @@ def _add_rms_reference(x, res, W, dh_v, dy_v):
     return h1.detach(), y1.detach(), x1.grad, r1.grad
 
 
-@pytest.mark.parametrize("ci", range(3), ids=["33v", "64v8", "64v8+v"])
+@pytest.mark.parametrize("ci", [0, 1, 2, 5, 6, 7], ids=["33v", "64v8", "64v8+v", "64v+v", "64v2+v", "64v4+v"])
 @pytest.mark.parametrize("dtype,lay", DTYPE_LAYOUT)
 def test_fused_add_rmsnorm_on_views_equals_add_then_norm(dtype, lay, ci):
     from unsloth_amd.kernels import rms_layernorm as M
@@ -287,7 +290,7 @@ def test_fused_add_rmsnorm_on_views_equals_add_then_norm(dtype, lay, ci):
         h2, y2 = M.fast_add_rms_layernorm(_Norm(W), xv.requires_grad_(True), rv.requires_grad_(True))    # must not raise
     finally:
         del M.Fast_Add_RMS_Layernorm.apply
-    assert bool(fused) == (vectorizable(lay) and ci < 2), "which path ran"
+    assert bool(fused) == (vectorizable(lay) and cols <= 64 * vec_of(dtype) * 8), "which path ran"
     assert torch.isfinite(h2.float()).all() and torch.isfinite(y2.float()).all()
     assert torch.equal(h2, h1) and torch.equal(y2, y1)
     torch.autograd.backward([h2, y2], [dhv, dyv])
@@ -322,7 +325,7 @@ def test_fused_add_rmsnorm_backward_takes_misaligned_gradients(lay):
 # layernorm.hip ln_fwd / ln_bwd, `fast` (iters = ceil(cols / (256 VEC))):
 #   aligned, padded                         -> layernorm_fwd_kernel / layernorm_bwd_kernel (row in registers)
 #   odd_stride, offset, offset_padded       -> layernorm_*_generic, scalar loops
-#   cols 256 VEC 4 | 256 VEC 4 + VEC        -> the backward's `iters <= 4`: fast | generic (the forward stays fast: LN_F(4) | LN_F(8))
+#   cols 256 VEC 4 | 256 VEC 4 + VEC        -> the backward's `iters <= 4`: fast | generic (the forward stays fast: ITERS 4 | 8)
 #   cols 256 VEC 8 | 256 VEC 8 + VEC        -> the forward's LN_MAX_ITERS: fast | generic (the backward is generic for both)
 LN_ROWS = 5
 

@@ -34,10 +34,12 @@ def parse(path):
 
 def algorithmic_bytes(name, T, H=4096, I=14336, V=128256, Hq=32, Hk=8, D=128):
     """SURVEY 8(d) per-call figures for the kernels of the Llama-3-8B step (bf16); None where the table has no row."""
-    if name.startswith("rms_fwd_rb"):
-        # ",201" = the add-fused instance (reads x and the residual, writes h and y): 4 row passes instead of 2
+    # rms_*_rows<T, WT, TPR, ITERS, GEMMA, ADD>; profiles from before the two forms shared a kernel: rms_*_rb<T, WT, ITERS, GEMMA, ADD>
+    if name.startswith(("rms_fwd_rows", "rms_fwd_rb")):
+        # a last digit of 1 (",201", ",256201") = the add-fused instance (reads x and the residual, writes h and y): 4 row
+        # passes instead of 2
         return (4 if name.rstrip(">").endswith("1") else 2) * T * H * 2 + H * 2 + T * 4
-    if name.startswith("rms_bwd_rb"):
+    if name.startswith(("rms_bwd_rows", "rms_bwd_rb")):
         return (4 if name.rstrip(">").endswith("1") else 3) * T * H * 2 + H * 2 + T * 4
     if name.startswith("rope_vec"):
         return 2 * T * (Hq + Hk) * D * 2 + 2 * T * (D // 2) * 2

@@ -95,6 +95,12 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     for (int i = 0; i < NW; ++i) t += red[i];
     return t;
 }
+// Sum over the TPR threads that share a row: one wave (no LDS, no barrier; `red` unused) or the TPR / 64 waves of a block.
+template <int TPR>
+__device__ __forceinline__ float row_sum(float v, float* red) {
+    if constexpr (TPR == UAMD_WAVE) return wave_sum(v);
+    else return block_sum<TPR / UAMD_WAVE>(v, red);
+}
 template <int NW>
 __device__ __forceinline__ float block_max(float v, float* red) {
     v = wave_max(v);
@@ -259,3 +265,23 @@ static inline int uamd_cu_count_or_256() {
         case UAMD_F16: { using T = f16_t; __VA_ARGS__; break; }  \
         default: return UAMD_ERR_DTYPE;                       \
     }
+// ... and over the (activation, weight) pairs of the norms: the weight in the activation's dtype or in fp32. The statement
+// given returns; any other pair returns UAMD_ERR_DTYPE.
+#define UAMD_NORM_PAIR_(xd, wd, XC, XT, WC, WT_, ...) \
+    if ((xd) == XC && (wd) == WC) { using T = XT; using WT = WT_; __VA_ARGS__; }
+#define UAMD_DISPATCH_NORM(x_dtype, w_dtype, ...)                                               \
+    UAMD_NORM_PAIR_(x_dtype, w_dtype, UAMD_BF16, bf16_t, UAMD_BF16, bf16_t, __VA_ARGS__)        \
+    UAMD_NORM_PAIR_(x_dtype, w_dtype, UAMD_F16, f16_t, UAMD_F16, f16_t, __VA_ARGS__)            \
+    UAMD_NORM_PAIR_(x_dtype, w_dtype, UAMD_F32, float, UAMD_F32, float, __VA_ARGS__)            \
+    UAMD_NORM_PAIR_(x_dtype, w_dtype, UAMD_BF16, bf16_t, UAMD_F32, float, __VA_ARGS__)          \
+    UAMD_NORM_PAIR_(x_dtype, w_dtype, UAMD_F16, f16_t, UAMD_F32, float, __VA_ARGS__)            \
+    return UAMD_ERR_DTYPE;
+
+// f(std::integral_constant<int, I>{}) for the smallest listed I >= iters (the last one listed takes what is left): a
+// run-time count of vectors per thread picks a kernel's compile-time ITERS.
+template <int I, int... Rest, typename F>
+static inline void uamd_with_iters(int iters, F&& f) {
+    if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, I>{});
+    else if (iters <= I) f(std::integral_constant<int, I>{});
+    else uamd_with_iters<Rest...>(iters, f);
+}

@@ -159,15 +159,12 @@ int ln_fwd(const void* X, const void* W, const void* B, void* Y, float* r, float
     const bool fast = iters <= LN_MAX_ITERS && n_cols % VEC == 0 && xs % VEC == 0 && ys % VEC == 0 && aligned16(X) &&
                       aligned16(Y) && aligned16(W) && aligned16(B);
     dim3 grid((unsigned)n_rows), block(256);
-#define LN_F(I) hipLaunchKernelGGL((layernorm_fwd_kernel<T, WT, I>), grid, block, 0, st, (const T*)X, (const WT*)W, \
-                                   (const WT*)B, (T*)Y, r, mu, n_cols, xs, ys, eps)
     if (!fast) hipLaunchKernelGGL((layernorm_fwd_generic<T, WT>), grid, block, 0, st, (const T*)X, (const WT*)W,
                                   (const WT*)B, (T*)Y, r, mu, n_cols, xs, ys, eps);
-    else if (iters <= 1) LN_F(1);
-    else if (iters <= 2) LN_F(2);
-    else if (iters <= 4) LN_F(4);
-    else LN_F(8);
-#undef LN_F
+    else uamd_with_iters<1, 2, 4, LN_MAX_ITERS>(iters, [&](auto it) {
+        hipLaunchKernelGGL((layernorm_fwd_kernel<T, WT, decltype(it)::value>), grid, block, 0, st, (const T*)X, (const WT*)W,
+                           (const WT*)B, (T*)Y, r, mu, n_cols, xs, ys, eps);
+    });
     return uamd_launch_status();
 }
 
@@ -179,26 +176,16 @@ int ln_bwd(void* dY, const void* X, const void* W, const float* r, const float* 
     const bool fast = iters <= 4 && n_cols % VEC == 0 && xs % VEC == 0 && dys % VEC == 0 && aligned16(X) &&
                       aligned16(dY) && aligned16(W);
     dim3 grid((unsigned)n_rows), block(256);
-#define LN_B(I) hipLaunchKernelGGL((layernorm_bwd_kernel<T, WT, I>), grid, block, 0, st, (T*)dY, (const T*)X, \
-                                   (const WT*)W, r, mu, n_cols, dys, xs)
     if (!fast) hipLaunchKernelGGL((layernorm_bwd_generic<T, WT>), grid, block, 0, st, (T*)dY, (const T*)X, (const WT*)W,
                                   r, mu, n_cols, dys, xs);
-    else if (iters <= 1) LN_B(1);
-    else if (iters <= 2) LN_B(2);
-    else LN_B(4);
-#undef LN_B
+    else uamd_with_iters<1, 2, 4>(iters, [&](auto it) {
+        hipLaunchKernelGGL((layernorm_bwd_kernel<T, WT, decltype(it)::value>), grid, block, 0, st, (T*)dY, (const T*)X,
+                           (const WT*)W, r, mu, n_cols, dys, xs);
+    });
     return uamd_launch_status();
 }
 
 }  // namespace
-
-#define LN_DISPATCH(xd, wd, CALL)                                                             \
-    if (xd == UAMD_BF16 && wd == UAMD_BF16) { using T = bf16_t; using WT = bf16_t; return CALL; } \
-    if (xd == UAMD_F16 && wd == UAMD_F16) { using T = f16_t; using WT = f16_t; return CALL; }     \
-    if (xd == UAMD_F32 && wd == UAMD_F32) { using T = float; using WT = float; return CALL; }     \
-    if (xd == UAMD_BF16 && wd == UAMD_F32) { using T = bf16_t; using WT = float; return CALL; }   \
-    if (xd == UAMD_F16 && wd == UAMD_F32) { using T = f16_t; using WT = float; return CALL; }     \
-    return UAMD_ERR_DTYPE;
 
 extern "C" int uamd_layernorm_fwd(const void* X, const void* W, const void* B, void* Y, float* r, float* mu,
                                   int64_t n_rows, int n_cols, int64_t x_row_stride, int64_t y_row_stride, float eps,
@@ -207,7 +194,7 @@ extern "C" int uamd_layernorm_fwd(const void* X, const void* W, const void* B, v
     if (n_rows == 0) return UAMD_OK;
     if (!X || !W || !B || !Y || !r || !mu) return UAMD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    LN_DISPATCH(x_dtype, w_dtype, (ln_fwd<T, WT>(X, W, B, Y, r, mu, n_rows, n_cols, x_row_stride, y_row_stride, eps, st)))
+    UAMD_DISPATCH_NORM(x_dtype, w_dtype, return ln_fwd<T, WT>(X, W, B, Y, r, mu, n_rows, n_cols, x_row_stride, y_row_stride, eps, st))
 }
 
 extern "C" int uamd_layernorm_bwd(void* dY, const void* X, const void* W, const float* r, const float* mu, int64_t n_rows,
@@ -217,5 +204,5 @@ extern "C" int uamd_layernorm_bwd(void* dY, const void* X, const void* W, const 
     if (n_rows == 0) return UAMD_OK;
     if (!dY || !X || !W || !r || !mu) return UAMD_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    LN_DISPATCH(x_dtype, w_dtype, (ln_bwd<T, WT>(dY, X, W, r, mu, n_rows, n_cols, dy_row_stride, x_row_stride, st)))
+    UAMD_DISPATCH_NORM(x_dtype, w_dtype, return ln_bwd<T, WT>(dY, X, W, r, mu, n_rows, n_cols, dy_row_stride, x_row_stride, st))
 }

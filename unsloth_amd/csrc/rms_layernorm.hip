@@ -5,11 +5,17 @@
 //   unsloth/kernels/rms_layernorm.py:62-120  _rms_layernorm_backward
 //   unsloth/kernels/rms_layernorm.py:123-159 _gemma_rms_layernorm_forward
 //
-// HBM-bound. Design for CDNA4: ONE WAVE (64 lanes) owns one row, the whole row lives in
-// registers as 16-byte vectors (single HBM read, all loads issued before the first use),
-// the reduction is a 6-step wave64 xor-shuffle: no LDS, no barrier. A 256-thread block
-// carries 4 rows. Rows that do not fit the register budget (or are not 16-byte aligned)
-// take the generic block-per-row two-pass kernel.
+// HBM-bound. The whole row lives in registers as 16-byte vectors (single HBM read, all loads issued before the first
+// use), shared by TPR threads of a 256-thread block; UAMD_TUNE_RMS_VAR picks TPR:
+//   1 (the default)  TPR = 256, one row per BLOCK: ITERS = n_cols / 2048 vectors per thread for 16-bit data (2 at hidden
+//                    4096) and ONE LDS reduction. Few registers per thread -> 8 blocks per CU resident and several passes
+//                    of blocks per launch, so the loads of one block overlap the stores of another.
+//   0                TPR = 64, one row per WAVE, 4 rows per block: the reduction is a 6-step wave64 xor-shuffle, no LDS,
+//                    no barrier, but all 8192 rows of a launch sit on the chip at once: one read phase, then one write
+//                    phase. Kept for the parity tests of the two forms.
+// The two forms sum a row in different (each fixed, run-to-run deterministic) orders; r is compared against the oracle
+// with a tolerance. Rows that do not fit the register budget (or are not 16-byte aligned) take the generic block-per-row
+// two-pass kernel.
 #include "common.h"
 
 namespace {
@@ -17,21 +23,22 @@ namespace {
 // ADD: the residual add in front of the norm is fused in -- h = T(x + res) (one rounding, what `residual + x`
 // gives in torch), h is written to Hout (the next residual) and normalised (llama.py:823-844 does add, then norm,
 // as two passes over the activations).
-template <typename T, typename WT, int ITERS, bool GEMMA, bool ADD = false>
+template <typename T, typename WT, int TPR, int ITERS, bool GEMMA, bool ADD>
 __global__ void __launch_bounds__(256)
-rms_fwd_wave(const T* __restrict__ X, const WT* __restrict__ W, T* __restrict__ Y,
+rms_fwd_rows(const T* __restrict__ X, const WT* __restrict__ W, T* __restrict__ Y,
              float* __restrict__ R, int64_t n_rows, int n_cols, int64_t xs, int64_t ys, float eps, int mode,
-             const T* __restrict__ Res = nullptr, T* __restrict__ Hout = nullptr, int64_t rs = 0, int64_t hs = 0) {
+             const T* __restrict__ Res, T* __restrict__ Hout, int64_t rs, int64_t hs) {
     constexpr int VEC = Vec16<T>::N;
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n_rows) return;
+    __shared__ float red[TPR / 64];
+    const unsigned t = TPR == 64 ? threadIdx.x & 63 : threadIdx.x;
+    const int64_t row = TPR == 64 ? (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : blockIdx.x;
+    if (TPR == 64 && row >= n_rows) return;
     const T* x = X + row * xs;
     Vec16<T> xv[ITERS];
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < ITERS; ++i) {
-        const int c = (lane + 64 * i) * VEC;
+        const int c = (t + TPR * i) * VEC;
         if (c < n_cols) xv[i] = ld16_m(x + c, mode);
         else xv[i].raw = make_uint4(0, 0, 0, 0);
     }
@@ -41,13 +48,13 @@ rms_fwd_wave(const T* __restrict__ X, const WT* __restrict__ W, T* __restrict__ 
         Vec16<T> rv[ITERS];
 #pragma unroll
         for (int i = 0; i < ITERS; ++i) {
-            const int c = (lane + 64 * i) * VEC;
+            const int c = (t + TPR * i) * VEC;
             if (c < n_cols) rv[i] = ld16_m(res + c, mode);
             else rv[i].raw = make_uint4(0, 0, 0, 0);
         }
 #pragma unroll
         for (int i = 0; i < ITERS; ++i) {
-            const int c = (lane + 64 * i) * VEC;
+            const int c = (t + TPR * i) * VEC;
 #pragma unroll
             for (int j = 0; j < VEC; ++j) xv[i].e[j] = from_f32<T>(to_f32(xv[i].e[j]) + to_f32(rv[i].e[j]));
             if (c < n_cols) st16(h + c, xv[i]);
@@ -57,13 +64,13 @@ rms_fwd_wave(const T* __restrict__ X, const WT* __restrict__ W, T* __restrict__ 
     for (int i = 0; i < ITERS; ++i)
 #pragma unroll
         for (int j = 0; j < VEC; ++j) { float f = to_f32(xv[i].e[j]); ss += f * f; }
-    ss = wave_sum(ss);
+    ss = row_sum<TPR>(ss, red);
     const float inv = rsqrtf(ss / (float)n_cols + eps);
-    if (lane == 0) R[row] = inv;
+    if (t == 0) R[row] = inv;
     T* y = Y + row * ys;
 #pragma unroll
     for (int i = 0; i < ITERS; ++i) {
-        const int c = (lane + 64 * i) * VEC;
+        const int c = (t + TPR * i) * VEC;
         if (c < n_cols) {
             Vec16<T> o;
             float wf[VEC];
@@ -85,188 +92,68 @@ rms_fwd_wave(const T* __restrict__ X, const WT* __restrict__ W, T* __restrict__ 
 
 // ADD: dX = T(T(rms_dx) + dRes): the gradient that reaches h = x + res from the residual path is added here
 // instead of by a separate autograd accumulation pass (same two roundings as that pass).
-template <typename T, typename WT, int ITERS, bool GEMMA, bool ADD = false>
+template <typename T, typename WT, int TPR, int ITERS, bool GEMMA, bool ADD>
 __global__ void __launch_bounds__(256)
-rms_bwd_wave(const T* dY, T* dX, const T* __restrict__ X,
+rms_bwd_rows(const T* dY, T* dX, const T* __restrict__ X,
              const WT* __restrict__ W, const float* __restrict__ R, int64_t n_rows, int n_cols,
-             int64_t dys, int64_t dxs, int64_t xs, int mode, const T* dRes = nullptr, int64_t drs = 0) {
+             int64_t dys, int64_t dxs, int64_t xs, int mode, const T* dRes, int64_t drs) {
     constexpr int VEC = Vec16<T>::N;
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n_rows) return;
+    // a row over a block leaves the registers to keep W (Gemma's +1 applied) and dRes from the first pass; over a wave
+    // (4x the vectors per thread) the second pass loads them: the other choice changes either form's occupancy
+    constexpr bool KEEP = TPR > 64;
+    __shared__ float red[TPR / 64];
+    const unsigned t = TPR == 64 ? threadIdx.x & 63 : threadIdx.x;
+    const int64_t row = TPR == 64 ? (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : blockIdx.x;
+    if (TPR == 64 && row >= n_rows) return;
     const T* dy = dY + row * dys;
     const T* x = X + row * xs;
-    Vec16<T> dv[ITERS], xv[ITERS];
+    Vec16<T> dv[ITERS], xv[ITERS], rv[KEEP && ADD ? ITERS : 1];
 #pragma unroll
     for (int i = 0; i < ITERS; ++i) {
-        const int c = (lane + 64 * i) * VEC;
-        if (c < n_cols) { dv[i] = ld16_m(dy + c, mode); xv[i] = ld16_m(x + c, mode); }
-        else { dv[i].raw = make_uint4(0, 0, 0, 0); xv[i].raw = make_uint4(0, 0, 0, 0); }
-    }
-    const float inv = R[row];
-    float rs = 0.f;
-#pragma unroll
-    for (int i = 0; i < ITERS; ++i) {
-        const int c = (lane + 64 * i) * VEC;
-        if (c < n_cols) {
-            float wf[VEC];
-            load_w<WT, VEC>(W + c, wf);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                float w = wf[j];
-                if (GEMMA) w += 1.0f;
-                rs += to_f32(dv[i].e[j]) * w * (to_f32(xv[i].e[j]) * inv);
-            }
-        }
-    }
-    rs = wave_sum(rs);
-    const float n = (float)n_cols;
-    T* dx = dX + row * dxs;
-#pragma unroll
-    for (int i = 0; i < ITERS; ++i) {
-        const int c = (lane + 64 * i) * VEC;
-        if (c < n_cols) {
-            Vec16<T> o;
-            float wf[VEC];
-            load_w<WT, VEC>(W + c, wf);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                float w = wf[j];
-                if (GEMMA) w += 1.0f;
-                const float dyw = to_f32(dv[i].e[j]) * w;
-                const float normed = to_f32(xv[i].e[j]) * inv;
-                // rms_layernorm.py:112
-                o.e[j] = from_f32<T>(inv / n * (n * dyw - normed * rs));
-            }
-            if (ADD) {
-                const Vec16<T> dr = ld16_m(dRes + row * drs + c, mode);
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) o.e[j] = from_f32<T>(to_f32(o.e[j]) + to_f32(dr.e[j]));
-            }
-            st16_m(dx + c, o, mode);
-        }
-    }
-}
-
-// Row-per-BLOCK variants (UAMD_TUNE_RMS_VAR = 1): the same arithmetic with the row spread over the 4 waves of a
-// 256-thread block (ITERS = n_cols / 2048 vectors per thread for 16-bit data: 2 at hidden 4096) and ONE LDS
-// reduction. Fewer registers per thread -> 8 blocks per CU resident and several passes of blocks per launch, so
-// the loads of one block overlap the stores of another (the wave-per-row kernels put all 8192 rows of a launch
-// on the chip at once: one read phase, then one write phase).
-template <typename T, typename WT, int ITERS, bool GEMMA, bool ADD = false>
-__global__ void __launch_bounds__(256)
-rms_fwd_rb(const T* __restrict__ X, const WT* __restrict__ W, T* __restrict__ Y,
-           float* __restrict__ R, int64_t n_rows, int n_cols, int64_t xs, int64_t ys, float eps, int mode,
-           const T* __restrict__ Res = nullptr, T* __restrict__ Hout = nullptr, int64_t rs = 0, int64_t hs = 0) {
-    constexpr int VEC = Vec16<T>::N;
-    __shared__ float red[4];
-    const int64_t row = blockIdx.x;
-    const T* x = X + row * xs;
-    Vec16<T> xv[ITERS];
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < ITERS; ++i) {
-        const int c = (threadIdx.x + 256 * i) * VEC;
-        if (c < n_cols) xv[i] = ld16_m(x + c, mode);
-        else xv[i].raw = make_uint4(0, 0, 0, 0);
-    }
-    if (ADD) {
-        const T* res = Res + row * rs;
-        T* h = Hout + row * hs;
-        Vec16<T> rv[ITERS];
-#pragma unroll
-        for (int i = 0; i < ITERS; ++i) {
-            const int c = (threadIdx.x + 256 * i) * VEC;
-            if (c < n_cols) rv[i] = ld16_m(res + c, mode);
-            else rv[i].raw = make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < ITERS; ++i) {
-            const int c = (threadIdx.x + 256 * i) * VEC;
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) xv[i].e[j] = from_f32<T>(to_f32(xv[i].e[j]) + to_f32(rv[i].e[j]));
-            if (c < n_cols) st16(h + c, xv[i]);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < ITERS; ++i)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) { float f = to_f32(xv[i].e[j]); ss += f * f; }
-    // same summation tree as the wave kernel would need is NOT required: r is compared against the oracle with a
-    // tolerance; the fixed-order block sum keeps it run-to-run deterministic
-    ss = block_sum<4>(ss, red);
-    const float inv = rsqrtf(ss / (float)n_cols + eps);
-    if (threadIdx.x == 0) R[row] = inv;
-    T* y = Y + row * ys;
-#pragma unroll
-    for (int i = 0; i < ITERS; ++i) {
-        const int c = (threadIdx.x + 256 * i) * VEC;
-        if (c < n_cols) {
-            Vec16<T> o;
-            float wf[VEC];
-            load_w<WT, VEC>(W + c, wf);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                const float normed = to_f32(xv[i].e[j]) * inv;
-                if (GEMMA) o.e[j] = from_f32<T>(normed * (wf[j] + 1.0f));
-                else o.e[j] = from_f32<T>(round_to<WT>(round_to<WT>(normed) * wf[j]));
-            }
-            st16_m(y + c, o, mode);
-        }
-    }
-}
-
-template <typename T, typename WT, int ITERS, bool GEMMA, bool ADD = false>
-__global__ void __launch_bounds__(256)
-rms_bwd_rb(const T* dY, T* dX, const T* __restrict__ X, const WT* __restrict__ W, const float* __restrict__ R,
-           int64_t n_rows, int n_cols, int64_t dys, int64_t dxs, int64_t xs, int mode, const T* dRes = nullptr,
-           int64_t drs = 0) {
-    constexpr int VEC = Vec16<T>::N;
-    __shared__ float red[4];
-    const int64_t row = blockIdx.x;
-    const T* dy = dY + row * dys;
-    const T* x = X + row * xs;
-    Vec16<T> dv[ITERS], xv[ITERS], rv[ADD ? ITERS : 1];
-#pragma unroll
-    for (int i = 0; i < ITERS; ++i) {
-        const int c = (threadIdx.x + 256 * i) * VEC;
+        const int c = (t + TPR * i) * VEC;
         if (c < n_cols) {
             dv[i] = ld16_m(dy + c, mode); xv[i] = ld16_m(x + c, mode);
-            if (ADD) rv[i] = ld16_m(dRes + row * drs + c, mode);
+            if (KEEP && ADD) rv[i] = ld16_m(dRes + row * drs + c, mode);
         } else { dv[i].raw = make_uint4(0, 0, 0, 0); xv[i].raw = make_uint4(0, 0, 0, 0); }
     }
     const float inv = R[row];
-    float wf[ITERS][VEC];
+    float wf[KEEP ? ITERS : 1][VEC];
     float rsum = 0.f;
 #pragma unroll
     for (int i = 0; i < ITERS; ++i) {
-        const int c = (threadIdx.x + 256 * i) * VEC;
+        const int c = (t + TPR * i) * VEC;
         if (c < n_cols) {
-            load_w<WT, VEC>(W + c, wf[i]);
+            float* w = wf[KEEP ? i : 0];
+            load_w<WT, VEC>(W + c, w);
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
-                if (GEMMA) wf[i][j] += 1.0f;
-                rsum += to_f32(dv[i].e[j]) * wf[i][j] * (to_f32(xv[i].e[j]) * inv);
+                if (GEMMA) w[j] += 1.0f;
+                rsum += to_f32(dv[i].e[j]) * w[j] * (to_f32(xv[i].e[j]) * inv);
             }
         }
     }
-    rsum = block_sum<4>(rsum, red);
+    rsum = row_sum<TPR>(rsum, red);
     const float n = (float)n_cols;
     T* dx = dX + row * dxs;
 #pragma unroll
     for (int i = 0; i < ITERS; ++i) {
-        const int c = (threadIdx.x + 256 * i) * VEC;
+        const int c = (t + TPR * i) * VEC;
         if (c < n_cols) {
             Vec16<T> o;
+            float* w = wf[KEEP ? i : 0];
+            if (!KEEP) load_w<WT, VEC>(W + c, w);
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
-                const float dyw = to_f32(dv[i].e[j]) * wf[i][j];
+                if (GEMMA && !KEEP) w[j] += 1.0f;
+                const float dyw = to_f32(dv[i].e[j]) * w[j];
                 const float normed = to_f32(xv[i].e[j]) * inv;
-                o.e[j] = from_f32<T>(inv / n * (n * dyw - normed * rsum));       // rms_layernorm.py:112
+                // rms_layernorm.py:112
+                o.e[j] = from_f32<T>(inv / n * (n * dyw - normed * rsum));
             }
             if (ADD) {
+                if (!KEEP) rv[0] = ld16_m(dRes + row * drs + c, mode);
 #pragma unroll
-                for (int j = 0; j < VEC; ++j) o.e[j] = from_f32<T>(to_f32(o.e[j]) + to_f32(rv[i].e[j]));
+                for (int j = 0; j < VEC; ++j) o.e[j] = from_f32<T>(to_f32(o.e[j]) + to_f32(rv[KEEP ? i : 0].e[j]));
             }
             st16_m(dx + c, o, mode);
         }
@@ -322,131 +209,81 @@ rms_bwd_block(const T* dY, T* dX, const T* __restrict__ X,
     }
 }
 
-template <typename T, typename WT, bool GEMMA>
-int launch_fwd(const void* X, const void* W, void* Y, float* R, int64_t n_rows, int n_cols,
-               int64_t xs, int64_t ys, float eps, hipStream_t st) {
+// which vector form a launch takes (the row-block form's grid is one block per row: n_rows has to fit it). A row of
+// `iters` vectors per lane of a wave is (iters + 3) / 4 per thread of a block.
+static inline bool rms_row_per_block(int64_t n_rows) {
+    return uamd_tuning_get(UAMD_TUNE_RMS_VAR) == 1 && n_rows <= 0x7fffffffLL;
+}
+
+// ADD: the fused residual add of uamd_add_rms_layernorm_fwd (Res, H and their row strides). It has no scalar form and no
+// Gemma form: UAMD_ERR_ALIGN for what the vector kernels do not take, and the caller runs the two separate ops.
+template <typename T, typename WT, bool GEMMA, bool ADD>
+int launch_fwd(const void* X, const void* W, void* Y, float* R, int64_t n_rows, int n_cols, int64_t xs, int64_t ys,
+               float eps, hipStream_t st, const void* Res, void* H, int64_t rs, int64_t hs) {
+    static_assert(!(ADD && GEMMA), "the fused add has no Gemma form");
     constexpr int VEC = Vec16<T>::N;
-    const bool vec_ok = (n_cols % VEC == 0) && (xs % VEC == 0) && (ys % VEC == 0) &&
-                        aligned16(X) && aligned16(Y) && aligned16(W) && n_cols <= 64 * VEC * 16;
+    const bool vec_ok = (n_cols % VEC == 0) && (xs % VEC == 0) && (ys % VEC == 0) && aligned16(X) && aligned16(Y) &&
+                        aligned16(W) && n_cols <= 64 * VEC * (ADD ? 8 : 16) &&
+                        (!ADD || ((rs % VEC == 0) && (hs % VEC == 0) && aligned16(Res) && aligned16(H)));
+    if (ADD && !vec_ok) return UAMD_ERR_ALIGN;
     const T* x = (const T*)X; const WT* w = (const WT*)W; T* y = (T*)Y;
-    if (vec_ok) {
-        const int iters = (n_cols + 64 * VEC - 1) / (64 * VEC);
-        dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
-        const int mode = uamd_tuning_get(UAMD_TUNE_STREAM_NT);
-        if (uamd_tuning_get(UAMD_TUNE_RMS_VAR) == 1 && iters <= 16 && n_rows <= 0x7fffffffLL) {
-            const int it = (iters + 3) / 4;
-            dim3 g1((unsigned)n_rows);
-#define LB(I) hipLaunchKernelGGL((rms_fwd_rb<T, WT, I, GEMMA>), g1, block, 0, st, x, w, y, R, n_rows, n_cols, xs, ys, eps, mode)
-            if (it <= 1) LB(1); else if (it <= 2) LB(2); else LB(4);
-#undef LB
-            return uamd_launch_status();
-        }
-#define L(I) hipLaunchKernelGGL((rms_fwd_wave<T, WT, I, GEMMA>), grid, block, 0, st, x, w, y, R, n_rows, n_cols, xs, ys, eps, mode)
-        if (iters <= 1) L(1); else if (iters <= 2) L(2); else if (iters <= 4) L(4);
-        else if (iters <= 8) L(8); else L(16);
-#undef L
-    } else {
+    if (!vec_ok) {
         hipLaunchKernelGGL((rms_fwd_block<T, WT, GEMMA>), dim3((unsigned)n_rows), dim3(256), 0, st,
                            x, w, y, R, n_cols, xs, ys, eps);
+        return uamd_launch_status();
+    }
+    const int iters = (n_cols + 64 * VEC - 1) / (64 * VEC);
+    const int mode = uamd_tuning_get(UAMD_TUNE_STREAM_NT);
+    auto launch = [&](auto tpr, auto it) {
+        constexpr int TPR = decltype(tpr)::value;
+        hipLaunchKernelGGL((rms_fwd_rows<T, WT, TPR, decltype(it)::value, GEMMA, ADD>),
+                           dim3((unsigned)(TPR == 64 ? (n_rows + 3) / 4 : n_rows)), dim3(256), 0, st, x, w, y, R, n_rows,
+                           n_cols, xs, ys, eps, mode, (const T*)Res, (T*)H, rs, hs);
+    };
+    auto block = [&](auto it) { launch(std::integral_constant<int, 256>{}, it); };
+    auto wave = [&](auto it) { launch(std::integral_constant<int, 64>{}, it); };
+    if (rms_row_per_block(n_rows)) {
+        if constexpr (ADD) uamd_with_iters<1, 2>((iters + 3) / 4, block);
+        else uamd_with_iters<1, 2, 4>((iters + 3) / 4, block);
+    } else {
+        if constexpr (ADD) uamd_with_iters<1, 2, 4, 8>(iters, wave);
+        else uamd_with_iters<1, 2, 4, 8, 16>(iters, wave);
     }
     return uamd_launch_status();
 }
 
-template <typename T, typename WT, bool GEMMA>
-int launch_bwd(const void* dY, void* dX, const void* X, const void* W, const float* R,
-               int64_t n_rows, int n_cols, int64_t dys, int64_t dxs, int64_t xs, hipStream_t st) {
+// ADD: the fused dRes of uamd_add_rms_layernorm_bwd, under the same rule as the forward's.
+template <typename T, typename WT, bool GEMMA, bool ADD>
+int launch_bwd(const void* dY, void* dX, const void* X, const void* W, const float* R, int64_t n_rows, int n_cols,
+               int64_t dys, int64_t dxs, int64_t xs, hipStream_t st, const void* dRes, int64_t drs) {
+    static_assert(!(ADD && GEMMA), "the fused add has no Gemma form");
     constexpr int VEC = Vec16<T>::N;
-    const bool vec_ok = (n_cols % VEC == 0) && (xs % VEC == 0) && (dys % VEC == 0) &&
-                        (dxs % VEC == 0) && aligned16(X) && aligned16(dY) && aligned16(dX) && aligned16(W) &&
-                        n_cols <= 64 * VEC * 8;
+    const bool vec_ok = (n_cols % VEC == 0) && (xs % VEC == 0) && (dys % VEC == 0) && (dxs % VEC == 0) && aligned16(X) &&
+                        aligned16(dY) && aligned16(dX) && aligned16(W) && n_cols <= 64 * VEC * 8 &&
+                        (!ADD || ((drs % VEC == 0) && aligned16(dRes)));
+    if (ADD && !vec_ok) return UAMD_ERR_ALIGN;
     const T* dy = (const T*)dY; T* dx = (T*)dX; const T* x = (const T*)X; const WT* w = (const WT*)W;
-    if (vec_ok) {
-        const int iters = (n_cols + 64 * VEC - 1) / (64 * VEC);
-        dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
-        const int mode = uamd_tuning_get(UAMD_TUNE_STREAM_NT);
-        if (uamd_tuning_get(UAMD_TUNE_RMS_VAR) == 1 && n_rows <= 0x7fffffffLL) {
-            const int it = (iters + 3) / 4;
-            dim3 g1((unsigned)n_rows);
-#define LB(I) hipLaunchKernelGGL((rms_bwd_rb<T, WT, I, GEMMA>), g1, block, 0, st, dy, dx, x, w, R, n_rows, n_cols, dys, dxs, xs, mode)
-            if (it <= 1) LB(1); else LB(2);
-#undef LB
-            return uamd_launch_status();
-        }
-#define L(I) hipLaunchKernelGGL((rms_bwd_wave<T, WT, I, GEMMA>), grid, block, 0, st, dy, dx, x, w, R, n_rows, n_cols, dys, dxs, xs, mode)
-        if (iters <= 1) L(1); else if (iters <= 2) L(2); else if (iters <= 4) L(4); else L(8);
-#undef L
-    } else {
+    if (!vec_ok) {
         hipLaunchKernelGGL((rms_bwd_block<T, WT, GEMMA>), dim3((unsigned)n_rows), dim3(256), 0, st,
                            dy, dx, x, w, R, n_cols, dys, dxs, xs);
-    }
-    return uamd_launch_status();
-}
-
-template <typename T, typename WT, bool GEMMA>
-int launch_add_fwd(const void* X, const void* Res, const void* W, void* H, void* Y, float* R, int64_t n_rows,
-                   int n_cols, int64_t xs, int64_t rs, int64_t hs, int64_t ys, float eps, hipStream_t st) {
-    constexpr int VEC = Vec16<T>::N;
-    const bool vec_ok = (n_cols % VEC == 0) && (xs % VEC == 0) && (ys % VEC == 0) && (rs % VEC == 0) &&
-                        (hs % VEC == 0) && aligned16(X) && aligned16(Y) && aligned16(W) && aligned16(Res) &&
-                        aligned16(H) && n_cols <= 64 * VEC * 8;
-    if (!vec_ok || GEMMA) return UAMD_ERR_ALIGN;
-    const int iters = (n_cols + 64 * VEC - 1) / (64 * VEC);
-    dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
-    const int mode = uamd_tuning_get(UAMD_TUNE_STREAM_NT);
-    if (uamd_tuning_get(UAMD_TUNE_RMS_VAR) == 1 && n_rows <= 0x7fffffffLL) {
-        const int it = (iters + 3) / 4;
-        dim3 g1((unsigned)n_rows);
-#define LB(I) hipLaunchKernelGGL((rms_fwd_rb<T, WT, I, false, true>), g1, block, 0, st, (const T*)X, (const WT*)W, (T*)Y, R, n_rows, n_cols, xs, ys, eps, mode, (const T*)Res, (T*)H, rs, hs)
-        if (it <= 1) LB(1); else LB(2);
-#undef LB
         return uamd_launch_status();
     }
-#define L(I) hipLaunchKernelGGL((rms_fwd_wave<T, WT, I, false, true>), grid, block, 0, st, (const T*)X, (const WT*)W, (T*)Y, R, n_rows, n_cols, xs, ys, eps, mode, (const T*)Res, (T*)H, rs, hs)
-    if (iters <= 1) L(1); else if (iters <= 2) L(2); else if (iters <= 4) L(4); else L(8);
-#undef L
-    return uamd_launch_status();
-}
-
-template <typename T, typename WT, bool GEMMA>
-int launch_add_bwd(const void* dY, const void* dRes, void* dX, const void* X, const void* W, const float* R,
-                   int64_t n_rows, int n_cols, int64_t dys, int64_t drs, int64_t dxs, int64_t xs, hipStream_t st) {
-    constexpr int VEC = Vec16<T>::N;
-    const bool vec_ok = (n_cols % VEC == 0) && (xs % VEC == 0) && (dys % VEC == 0) && (dxs % VEC == 0) &&
-                        (drs % VEC == 0) && aligned16(X) && aligned16(dY) && aligned16(dX) && aligned16(W) &&
-                        aligned16(dRes) && n_cols <= 64 * VEC * 8;
-    if (!vec_ok || GEMMA) return UAMD_ERR_ALIGN;
     const int iters = (n_cols + 64 * VEC - 1) / (64 * VEC);
-    dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
     const int mode = uamd_tuning_get(UAMD_TUNE_STREAM_NT);
-    if (uamd_tuning_get(UAMD_TUNE_RMS_VAR) == 1 && n_rows <= 0x7fffffffLL) {
-        const int it = (iters + 3) / 4;
-        dim3 g1((unsigned)n_rows);
-#define LB(I) hipLaunchKernelGGL((rms_bwd_rb<T, WT, I, false, true>), g1, block, 0, st, (const T*)dY, (T*)dX, (const T*)X, (const WT*)W, R, n_rows, n_cols, dys, dxs, xs, mode, (const T*)dRes, drs)
-        if (it <= 1) LB(1); else LB(2);
-#undef LB
-        return uamd_launch_status();
-    }
-#define L(I) hipLaunchKernelGGL((rms_bwd_wave<T, WT, I, false, true>), grid, block, 0, st, (const T*)dY, (T*)dX, (const T*)X, (const WT*)W, R, n_rows, n_cols, dys, dxs, xs, mode, (const T*)dRes, drs)
-    if (iters <= 1) L(1); else if (iters <= 2) L(2); else if (iters <= 4) L(4); else L(8);
-#undef L
+    auto launch = [&](auto tpr, auto it) {
+        constexpr int TPR = decltype(tpr)::value;
+        hipLaunchKernelGGL((rms_bwd_rows<T, WT, TPR, decltype(it)::value, GEMMA, ADD>),
+                           dim3((unsigned)(TPR == 64 ? (n_rows + 3) / 4 : n_rows)), dim3(256), 0, st, dy, dx, x, w, R,
+                           n_rows, n_cols, dys, dxs, xs, mode, (const T*)dRes, drs);
+    };
+    if (rms_row_per_block(n_rows))
+        uamd_with_iters<1, 2>((iters + 3) / 4, [&](auto it) { launch(std::integral_constant<int, 256>{}, it); });
+    else
+        uamd_with_iters<1, 2, 4, 8>(iters, [&](auto it) { launch(std::integral_constant<int, 64>{}, it); });
     return uamd_launch_status();
 }
 
 }  // namespace
-
-#define RMS_DISPATCH(FN, ...)                                                        \
-    if (x_dtype == UAMD_BF16 && w_dtype == UAMD_BF16) {                               \
-        return gemma ? FN<bf16_t, bf16_t, true>(__VA_ARGS__) : FN<bf16_t, bf16_t, false>(__VA_ARGS__); \
-    } else if (x_dtype == UAMD_BF16 && w_dtype == UAMD_F32) {                         \
-        return gemma ? FN<bf16_t, float, true>(__VA_ARGS__) : FN<bf16_t, float, false>(__VA_ARGS__);   \
-    } else if (x_dtype == UAMD_F16 && w_dtype == UAMD_F16) {                          \
-        return gemma ? FN<f16_t, f16_t, true>(__VA_ARGS__) : FN<f16_t, f16_t, false>(__VA_ARGS__);     \
-    } else if (x_dtype == UAMD_F16 && w_dtype == UAMD_F32) {                          \
-        return gemma ? FN<f16_t, float, true>(__VA_ARGS__) : FN<f16_t, float, false>(__VA_ARGS__);     \
-    } else if (x_dtype == UAMD_F32 && w_dtype == UAMD_F32) {                          \
-        return gemma ? FN<float, float, true>(__VA_ARGS__) : FN<float, float, false>(__VA_ARGS__);     \
-    }                                                                                \
-    return UAMD_ERR_DTYPE;
 
 // ---- weight gradient (full fine-tuning: the norm weights train; the reference's kernel returns no dW,
 //      rms_layernorm.py:218-240, and leaves trainable norms to HF's torch RMSNorm + autograd):
@@ -534,16 +371,8 @@ extern "C" int uamd_rms_layernorm_dw(const void* dY, const void* X, const float*
         if (!accumulate) return (int)hipMemsetAsync(dW, 0, (size_t)n_cols * (w_dtype == UAMD_F32 ? 4 : 2), st);
         return UAMD_OK;
     }
-#define DW_CASE(XT, XC, WT, WC) \
-    if (x_dtype == XC && w_dtype == WC) \
-        return launch_dw<XT, WT>(dY, X, r, dW, workspace, ws_elems, n_rows, n_cols, dy_row_stride, x_row_stride, accumulate, st);
-    DW_CASE(bf16_t, UAMD_BF16, bf16_t, UAMD_BF16)
-    DW_CASE(bf16_t, UAMD_BF16, float, UAMD_F32)
-    DW_CASE(f16_t, UAMD_F16, f16_t, UAMD_F16)
-    DW_CASE(f16_t, UAMD_F16, float, UAMD_F32)
-    DW_CASE(float, UAMD_F32, float, UAMD_F32)
-#undef DW_CASE
-    return UAMD_ERR_DTYPE;
+    UAMD_DISPATCH_NORM(x_dtype, w_dtype, return launch_dw<T, WT>(dY, X, r, dW, workspace, ws_elems, n_rows, n_cols,
+                                                                 dy_row_stride, x_row_stride, accumulate, st))
 }
 
 extern "C" int uamd_rms_layernorm_fwd(const void* X, const void* W, void* Y, float* r,
@@ -553,7 +382,8 @@ extern "C" int uamd_rms_layernorm_fwd(const void* X, const void* W, void* Y, flo
     if (n_rows < 0 || n_cols <= 0) return UAMD_ERR_ARG;
     if (n_rows == 0) return UAMD_OK;
     hipStream_t st = (hipStream_t)stream;
-    RMS_DISPATCH(launch_fwd, X, W, Y, r, n_rows, n_cols, x_row_stride, y_row_stride, eps, st)
+    UAMD_DISPATCH_NORM(x_dtype, w_dtype, auto f = gemma ? launch_fwd<T, WT, true, false> : launch_fwd<T, WT, false, false>;
+                       return f(X, W, Y, r, n_rows, n_cols, x_row_stride, y_row_stride, eps, st, nullptr, nullptr, 0, 0))
 }
 
 extern "C" int uamd_rms_layernorm_bwd(const void* dY, void* dX, const void* X, const void* W,
@@ -564,8 +394,8 @@ extern "C" int uamd_rms_layernorm_bwd(const void* dY, void* dX, const void* X, c
     if (n_rows < 0 || n_cols <= 0) return UAMD_ERR_ARG;
     if (n_rows == 0) return UAMD_OK;
     hipStream_t st = (hipStream_t)stream;
-    RMS_DISPATCH(launch_bwd, dY, dX, X, W, r, n_rows, n_cols, dy_row_stride, dx_row_stride,
-                 x_row_stride, st)
+    UAMD_DISPATCH_NORM(x_dtype, w_dtype, auto f = gemma ? launch_bwd<T, WT, true, false> : launch_bwd<T, WT, false, false>;
+                       return f(dY, dX, X, W, r, n_rows, n_cols, dy_row_stride, dx_row_stride, x_row_stride, st, nullptr, 0))
 }
 
 // h = X + Res (written to H), Y = rmsnorm(h) * W, r = rsqrt(mean h^2 + eps): residual add + norm in ONE pass
@@ -578,9 +408,8 @@ extern "C" int uamd_add_rms_layernorm_fwd(const void* X, const void* Res, const 
     if (n_rows < 0 || n_cols <= 0 || !X || !Res || !H || !Y || !W || !r) return UAMD_ERR_ARG;
     if (n_rows == 0) return UAMD_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int gemma = 0;
-    RMS_DISPATCH(launch_add_fwd, X, Res, W, H, Y, r, n_rows, n_cols, x_row_stride, res_row_stride, h_row_stride,
-                 y_row_stride, eps, st)
+    UAMD_DISPATCH_NORM(x_dtype, w_dtype, return launch_fwd<T, WT, false, true>(
+        X, W, Y, r, n_rows, n_cols, x_row_stride, y_row_stride, eps, st, Res, H, res_row_stride, h_row_stride))
 }
 
 // dX = rmsnorm_backward(dY; h, W, r) + dRes, dRes = the gradient arriving at h from the residual path. dX may
@@ -592,7 +421,6 @@ extern "C" int uamd_add_rms_layernorm_bwd(const void* dY, const void* dRes, void
     if (n_rows < 0 || n_cols <= 0 || !dY || !dRes || !dX || !H || !W || !r) return UAMD_ERR_ARG;
     if (n_rows == 0) return UAMD_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int gemma = 0;
-    RMS_DISPATCH(launch_add_bwd, dY, dRes, dX, H, W, r, n_rows, n_cols, dy_row_stride, dres_row_stride,
-                 dx_row_stride, h_row_stride, st)
+    UAMD_DISPATCH_NORM(x_dtype, w_dtype, return launch_bwd<T, WT, false, true>(
+        dY, dX, H, W, r, n_rows, n_cols, dy_row_stride, dx_row_stride, h_row_stride, st, dRes, dres_row_stride))
 }

@@ -27,6 +27,11 @@ def _vec_layout(*tensors):
     return True
 
 
+def _add_width_ok(X):
+    """The fused add + norm kernels keep a row of up to 64 x 8 16-byte vectors (they have no scalar form)."""
+    return X.shape[-1] <= 64 * (16 // X.element_size()) * 8
+
+
 def rms_fwd(X, W, eps, gemma=False):
     """(Y, r) for X [..., dim]; Y [rows, dim]."""
     _lib.require_gpu(X, W)
@@ -96,7 +101,7 @@ def rms_bwd_(dY, H, W, r, dH=None, gemma=False):
     dY2, H2 = _rows(dY), _rows(H)
     n_rows, dim = dY2.shape
     dX = torch.empty_like(dY2) if gemma else dY2
-    if dH is not None and not (dim <= 64 * (16 // dY2.element_size()) * 8 and _vec_layout(dY2, H2, W, _rows(dH))):
+    if dH is not None and not (_add_width_ok(dY2) and _vec_layout(dY2, H2, W, _rows(dH))):
         # the fused kernel has no scalar form: the norm's backward (which has one), then the add, with the same two roundings
         assert not gemma
         return rms_bwd_(dY2, H2, W, r).add_(_rows(dH))
@@ -160,7 +165,7 @@ def add_rms_supported(X, W, residual=None):
     """shapes and layouts the fused kernel takes (otherwise: torch add + fast_rms_layernorm)."""
     vec = 16 // X.element_size()
     return (X.is_cuda and X.dtype in (torch.bfloat16, torch.float16, torch.float32) and X.shape[-1] % vec == 0
-            and X.shape[-1] <= 64 * vec * 8 and W.dtype in (X.dtype, torch.float32)
+            and _add_width_ok(X) and W.dtype in (X.dtype, torch.float32)
             and _vec_layout(X, W, *(() if residual is None else (residual,))))
 
 
