@@ -230,6 +230,41 @@ def test_attn_decode_fused_with_other_split_sizes(split_keys, lens):
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("D,S,B,Hq,Hk,lens", [(128, 512, 1, 8, 2, (100,)), (128, 512, 2, 16, 8, (100, 37)), (64, 512, 1, 8, 2, (100,)),
+                                              (64, 512, 3, 28, 4, (100, 37, 33)), (64, 1024, 2, 16, 8, (100, 37))])
+def test_attn_decode_fused_is_bit_equal_at_one_block_load_per_split(dtype, D, S, B, Hq, Hk, lens):
+    """With split_keys = one block-load of keys (DecGeo<D>::KPB = 2048 / D: 16 at D = 128, 32 at D = 64) every lane group sees at
+    most one valid key per split, so the single launch's 128-key trip and the three launches' one-key trip do the same
+    operations (the other keys of the trip add exp2(-inf) = 0 times a finite row): out and both caches are EQUAL, no tolerance,
+    over three consecutive tokens. Rotation, merge and combine are the same device functions in both; this pins the rest. The
+    grids: 64, 32 and 192 workgroups (granule combine on a 256-CU device) and 512 (arrival counter) at either head dim."""
+    from unsloth_amd.kernels import decode as Dk
+    split_keys = 2048 // D
+    inv = 1.0 / (10000 ** (torch.arange(0, D, 2).float() / D))
+    ang = torch.arange(S).float()[:, None] * inv[None, :]
+    cos = torch.cat([ang.cos(), ang.cos()], dim=1).to(dtype).to(DEV)
+    sin = torch.cat([ang.sin(), ang.sin()], dim=1).to(dtype).to(DEV)
+    kc1 = torch.randn(B, Hk, S, D, generator=g(9)).to(dtype).to(DEV)
+    vc1 = torch.randn(B, Hk, S, D, generator=g(10)).to(dtype).to(DEV)
+    kc2, vc2 = kc1.clone(), vc1.clone()
+    kv_len = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    part1 = torch.empty(B, Hq, S // split_keys, D + 2, dtype=torch.float32, device=DEV)
+    part2, cnt = Dk.fused_attn_workspace(B, Hq, Hk, S, D, split_keys, DEV)
+    scale = 1.0 / math.sqrt(D)
+    for step in range(3):
+        raw = torch.randn(B, (Hq + 2 * Hk) * D, generator=g(20 + step)).to(dtype).to(DEV)
+        q1 = raw.clone()
+        out1 = torch.empty(B, Hq * D, dtype=dtype, device=DEV)
+        Dk.rope_kv_append(q1, cos, sin, kv_len, kc1, vc1, Hq, Hk, D)
+        Dk.attn_decode(q1[:, :Hq * D], kc1, vc1, kv_len, out1, part1, split_keys, scale, len_add=1)
+        out2 = torch.full((B, Hq * D), float("nan"), dtype=dtype, device=DEV)
+        Dk.attn_decode_fused(raw, cos, sin, kv_len, kc2, vc2, out2, part2, cnt, split_keys, scale, Hq)
+        assert torch.equal(out2, out1), (step, (out2.float() - out1.float()).abs().max().item())
+        assert torch.equal(kc2, kc1) and torch.equal(vc2, vc1)
+        kv_len += 1
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("nf4", [True, False])
 def test_gemv_fused_glu_epilogue_and_the_in_launch_lora_hand_off(dtype, nf4):
     """uamd_gemv_fused with glu: gate | up in, h = SwiGLU out -- bit-identical to the gate|up launch + uamd_swiglu_fg when there

@@ -721,6 +721,14 @@ int launch_gemv(const GemvArgs& a, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------------------------
 // RoPE (rotate-half, the training kernel's arithmetic and rounding points) on the new token's q and k, and the
 // append of k, v to the cache at position kv_len[b]. qkv: [B, (Hq + 2 Hk) D] as the fused q|k|v GEMV wrote it.
+//
+// One rotated pair. Rounding points of the training kernel for 16-bit tables (csrc/rope_embedding.hip rotate<T, NATIVE>, i.e.
+// the reference's Triton arithmetic in the cos / sin dtype): every product and the sum are rounded to T.
+template <typename T>
+__device__ __forceinline__ void rope_pair(float x1, float x2, float c, float s, T& r1, T& r2) {
+    r1 = from_f32<T>(round_to<T>(x1 * c) - round_to<T>(x2 * s));
+    r2 = from_f32<T>(round_to<T>(x2 * c) + round_to<T>(x1 * s));
+}
 template <typename T>
 __global__ void __launch_bounds__(64) rope_append_kernel(T* __restrict__ qkv, int64_t ld_qkv, const T* __restrict__ cos_t,
                                                          const T* __restrict__ sin_t, int64_t ld_cs,
@@ -736,11 +744,8 @@ __global__ void __launch_bounds__(64) rope_append_kernel(T* __restrict__ qkv, in
         T* kd = (h >= Hq && len < s_max) ? kc + (int64_t)b * c_sb + (int64_t)(h - Hq) * c_sh + (int64_t)len * D : nullptr;
         for (int j = threadIdx.x; j < half; j += 64) {
             const float c = to_f32(cos_t[(int64_t)pos * ld_cs + j]), s = to_f32(sin_t[(int64_t)pos * ld_cs + j]);
-            const float x1 = to_f32(v[j]), x2 = to_f32(v[j + half]);
-            // rounding points of the training kernel for 16-bit tables (csrc/rope_embedding.hip rotate<T, NATIVE>, i.e. the
-            // reference's Triton arithmetic in the cos / sin dtype): every product and the sum are rounded to T
-            const T r1 = from_f32<T>(round_to<T>(x1 * c) - round_to<T>(x2 * s));
-            const T r2 = from_f32<T>(round_to<T>(x2 * c) + round_to<T>(x1 * s));
+            T r1, r2;
+            rope_pair(to_f32(v[j]), to_f32(v[j + half]), c, s, r1, r2);
             v[j] = r1;
             v[j + half] = r2;
             if (kd) { kd[j] = r1; kd[j + half] = r2; }
@@ -762,6 +767,91 @@ template <int DD> struct DecGeo {
     static constexpr int KPW = 64 / LPK;        // keys per wave-load
     static constexpr int KPB = 4 * KPW;         // keys per block-load: the loop stride and the alignment of a split's start
 };
+
+// Shared by the three launches (attn_decode_kernel -> attn_decode_combine_kernel) and the single one
+// (attn_decode_fused_kernel):
+
+// offset of the partial of (bh = b * Hq + query head, split)
+template <int DD>
+__device__ __forceinline__ int64_t part_index(int64_t bh, int nsplit, int split) { return (bh * nsplit + split) * (DD + 2); }
+
+// THE online-softmax merge: (m, l) takes in a second partial (mo, lo), both in the exp2 domain; the caller scales its own
+// values by a and the other partial's by c. mr: with nothing but masked keys on both sides (max -inf) the factors are
+// exp2(-inf - 0) = 0 instead of exp2(-inf + inf) = NaN.
+__device__ __forceinline__ void softmax_merge(float& m, float& l, float mo, float lo, float& a, float& c) {
+    const float mn = fmaxf(m, mo);
+    const float mr = mn == -INFINITY ? 0.f : mn;
+    a = __builtin_amdgcn_exp2f(m - mr);
+    c = __builtin_amdgcn_exp2f(mo - mr);
+    l = l * a + lo * c;
+    m = mn;
+}
+
+// The key slots of a wave merged by shuffles (lanes with the same column slice), then the wave's (m, l, o) into LDS.
+template <int G, int DD>
+__device__ __forceinline__ void waves_to_lds(float (&m)[G], float (&l)[G], float (&o)[G][8], float (&red)[4][G][2],
+                                             float (&red_o)[4][G][DD], int lane, int wave) {
+    constexpr int LPK = DecGeo<DD>::LPK;
+    const int lc = lane % LPK;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int off = LPK; off <= 32; off <<= 1) {
+            const float mo = __shfl_xor(m[g], off, 64), lo = __shfl_xor(l[g], off, 64);
+            float a, c;
+            softmax_merge(m[g], l[g], mo, lo, a, c);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[g][j] = o[g][j] * a + __shfl_xor(o[g][j], off, 64) * c;
+        }
+        if (lane < LPK) {
+            if (lc == 0) { red[wave][g][0] = m[g]; red[wave][g][1] = l[g]; }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) red_o[wave][g][lc * 8 + j] = o[g][j];
+        }
+    }
+}
+
+// ... and, after the barrier, the block's partial (mm, ll, oo) of head g, column d over its 4 waves.
+template <int G, int DD>
+__device__ __forceinline__ void block_partial(const float (&red)[4][G][2], const float (&red_o)[4][G][DD], int g, int d,
+                                              float& mm, float& ll, float& oo) {
+    mm = -INFINITY;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) mm = fmaxf(mm, red[s][g][0]);
+    const float mr = mm == -INFINITY ? 0.f : mm;
+    ll = 0.f; oo = 0.f;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const float a = __builtin_amdgcn_exp2f(red[s][g][0] - mr);
+        ll += red[s][g][1] * a;
+        oo += red_o[s][g][d] * a;
+    }
+}
+
+// Column d of a head's output from its plain partials pp[nsplit][DD + 2]: running (max, sum, value) over the splits in a fixed
+// order; 4 splits' loads in flight at a time.
+template <int DD>
+__device__ __forceinline__ float combine_splits(const float* pp, int nsplit, int d) {
+    float mm = -INFINITY, ll = 0.f, oo = 0.f;
+    for (int s0 = 0; s0 < nsplit; s0 += 4) {
+        float ms[4], ls[4], os[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int s = min(s0 + j, nsplit - 1);
+            ms[j] = s0 + j < nsplit ? pp[s * (DD + 2) + DD] : -INFINITY;
+            ls[j] = pp[s * (DD + 2) + DD + 1];
+            os[j] = pp[s * (DD + 2) + d];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float a, c;
+            softmax_merge(mm, ll, ms[j], ls[j], a, c);
+            oo = oo * a + os[j] * c;
+        }
+    }
+    return ll > 0.f ? oo / ll : 0.f;
+}
+
 template <typename T, int G, int DD>
 __global__ void __launch_bounds__(256) attn_decode_kernel(const T* __restrict__ q, int64_t q_sb, const T* __restrict__ kc,
                                                           const T* __restrict__ vc, int64_t c_sb, int64_t c_sh,
@@ -806,51 +896,19 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const T* __restrict__ 
         }
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            const float mn = fmaxf(m[g], s[g]);
-            const float mr = mn == -INFINITY ? 0.f : mn;
-            const float alpha = __builtin_amdgcn_exp2f(m[g] - mr);
-            const float pe = __builtin_amdgcn_exp2f(s[g] - mr);
-            m[g] = mn;
-            l[g] = l[g] * alpha + pe;
+            float alpha, pe;
+            softmax_merge(m[g], l[g], s[g], 1.f, alpha, pe);      // the key as a partial of its own: (s, 1)
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[g][j] = o[g][j] * alpha + pe * to_f32(vv.e[j]);
         }
     }
-    // combine: the key slots of a wave by shuffles (lanes with the same column slice), then the 4 waves through LDS
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-#pragma unroll
-        for (int off = LPK; off <= 32; off <<= 1) {
-            const float mo = __shfl_xor(m[g], off, 64), lo = __shfl_xor(l[g], off, 64);
-            const float mn = fmaxf(m[g], mo);
-            const float mr = mn == -INFINITY ? 0.f : mn;
-            const float a = __builtin_amdgcn_exp2f(m[g] - mr), c = __builtin_amdgcn_exp2f(mo - mr);
-            l[g] = l[g] * a + lo * c;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[g][j] = o[g][j] * a + __shfl_xor(o[g][j], off, 64) * c;
-            m[g] = mn;
-        }
-        if (lane < LPK) {
-            if (lc == 0) { red[wave][g][0] = m[g]; red[wave][g][1] = l[g]; }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) red_o[wave][g][lc * 8 + j] = o[g][j];
-        }
-    }
+    waves_to_lds<G, DD>(m, l, o, red, red_o, lane, wave);
     __syncthreads();
     for (int i = tid; i < G * DD; i += 256) {
         const int g = i / DD, d = i - g * DD;
-        float mm = -INFINITY;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) mm = fmaxf(mm, red[s][g][0]);
-        const float mr = mm == -INFINITY ? 0.f : mm;
-        float ll = 0.f, oo = 0.f;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const float a = __builtin_amdgcn_exp2f(red[s][g][0] - mr);
-            ll += red[s][g][1] * a;
-            oo += red_o[s][g][d] * a;
-        }
-        float* pp = part + (((int64_t)b * Hq + kvh * G + g) * nsplit + split) * (DD + 2);
+        float mm, ll, oo;
+        block_partial<G, DD>(red, red_o, g, d, mm, ll, oo);
+        float* pp = part + part_index<DD>((int64_t)b * Hq + kvh * G + g, nsplit, split);
         pp[d] = oo;
         if (d == 0) { pp[DD] = mm; pp[DD + 1] = ll; }
     }
@@ -860,43 +918,26 @@ template <typename T, int DD>
 __global__ void __launch_bounds__(DD) attn_decode_combine_kernel(const float* __restrict__ part, T* __restrict__ out,
                                                                   int64_t o_sb, int Hq, int nsplit) {
     const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;
-    const float* pp = part + ((int64_t)b * Hq + h) * nsplit * (DD + 2);
-    // running (max, sum, value) over the splits in a fixed order; 4 splits' loads in flight at a time
-    float mm = -INFINITY, ll = 0.f, oo = 0.f;
-    for (int s0 = 0; s0 < nsplit; s0 += 4) {
-        float ms[4], ls[4], os[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int s = min(s0 + j, nsplit - 1);
-            ms[j] = s0 + j < nsplit ? pp[s * (DD + 2) + DD] : -INFINITY;
-            ls[j] = pp[s * (DD + 2) + DD + 1];
-            os[j] = pp[s * (DD + 2) + d];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float mn = fmaxf(mm, ms[j]);
-            const float mr = mn == -INFINITY ? 0.f : mn;
-            const float a = __builtin_amdgcn_exp2f(mm - mr), c = __builtin_amdgcn_exp2f(ms[j] - mr);
-            ll = ll * a + ls[j] * c;
-            oo = oo * a + os[j] * c;
-            mm = mn;
-        }
-    }
-    out[(int64_t)b * o_sb + (int64_t)h * DD + d] = from_f32<T>(ll > 0.f ? oo / ll : 0.f);
+    const float* pp = part + part_index<DD>((int64_t)b * Hq + h, nsplit, 0);
+    out[(int64_t)b * o_sb + (int64_t)h * DD + d] = from_f32<T>(combine_splits<DD>(pp, nsplit, d));
 }
 
-
 // ---------------------------------------------------------------------------------------------------------------
-// RoPE + cache append + split-KV attention + combine as ONE launch (uamd_attn_decode_fused). Same RoPE arithmetic, key
-// partition and combine order as rope_append_kernel -> attn_decode_kernel -> attn_decode_combine_kernel; the keys of a
-// split are accumulated chunk-wise (one running-max rescale per NI keys of a lane group instead of one per key), so the
-// result equals the three launches' to fp32 rounding, not bit for bit. What changes:
+// RoPE + cache append + split-KV attention + combine as ONE launch (uamd_attn_decode_fused). The rotation (rope_pair), the
+// merge of a block's partials (softmax_merge, waves_to_lds, block_partial), the partial layout (part_index) and the combine
+// (combine_splits) are the functions rope_append_kernel -> attn_decode_kernel -> attn_decode_combine_kernel call, and the key
+// partition is the same. What differs:
+//   * the keys of a split are accumulated chunk-wise (one running-max rescale per NI keys of a lane group instead of one per
+//     key), so the result equals the three launches' to fp32 rounding, and bit for bit where a split holds one block-load of
+//     keys. The trip stays written out here: as a shared function the compiler schedules its G = 7, D = 128 instance, at the
+//     register limit, measurably slower;
 //   * every block rotates the G query heads of its KV head itself from the raw q|k|v row (G x D/2 pairs; qkv is not written);
 //   * the block whose split owns position len0 = kv_len[b] rotates the new k, appends k and v to the cache and takes both
 //     from LDS when its loop reaches that key (a store followed by a load of the same line in one kernel would depend on the
 //     vector cache's write policy);
 //   * all K / V loads of a 128-key trip (NI wave-loads of each: 8 at D = 128, 4 at D = 64, where a wave-load covers twice the
-//     keys) are issued before the first one is used: the old loop paid one HBM round trip per block-load, eight in a row;
+//     keys) are issued before the first one is used: a loop of one block-load per trip pays one HBM round trip each, eight in
+//     a row;
 //   * the combine. Launches of up to 256 blocks (context 4096 at 8 KV heads): partials travel as 8-byte {value, tag}
 //     granules (one device-scope store each, never torn, no fence; the caller's launch tag as in gemv_kernel) and every block
 //     combines ITS 1 / nsplit of the G x D outputs, polling the granules of all splits in split order. Larger launches
@@ -945,23 +986,22 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
     const T* sn = (const T*)a.sin_t + (int64_t)pos * a.ld_cs;
     constexpr int HALF = DD / 2;
     static_assert(HALF <= 64 && 64 + DD <= 256, "wave 0 rotates the new k, the lanes from wave 1 on copy the new v");
-    // rounding points of rope_append_kernel (= the training kernel for 16-bit tables): every product and the sum rounded to T
     for (int i = tid; i < G * HALF; i += 256) {
         const int g = i / HALF, j = i - g * HALF;
         const T* v = row + (int64_t)(kvh * G + g) * DD;
         const float c = to_f32(cs[j]), s = to_f32(sn[j]);
-        const float x1 = to_f32(v[j]), x2 = to_f32(v[j + HALF]);
-        q_s[g][j] = round_to<T>(round_to<T>(x1 * c) - round_to<T>(x2 * s)) * a.scale_log2;
-        q_s[g][j + HALF] = round_to<T>(round_to<T>(x2 * c) + round_to<T>(x1 * s)) * a.scale_log2;
+        T r1, r2;
+        rope_pair(to_f32(v[j]), to_f32(v[j + HALF]), c, s, r1, r2);
+        q_s[g][j] = to_f32(r1) * a.scale_log2;
+        q_s[g][j + HALF] = to_f32(r2) * a.scale_log2;
     }
     if (own) {
         if (tid < HALF) {
             const int j = tid;
             const T* v = row + (int64_t)(a.Hq + kvh) * DD;
             const float c = to_f32(cs[j]), s = to_f32(sn[j]);
-            const float x1 = to_f32(v[j]), x2 = to_f32(v[j + HALF]);
-            const T r1 = from_f32<T>(round_to<T>(x1 * c) - round_to<T>(x2 * s));
-            const T r2 = from_f32<T>(round_to<T>(x2 * c) + round_to<T>(x1 * s));
+            T r1, r2;
+            rope_pair(to_f32(v[j]), to_f32(v[j + HALF]), c, s, r1, r2);
             kn[j] = r1;
             kn[j + HALF] = r2;
             if (len0 < a.s_max) {
@@ -1050,42 +1090,15 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
         }
     }
     DSTAMP(5);
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-#pragma unroll
-        for (int off = LPK; off <= 32; off <<= 1) {
-            const float mo = __shfl_xor(m[g], off, 64), lo = __shfl_xor(l[g], off, 64);
-            const float mn = fmaxf(m[g], mo);
-            const float mr = mn == -INFINITY ? 0.f : mn;
-            const float aa = __builtin_amdgcn_exp2f(m[g] - mr), c = __builtin_amdgcn_exp2f(mo - mr);
-            l[g] = l[g] * aa + lo * c;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[g][j] = o[g][j] * aa + __shfl_xor(o[g][j], off, 64) * c;
-            m[g] = mn;
-        }
-        if (lane < LPK) {
-            if (lc == 0) { red[wave][g][0] = m[g]; red[wave][g][1] = l[g]; }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) red_o[wave][g][lc * 8 + j] = o[g][j];
-        }
-    }
+    waves_to_lds<G, DD>(m, l, o, red, red_o, lane, wave);
     __syncthreads();
     for (int i = tid; i < G * DD; i += 256) {
         const int g = i / DD, d = i - g * DD;
-        float mm = -INFINITY;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) mm = fmaxf(mm, red[s][g][0]);
-        const float mr = mm == -INFINITY ? 0.f : mm;
-        float ll = 0.f, oo = 0.f;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const float aa = __builtin_amdgcn_exp2f(red[s][g][0] - mr);
-            ll += red[s][g][1] * aa;
-            oo += red_o[s][g][d] * aa;
-        }
+        float mm, ll, oo;
+        block_partial<G, DD>(red, red_o, g, d, mm, ll, oo);
+        const int64_t at = part_index<DD>((int64_t)b * a.Hq + kvh * G + g, a.nsplit, split);
         if (a.gran) {       // {value, tag} granules: one 8-byte device-scope store each, no fence
-            unsigned long long* pg = reinterpret_cast<unsigned long long*>(a.part) +
-                                     (((int64_t)b * a.Hq + kvh * G + g) * a.nsplit + split) * (DD + 2);
+            unsigned long long* pg = reinterpret_cast<unsigned long long*>(a.part) + at;
             const unsigned long long hi = (unsigned long long)tag << 32;
             __hip_atomic_store(pg + d, hi | __float_as_uint(oo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (d == 0) {
@@ -1093,14 +1106,14 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
                 __hip_atomic_store(pg + DD + 1, hi | __float_as_uint(ll), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         } else {
-            float* pp = a.part + (((int64_t)b * a.Hq + kvh * G + g) * a.nsplit + split) * (DD + 2);
+            float* pp = a.part + at;
             pp[d] = oo;
             if (d == 0) { pp[DD] = mm; pp[DD + 1] = ll; }
         }
     }
     if (a.gran) {
         // ---- every block of the (batch, KV head) combines ITS share of the G x D outputs from the granules of all splits, in
-        //      split order (the old combine kernel's arithmetic). All blocks of the launch are resident (the host checks), and
+        //      split order (combine_splits' arithmetic). All blocks of the launch are resident (the host checks), and
         //      each has published before it polls: nobody waits for a block that has not started. Polls are bounded.
         DSTAMP(6);
         const int chunk = (G * DD + a.nsplit - 1) / a.nsplit;
@@ -1108,7 +1121,7 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
         for (int i = split * chunk + tid; i < i_end; i += 256) {
             const int g = i / DD, d = i - g * DD;
             const unsigned long long* pg = reinterpret_cast<const unsigned long long*>(a.part) +
-                                           ((int64_t)b * a.Hq + kvh * G + g) * a.nsplit * (DD + 2);
+                                           part_index<DD>((int64_t)b * a.Hq + kvh * G + g, a.nsplit, 0);
             float mm = -INFINITY, ll = 0.f, oo = 0.f;
             for (int sb = 0; sb < a.nsplit; sb += 8) {
                 unsigned long long gm[8], gl[8], go[8];
@@ -1132,12 +1145,9 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
                     if (sb + j >= a.nsplit) break;
                     const float msj = (unsigned)(gm[j] >> 32) == tag ? __uint_as_float((unsigned)gm[j]) : __builtin_nanf("");
                     const float lsj = __uint_as_float((unsigned)gl[j]), osj = __uint_as_float((unsigned)go[j]);
-                    const float mn = fmaxf(mm, msj);
-                    const float mr = mn == -INFINITY ? 0.f : mn;
-                    const float aa = __builtin_amdgcn_exp2f(mm - mr), c = __builtin_amdgcn_exp2f(msj - mr);
-                    ll = ll * aa + lsj * c;
+                    float aa, c;
+                    softmax_merge(mm, ll, msj, lsj, aa, c);
                     oo = oo * aa + osj * c;
-                    mm = mn;
                 }
             }
             ((T*)a.out)[(int64_t)b * a.o_sb + (int64_t)(kvh * G + g) * DD + d] = from_f32<T>(ll > 0.f ? oo / ll : 0.f);
@@ -1167,28 +1177,8 @@ __global__ void __launch_bounds__(256) attn_decode_fused_kernel(AttnDecFusedArgs
     DSTAMP(9);
     for (int i = tid; i < G * DD; i += 256) {
         const int g = i / DD, d = i - g * DD;
-        const float* pp = a.part + ((int64_t)b * a.Hq + kvh * G + g) * a.nsplit * (DD + 2);
-        float mm = -INFINITY, ll = 0.f, oo = 0.f;
-        for (int sb = 0; sb < a.nsplit; sb += 4) {
-            float ms[4], ls[4], os[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int s = min(sb + j, a.nsplit - 1);
-                ms[j] = sb + j < a.nsplit ? pp[s * (DD + 2) + DD] : -INFINITY;
-                ls[j] = pp[s * (DD + 2) + DD + 1];
-                os[j] = pp[s * (DD + 2) + d];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float mn = fmaxf(mm, ms[j]);
-                const float mr = mn == -INFINITY ? 0.f : mn;
-                const float aa = __builtin_amdgcn_exp2f(mm - mr), c = __builtin_amdgcn_exp2f(ms[j] - mr);
-                ll = ll * aa + ls[j] * c;
-                oo = oo * aa + os[j] * c;
-                mm = mn;
-            }
-        }
-        ((T*)a.out)[(int64_t)b * a.o_sb + (int64_t)(kvh * G + g) * DD + d] = from_f32<T>(ll > 0.f ? oo / ll : 0.f);
+        const float* pp = a.part + part_index<DD>((int64_t)b * a.Hq + kvh * G + g, a.nsplit, 0);
+        ((T*)a.out)[(int64_t)b * a.o_sb + (int64_t)(kvh * G + g) * DD + d] = from_f32<T>(combine_splits<DD>(pp, a.nsplit, d));
     }
     if (tid == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     DSTAMP(10);
@@ -1320,51 +1310,38 @@ extern "C" int uamd_rope_kv_append(void* qkv, int64_t ld_qkv, const void* cos_t,
     return uamd_launch_status();
 }
 
-// keys per block-load of the decode attention kernels (DecGeo<D>::KPB): split_keys must be a multiple of it
-static int dec_block_keys(int D) { return D == 64 ? DecGeo<64>::KPB : DecGeo<128>::KPB; }
-
-#define UAMD_DECODE_G(TT, DV)                                                                                 \
-    switch (G) {                                                                                              \
-        case 1: UAMD_DECODE_LAUNCH(TT, 1, DV); break; case 2: UAMD_DECODE_LAUNCH(TT, 2, DV); break;           \
-        case 3: UAMD_DECODE_LAUNCH(TT, 3, DV); break; case 4: UAMD_DECODE_LAUNCH(TT, 4, DV); break;           \
-        case 5: UAMD_DECODE_LAUNCH(TT, 5, DV); break; case 6: UAMD_DECODE_LAUNCH(TT, 6, DV); break;           \
-        case 7: UAMD_DECODE_LAUNCH(TT, 7, DV); break; case 8: UAMD_DECODE_LAUNCH(TT, 8, DV); break;           \
-        default: return UAMD_ERR_ARG;                                                                         \
-    }
-
-// out[b, h, :] = softmax(q[b, h] . K[b, h / G, first..len) * scale) V  over the cache (len = kv_len[b] + len_add;
-// window > 0: only the last `window` keys). partials: fp32 workspace [B, Hq, nsplit, D + 2]. Replaces
-// llama.py:499-543 (expand + matmul + softmax + matmul, or SDPA).
-extern "C" int uamd_attn_decode(const void* q, int64_t q_sb, const void* k_cache, const void* v_cache, int64_t cache_sb,
-                                int64_t cache_sh, const int* kv_len, int len_add, float* partials, void* out,
-                                int64_t out_sb, int B, int Hq, int Hk, int D, int nsplit, int split_keys, int window,
-                                float scale, int dtype, void* stream) {
-    if (!q || !k_cache || !v_cache || !kv_len || !partials || !out || B <= 0 || Hq <= 0 || Hk <= 0 || Hq % Hk) return UAMD_ERR_ARG;
-    if ((D != 64 && D != 128) || nsplit <= 0 || split_keys <= 0 || split_keys % dec_block_keys(D)) return UAMD_ERR_ARG;
-    if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || (q_sb & 7) || (cache_sb & 7) || (cache_sh & 7)) return UAMD_ERR_ALIGN;
-    const int G = Hq / Hk;
-    const float sl2 = scale * 1.4426950408889634f;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)nsplit, (unsigned)Hk, (unsigned)B);
-#define UAMD_DECODE_LAUNCH(TT, GG, DV)                                                                                   \
-    hipLaunchKernelGGL((attn_decode_kernel<TT, GG, DV>), grid, dim3(256), 0, st, (const TT*)q, q_sb, (const TT*)k_cache,  \
-                       (const TT*)v_cache, cache_sb, cache_sh, kv_len, partials, Hq, nsplit, split_keys, window, sl2, len_add)
-    // every group size up to 8 (the kernel loops over its G query heads; Qwen2.5-7B / Qwen2-VL-7B: G = 7)
-#define UAMD_DECODE_D(TT, DV)                                                                         \
-    UAMD_DECODE_G(TT, DV)                                                                             \
-    if (int rc = uamd_launch_status()) return rc;                                                     \
-    hipLaunchKernelGGL((attn_decode_combine_kernel<TT, DV>), dim3(Hq, B), dim3(DV), 0, st, partials, (TT*)out, out_sb, Hq, nsplit)
-    UAMD_DISPATCH_HALF(dtype, if (D == 128) { UAMD_DECODE_D(T, 128); } else { UAMD_DECODE_D(T, 64); })
-#undef UAMD_DECODE_D
-#undef UAMD_DECODE_LAUNCH
-    return uamd_launch_status();
+namespace {
+// What uamd_attn_decode and uamd_attn_decode_fused ask of the geometry and the cache alike; split_keys: a multiple of the keys
+// per block-load (DecGeo<D>::KPB).
+int attn_decode_check(int Hq, int Hk, int D, int nsplit, int split_keys, const void* k_cache, const void* v_cache,
+                      int64_t cache_sb, int64_t cache_sh) {
+    if (Hq % Hk || (D != 64 && D != 128) || nsplit <= 0 || split_keys <= 0) return UAMD_ERR_ARG;
+    if (split_keys % (D == 64 ? DecGeo<64>::KPB : DecGeo<128>::KPB)) return UAMD_ERR_ARG;
+    if (!aligned16(k_cache) || !aligned16(v_cache) || (cache_sb & 7) || (cache_sh & 7)) return UAMD_ERR_ALIGN;
+    return UAMD_OK;
 }
 
-namespace {
+// f(T(), G, D as std::integral_constant) for the instantiations of the decode attention kernels: both 16-bit types, head dim
+// 64 / 128 (checked before), every group size up to 8 (the kernels loop over their G query heads; Qwen2.5-7B / Qwen2-VL-7B:
+// G = 7).
+template <int N> using IntC = std::integral_constant<int, N>;
+template <typename F>
+int attn_decode_dispatch(int dtype, int D, int G, F&& f) {
+    auto over_g = [&](auto t, auto dd) -> int {
+        switch (G) {
+            case 1: return f(t, IntC<1>(), dd); case 2: return f(t, IntC<2>(), dd); case 3: return f(t, IntC<3>(), dd);
+            case 4: return f(t, IntC<4>(), dd); case 5: return f(t, IntC<5>(), dd); case 6: return f(t, IntC<6>(), dd);
+            case 7: return f(t, IntC<7>(), dd); case 8: return f(t, IntC<8>(), dd);
+            default: return UAMD_ERR_ARG;
+        }
+    };
+    UAMD_DISPATCH_HALF(dtype, return D == 128 ? over_g(T(), IntC<128>()) : over_g(T(), IntC<64>()))
+}
+
 // How many blocks of attn_decode_fused_kernel<T, G, DD> are CERTAINLY resident at once on the current device: one per compute
 // unit THIS device has (a CPX / SPX partition reports its own CU count), and none when a block does not fit a CU at all.
-// The granule combine below polls for the other splits' partials, so a launch larger than this must not take it (a block
-// that starts only after another exits would be waited for in vain: 2^18 polls, then NaN). Cached per device and instantiation.
+// The granule combine polls for the other splits' partials, so a launch larger than this must not take it (a block that
+// starts only after another exits would be waited for in vain: 2^18 polls, then NaN). Cached per device and instantiation.
 template <typename T, int G, int DD>
 int attn_fused_resident_blocks() {
     static int cap[UAMD_DEVICE_SLOTS];
@@ -1383,17 +1360,39 @@ int attn_fused_resident_blocks() {
 }
 }  // namespace
 
+// out[b, h, :] = softmax(q[b, h] . K[b, h / G, first..len) * scale) V  over the cache (len = kv_len[b] + len_add;
+// window > 0: only the last `window` keys). partials: fp32 workspace [B, Hq, nsplit, D + 2]. Replaces
+// llama.py:499-543 (expand + matmul + softmax + matmul, or SDPA).
+extern "C" int uamd_attn_decode(const void* q, int64_t q_sb, const void* k_cache, const void* v_cache, int64_t cache_sb,
+                                int64_t cache_sh, const int* kv_len, int len_add, float* partials, void* out,
+                                int64_t out_sb, int B, int Hq, int Hk, int D, int nsplit, int split_keys, int window,
+                                float scale, int dtype, void* stream) {
+    if (!q || !k_cache || !v_cache || !kv_len || !partials || !out || B <= 0 || Hq <= 0 || Hk <= 0) return UAMD_ERR_ARG;
+    if (int rc = attn_decode_check(Hq, Hk, D, nsplit, split_keys, k_cache, v_cache, cache_sb, cache_sh)) return rc;
+    if (!aligned16(q) || (q_sb & 7)) return UAMD_ERR_ALIGN;
+    const float sl2 = scale * 1.4426950408889634f;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)nsplit, (unsigned)Hk, (unsigned)B);
+    return attn_decode_dispatch(dtype, D, Hq / Hk, [&](auto t, auto g, auto dd) -> int {
+        using T = decltype(t);
+        constexpr int G = decltype(g)::value, DD = decltype(dd)::value;
+        hipLaunchKernelGGL((attn_decode_kernel<T, G, DD>), grid, dim3(256), 0, st, (const T*)q, q_sb, (const T*)k_cache,
+                           (const T*)v_cache, cache_sb, cache_sh, kv_len, partials, Hq, nsplit, split_keys, window, sl2, len_add);
+        if (int rc = uamd_launch_status()) return rc;
+        hipLaunchKernelGGL((attn_decode_combine_kernel<T, DD>), dim3(Hq, B), dim3(DD), 0, st, partials, (T*)out, out_sb, Hq, nsplit);
+        return uamd_launch_status();
+    });
+}
+
 extern "C" int uamd_attn_decode_fused(const void* qkv, int64_t ld_qkv, const void* cos_t, const void* sin_t, int64_t ld_cs,
                                       const int* kv_len, const int* rope_pos, void* k_cache, void* v_cache,
                                       int64_t cache_sb, int64_t cache_sh, float* partials, int* counters, void* out,
                                       int64_t out_sb, int B, int Hq, int Hk, int D, int s_max, int nsplit, int split_keys,
                                       int window, float scale, unsigned tag, const int* tag_dev, int dtype, void* stream) {
     if (!qkv || !cos_t || !sin_t || !kv_len || !k_cache || !v_cache || !partials || !counters || !out || B <= 0 || Hq <= 0 ||
-        Hk <= 0 || Hq % Hk || s_max <= 0)
+        Hk <= 0 || s_max <= 0)
         return UAMD_ERR_ARG;
-    if ((D != 64 && D != 128) || nsplit <= 0 || split_keys <= 0 || split_keys % dec_block_keys(D)) return UAMD_ERR_ARG;
-    if (!aligned16(k_cache) || !aligned16(v_cache) || (cache_sb & 7) || (cache_sh & 7)) return UAMD_ERR_ALIGN;
-    const int G = Hq / Hk;
+    if (int rc = attn_decode_check(Hq, Hk, D, nsplit, split_keys, k_cache, v_cache, cache_sb, cache_sh)) return rc;
     AttnDecFusedArgs a;
     a.qkv = qkv; a.ld_qkv = ld_qkv; a.cos_t = cos_t; a.sin_t = sin_t; a.ld_cs = ld_cs; a.kv_len = kv_len; a.rope_pos = rope_pos;
     a.kc = k_cache; a.vc = v_cache; a.c_sb = cache_sb; a.c_sh = cache_sh; a.part = partials; a.counters = counters;
@@ -1403,20 +1402,17 @@ extern "C" int uamd_attn_decode_fused(const void* qkv, int64_t ld_qkv, const voi
     // device this call runs on, attn_fused_resident_blocks): a block polls for the partials of its KV head's other splits
     const int64_t blocks = (int64_t)nsplit * Hk * B;
     const bool want_gran = tag != 0 || tag_dev;                                       // (no tag: the arrival-counter path)
-    a.gran = 0;
     a.tag = tag;
     a.tag_dev = tag_dev;
     hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)nsplit, (unsigned)Hk, (unsigned)B);
-#define UAMD_DECODE_LAUNCH(TT, GG, DV)                                                                 \
-    do {                                                                                               \
-        a.gran = (want_gran && blocks <= attn_fused_resident_blocks<TT, GG, DV>()) ? 1 : 0;            \
-        hipLaunchKernelGGL((attn_decode_fused_kernel<TT, GG, DV>), grid, dim3(256), 0, st, a);         \
-    } while (0)
-    UAMD_DISPATCH_HALF(dtype, if (D == 128) { UAMD_DECODE_G(T, 128) } else { UAMD_DECODE_G(T, 64) })
-#undef UAMD_DECODE_LAUNCH
-#undef UAMD_DECODE_G
-    return uamd_launch_status();
+    const dim3 grid((unsigned)nsplit, (unsigned)Hk, (unsigned)B);
+    return attn_decode_dispatch(dtype, D, Hq / Hk, [&](auto t, auto g, auto dd) -> int {
+        using T = decltype(t);
+        constexpr int G = decltype(g)::value, DD = decltype(dd)::value;
+        a.gran = (want_gran && blocks <= attn_fused_resident_blocks<T, G, DD>()) ? 1 : 0;
+        hipLaunchKernelGGL((attn_decode_fused_kernel<T, G, DD>), grid, dim3(256), 0, st, a);
+        return uamd_launch_status();
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
