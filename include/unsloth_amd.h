@@ -306,8 +306,8 @@ int uamd_gemm_tn_256(const void* A, int64_t lda, int M, int K, const uamd_gemm_g
  * also be set from the environment -- UAMD_ATTN_VAR, UAMD_GLU_XA, UAMD_GEMM_S: the ones whose best value depends on the workload --;
  * the A/Bs of the others are settled and they remain here for the parity tests only (every listed value is exercised by one).
  *   UAMD_TUNE_GROUP_M     row panels per raster group of the 256x256 kernel (L2 reuse) */
-#define UAMD_TUNE_GLU_VAR 0     /* gated-MLP activation kernels: 0 = 2048-block grid-stride, 1 = uncapped grid,
-                                 * one 16-byte vector per thread, 2 = uncapped grid, two vectors per thread */
+#define UAMD_TUNE_GLU_VAR 0     /* gated-MLP activation kernels, one body with two parameters: 0 = one 16-byte vector per thread
+                                 * per trip, grid capped at 2048 blocks, 1 = one vector, uncapped grid, 2 = two vectors, uncapped */
 #define UAMD_TUNE_GROUP_M 1
 #define UAMD_TUNE_STREAM_NT 2   /* streaming kernels: bit0 non-temporal loads, bit1 n.t. stores */
 #define UAMD_TUNE_DEQUANT_T 3   /* transposing NF4 dequant: 1 = 64x256 tile kernel, 0 = 64x64, 2 = 64x256 with

@@ -10,6 +10,7 @@ file covers 0, 1, 2 and 5.
 import pytest
 import torch
 
+from oracle import ref_ops as R
 from tests._util import assert_ulp
 
 pytestmark = pytest.mark.gpu
@@ -31,11 +32,18 @@ def lib():
         L.uamd_set_tuning(k, v)
 
 
-def _glu(n_rows, dtype):
+FLAT = "812vec+3"       # 812 16-byte vectors + 3 elements, flat: with two vectors per thread block 0 runs a full trip and block 1 a
+                        # trip of 256 first and 44 second vectors; with one, four blocks, the last one partial; 3 elements for the tail
+
+
+def _glu_inputs(rows, dtype):
+    shape = (812 * (16 // dtype.itemsize) + 3,) if rows == FLAT else (rows, 14336)
+    return tuple(torch.randn(*shape, generator=g(seed)).to(dtype) for seed in (1, 2, 3))
+
+
+def _glu(rows, dtype):
     from unsloth_amd.kernels.swiglu import swiglu_fg_kernel, swiglu_DWf_DW_dfg_kernel
-    e = torch.randn(n_rows, 14336, generator=g(1)).to(dtype).to(DEV)
-    gt = torch.randn(n_rows, 14336, generator=g(2)).to(dtype).to(DEV)
-    dw = torch.randn(n_rows, 14336, generator=g(3)).to(dtype).to(DEV)
+    e, gt, dw = (t.to(DEV) for t in _glu_inputs(rows, dtype))
     h = swiglu_fg_kernel(e, gt)
     outs = swiglu_DWf_DW_dfg_kernel(dw.clone(), e.clone(), gt.clone())
     return (h,) + tuple(outs)
@@ -52,9 +60,15 @@ def _rms(rows, dim, dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
-@pytest.mark.parametrize("rows", [3, 700])                       # 700 x 14336 = past the 2048-block cap of variant 0
+@pytest.mark.parametrize("rows", [3, 700, FLAT])                 # 700 x 14336 = past the 2048-block cap of variant 0
 def test_glu_grid_variants_and_cache_hints_are_bitwise_equal(lib, rows, dtype):
     want = _glu(rows, dtype)
+    if rows == FLAT:        # the default against the oracle too (the bounds of test_gpu_elementwise.py::test_glu), not only itself
+        e, gt, dw = _glu_inputs(rows, dtype)
+        ref = (R.glu_forward(e, gt, "swiglu"),) + R.glu_backward(dw, e, gt, "swiglu")
+        f32 = dtype == torch.float32
+        for a, b, what, ulps, at in zip(want, ref, ("fwd h", "bwd h", "bwd df", "bwd de"), (1, 1, 1, 2), (1e-6, 4e-6, 4e-6, 4e-6)):
+            assert_ulp(a, b, dtype, ulps=32 if f32 else ulps, atol=at if f32 else None, what=what, allow_frac=5e-3)
     for var in (0, 1, 2):
         for nt in (0, 1, 2, 3):
             assert lib.uamd_set_tuning(GLU_VAR, var) == 0 and lib.uamd_set_tuning(STREAM_NT, nt) == 0

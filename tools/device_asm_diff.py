@@ -5,7 +5,7 @@ Compiles every file of _build.SOURCES in both trees to device-only assembly with
 + --cuda-device-only -S) and compares. Lines naming __hip_cuid_ (a hash of the translation unit) may differ. A file whose
 lines differ otherwise is compared kernel by kernel (a host-side change of dispatch order makes the compiler emit the same
 kernels in another order, which renumbers the local labels): same set of kernels, same body and .amdhsa_ block per kernel,
-same metadata entry per kernel. Exit status 0 = the same device code. No GPU needed."""
+same metadata entry per kernel; every kernel that differs is named. Exit status 0 = the same device code. No GPU needed."""
 import difflib
 import importlib.util
 import os
@@ -74,10 +74,10 @@ def main():
         msg = f"{s:24s} {len(d) - len(foreign):3d} __hip_cuid_ lines, {len(foreign)} foreign lines"
         if foreign:
             (ka, ma), (kb, mb) = kernels(a[s]), kernels(b[s])
-            diff = sorted(k for k in set(ka) | set(kb) if ka.get(k) != kb.get(k)) + sorted(k for k in set(ma) | set(mb) if ma.get(k) != mb.get(k))
+            diff = sorted({k for k in set(ka) | set(kb) if ka.get(k) != kb.get(k)} | {k for k in set(ma) | set(mb) if ma.get(k) != mb.get(k)})
             if diff:
                 bad += 1
-                msg += f" -- DEVICE CODE DIFFERS: {len(diff)} kernels, e.g. {diff[0]}"
+                msg += f" -- DEVICE CODE DIFFERS: {len(diff)} kernels" + "".join("\n    " + k for k in diff)
             else:
                 reordered += 1
                 foreign = []

@@ -9,8 +9,9 @@
 //   unsloth/kernels/geglu.py:142-167   _approx_forward_kernel
 //   unsloth/kernels/geglu.py:188-244   _approx_backward_kernel
 //
-// HBM-bound streaming kernels: 16-byte vectors per lane, two vectors per thread with every load of both issued
-// before the first use, one pass per 256-thread block over an UNCAPPED grid (the hardware dispatcher streams the
+// HBM-bound streaming kernels, one body per direction with two launch parameters (UAMD_TUNE_GLU_VAR, launch_glu): 16-byte
+// vectors per lane, NV vectors per thread per trip with every load of the trip issued before the first use, and the grid. The
+// default is two vectors per thread and one trip per 256-thread block over an UNCAPPED grid (the hardware dispatcher streams the
 // blocks; the round-1 version ran 2048 persistent blocks with a grid-stride loop: 5.85 -> 6.7 TB/s forward,
 // 5.04 -> 5.66 TB/s backward at 8192 tokens, profiles/r02_hbm_ab.jsonl; the reference's Triton kernels on the same
 // box: 5.5 / 6.0 TB/s, profiles/r02_ref_triton_microbench.jsonl). Inputs are read exactly once (2-3 x 235 MB at
@@ -25,9 +26,6 @@
 namespace {
 
 enum { ACT_SWIGLU = 0, ACT_GEGLU_EXACT = 1, ACT_GEGLU_APPROX = 2 };
-#ifndef UAMD_GLU_KNOCK
-#define UAMD_GLU_KNOCK 0      /* != 0: timing-only builds of glu_xa_kernel with one ingredient compiled out (results are wrong) */
-#endif
 
 __device__ __forceinline__ float sigmoidf_(float x) { return uamd_sigmoid(x); }      // common.h
 
@@ -67,30 +65,12 @@ __device__ __forceinline__ void act_bwd(float e, float& f, float& dfde) {
     }
 }
 
+// one element of the forward: f is rounded to the activation dtype before the product, which is a product IN that dtype
 template <typename T, int ACT>
-__global__ void __launch_bounds__(256)
-glu_fwd_kernel(const T* __restrict__ E, const T* __restrict__ G, T* __restrict__ H, int64_t n, int mode) {
-    constexpr int VEC = Vec16<T>::N;
-    const int64_t nvec = n / VEC;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += stride) {
-        Vec16<T> e = ld16_m(E + i * VEC, mode), g = ld16_m(G + i * VEC, mode), h;
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            float f;
-            act_fwd<ACT>(to_f32(e.e[j]), f);
-            h.e[j] = from_f32<T>(round_to<T>(f) * to_f32(g.e[j]));
-        }
-        st16_m(H + i * VEC, h, mode);
-    }
-    // tail (n not a multiple of VEC)
-    if (blockIdx.x == 0) {
-        for (int64_t k = nvec * VEC + threadIdx.x; k < n; k += 256) {
-            float f;
-            act_fwd<ACT>(to_f32(E[k]), f);
-            H[k] = from_f32<T>(round_to<T>(f) * to_f32(G[k]));
-        }
-    }
+__device__ __forceinline__ T fwd_one(T e, T g) {
+    float f;
+    act_fwd<ACT>(to_f32(e), f);
+    return from_f32<T>(round_to<T>(f) * to_f32(g));
 }
 
 template <typename T, int ACT>
@@ -112,151 +92,110 @@ __device__ __forceinline__ void bwd_one(T dw, T e, T g, T& h, T& df, T& de) {
     }
 }
 
-template <typename T, int ACT>
-__global__ void __launch_bounds__(256) glu_bwd_kernel(T* DW, T* E, T* G, int64_t n, int mode) {
-    constexpr int VEC = Vec16<T>::N;
-    const int64_t nvec = n / VEC;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += stride) {
-        Vec16<T> dw = ld16_m(DW + i * VEC, mode), e = ld16_m(E + i * VEC, mode), g = ld16_m(G + i * VEC, mode);
-        Vec16<T> h, df, de;
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) bwd_one<T, ACT>(dw.e[j], e.e[j], g.e[j], h.e[j], df.e[j], de.e[j]);
-        st16_m(DW + i * VEC, h, mode);   // swiglu.py:107-109
-        st16_m(E + i * VEC, df, mode);
-        st16_m(G + i * VEC, de, mode);
-    }
-    if (blockIdx.x == 0) {
-        for (int64_t k = nvec * VEC + threadIdx.x; k < n; k += 256) {
-            T h, df, de;
-            bwd_one<T, ACT>(DW[k], E[k], G[k], h, df, de);
-            DW[k] = h; E[k] = df; G[k] = de;
-        }
-    }
-}
-
-// Two vectors per thread, both tensors' loads of both vectors in flight before the first use; one pass per block
-// (no grid-stride loop: the hardware dispatcher streams 256-thread blocks, which is how the reference's Triton
-// kernel reaches 6.0 TB/s on this shape).
-template <typename T, int ACT>
-__global__ void __launch_bounds__(256) glu_bwd2_kernel(T* DW, T* E, T* G, int64_t n, int mode) {
-    constexpr int VEC = Vec16<T>::N;
-    const int64_t nvec = n / VEC;
-    const int64_t i0 = (int64_t)blockIdx.x * 512 + threadIdx.x, i1 = i0 + 256;
-    if (i1 < nvec) {
-        Vec16<T> dw0 = ld16_m(DW + i0 * VEC, mode), e0 = ld16_m(E + i0 * VEC, mode), g0 = ld16_m(G + i0 * VEC, mode);
-        Vec16<T> dw1 = ld16_m(DW + i1 * VEC, mode), e1 = ld16_m(E + i1 * VEC, mode), g1 = ld16_m(G + i1 * VEC, mode);
-        Vec16<T> h, df, de;
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) bwd_one<T, ACT>(dw0.e[j], e0.e[j], g0.e[j], h.e[j], df.e[j], de.e[j]);
-        st16_m(DW + i0 * VEC, h, mode);
-        st16_m(E + i0 * VEC, df, mode);
-        st16_m(G + i0 * VEC, de, mode);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) bwd_one<T, ACT>(dw1.e[j], e1.e[j], g1.e[j], h.e[j], df.e[j], de.e[j]);
-        st16_m(DW + i1 * VEC, h, mode);
-        st16_m(E + i1 * VEC, df, mode);
-        st16_m(G + i1 * VEC, de, mode);
-    } else if (i0 < nvec) {
-        Vec16<T> dw = ld16_m(DW + i0 * VEC, mode), e = ld16_m(E + i0 * VEC, mode), g = ld16_m(G + i0 * VEC, mode);
-        Vec16<T> h, df, de;
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) bwd_one<T, ACT>(dw.e[j], e.e[j], g.e[j], h.e[j], df.e[j], de.e[j]);
-        st16_m(DW + i0 * VEC, h, mode);
-        st16_m(E + i0 * VEC, df, mode);
-        st16_m(G + i0 * VEC, de, mode);
-    }
-    if (blockIdx.x == 0) {
-        for (int64_t k = nvec * VEC + threadIdx.x; k < n; k += 256) {
-            T h, df, de;
-            bwd_one<T, ACT>(DW[k], E[k], G[k], h, df, de);
-            DW[k] = h; E[k] = df; G[k] = de;
-        }
-    }
-}
-
-template <typename T, int ACT>
+// The streaming body, one per direction. A trip of a block = 256 * NV vectors: thread t takes vectors t + 256 v (v < NV) of
+// it, issues every load of the trip before the first use, then computes and stores vector by vector; the trips are a
+// grid-stride loop (one trip per block under an uncapped grid: the hardware dispatcher streams 256-thread blocks, which is
+// how the reference's Triton kernel reaches 6.0 TB/s on this shape). The elements past the last whole vector go to block 0.
+//
+// The forward writes its NV = 2 trip out as ONE PASS with a whole-trip and a one-vector branch instead of the loop, because
+// the last bit of fp16 GeGLU depends on it: where hipcc's SLP vectoriser pairs two elements, f = 0.5 e (1 + ..) is a
+// v_mul_f32 and a v_cvt_pk_f16_f32 (two roundings); where it does not, one v_fma_mixlo_f16 (one rounding) -- 1 element in
+// ~10^4 differs by an ulp, and which elements are paired follows the shape of the source. The loop form of NV = 2 pairs
+// none (it agrees with NV = 1 bit for bit); this form pairs what the two-vector kernel always paired, so every variant
+// returns what it returned before. SwiGLU and bf16 round the same way in every form.
+template <typename T, int ACT, int NV>
 __global__ void __launch_bounds__(256)
-glu_fwd2_kernel(const T* __restrict__ E, const T* __restrict__ G, T* __restrict__ H, int64_t n, int mode) {
+glu_fwd_kernel(const T* __restrict__ E, const T* __restrict__ G, T* __restrict__ H, int64_t n, int mode) {
     constexpr int VEC = Vec16<T>::N;
     const int64_t nvec = n / VEC;
-    const int64_t i0 = (int64_t)blockIdx.x * 512 + threadIdx.x, i1 = i0 + 256;
     auto one = [&](const Vec16<T>& e, const Vec16<T>& g, int64_t i) {
         Vec16<T> h;
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            float f;
-            act_fwd<ACT>(to_f32(e.e[j]), f);
-            h.e[j] = from_f32<T>(round_to<T>(f) * to_f32(g.e[j]));
-        }
+        for (int j = 0; j < VEC; ++j) h.e[j] = fwd_one<T, ACT>(e.e[j], g.e[j]);
         st16_m(H + i * VEC, h, mode);
     };
-    if (i1 < nvec) {
-        Vec16<T> e0 = ld16_m(E + i0 * VEC, mode), g0 = ld16_m(G + i0 * VEC, mode);
-        Vec16<T> e1 = ld16_m(E + i1 * VEC, mode), g1 = ld16_m(G + i1 * VEC, mode);
-        one(e0, g0, i0);
-        one(e1, g1, i1);
-    } else if (i0 < nvec) {
-        Vec16<T> e0 = ld16_m(E + i0 * VEC, mode), g0 = ld16_m(G + i0 * VEC, mode);
-        one(e0, g0, i0);
+    if constexpr (NV == 2) {
+        const int64_t i0 = (int64_t)blockIdx.x * 512 + threadIdx.x, i1 = i0 + 256;
+        if (i1 < nvec) {
+            Vec16<T> e0 = ld16_m(E + i0 * VEC, mode), g0 = ld16_m(G + i0 * VEC, mode);
+            Vec16<T> e1 = ld16_m(E + i1 * VEC, mode), g1 = ld16_m(G + i1 * VEC, mode);
+            one(e0, g0, i0);
+            one(e1, g1, i1);
+        } else if (i0 < nvec) {
+            Vec16<T> e0 = ld16_m(E + i0 * VEC, mode), g0 = ld16_m(G + i0 * VEC, mode);
+            one(e0, g0, i0);
+        }
+    } else {
+        const int64_t stride = (int64_t)gridDim.x * 256;
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += stride) {
+            Vec16<T> e = ld16_m(E + i * VEC, mode), g = ld16_m(G + i * VEC, mode), h;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) h.e[j] = fwd_one<T, ACT>(e.e[j], g.e[j]);
+            st16_m(H + i * VEC, h, mode);
+        }
+    }
+    if (blockIdx.x == 0)
+        for (int64_t k = nvec * VEC + threadIdx.x; k < n; k += 256) H[k] = fwd_one<T, ACT>(E[k], G[k]);
+}
+
+template <typename T, int ACT, int NV>
+__global__ void __launch_bounds__(256) glu_bwd_kernel(T* DW, T* E, T* G, int64_t n, int mode) {
+    constexpr int VEC = Vec16<T>::N;
+    const int64_t nvec = n / VEC;
+    const int64_t stride = (int64_t)gridDim.x * (256 * NV);
+    for (int64_t i0 = (int64_t)blockIdx.x * (256 * NV) + threadIdx.x; i0 < nvec; i0 += stride) {
+        Vec16<T> dw[NV], e[NV], g[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const int64_t i = i0 + 256 * v;
+            if (i < nvec) dw[v] = ld16_m(DW + i * VEC, mode), e[v] = ld16_m(E + i * VEC, mode), g[v] = ld16_m(G + i * VEC, mode);
+        }
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const int64_t i = i0 + 256 * v;
+            if (i >= nvec) break;
+            Vec16<T> h, df, de;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) bwd_one<T, ACT>(dw[v].e[j], e[v].e[j], g[v].e[j], h.e[j], df.e[j], de.e[j]);
+            st16_m(DW + i * VEC, h, mode);   // swiglu.py:107-109
+            st16_m(E + i * VEC, df, mode);
+            st16_m(G + i * VEC, de, mode);
+        }
     }
     if (blockIdx.x == 0) {
         for (int64_t k = nvec * VEC + threadIdx.x; k < n; k += 256) {
-            float f;
-            act_fwd<ACT>(to_f32(E[k]), f);
-            H[k] = from_f32<T>(round_to<T>(f) * to_f32(G[k]));
+            T h, df, de;
+            bwd_one<T, ACT>(DW[k], E[k], G[k], h, df, de);
+            DW[k] = h; E[k] = df; G[k] = de;
         }
     }
 }
 
-// UAMD_TUNE_GLU_VAR: 0 = 2048-block grid-stride kernels, 1 = the same kernels with one vector per thread and an
-// uncapped grid, 2 = two vectors per thread, uncapped grid
-inline unsigned grid_for(int64_t nvec, int var) {
-    int64_t blocks = (nvec + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    const int64_t cap = var == 0 ? 256 * 8 : 0x7fffffffLL;  // 256 CUs x 8 resident 256-thread blocks
-    return (unsigned)(blocks < cap ? blocks : cap);
-}
-
-template <typename T, int ACT>
-int launch_fwd(const void* e, const void* g, void* h, int64_t n, hipStream_t st) {
-    if (!aligned16(e) || !aligned16(g) || !aligned16(h)) return UAMD_ERR_ALIGN;
-    const int var = uamd_tuning_get(UAMD_TUNE_GLU_VAR);
+// One launcher for both directions (forward: a, b, c = e, g, h; backward: DW, e, g). UAMD_TUNE_GLU_VAR sets the body's two
+// parameters: 0 = one vector per thread per trip, the grid capped at 2048 persistent blocks; 1 = one vector, uncapped grid;
+// 2 = two vectors, uncapped grid. Uncapped = one block per trip up to the grid's limit; the loop covers whatever is left.
+template <typename T, int ACT, bool BWD>
+int launch_glu(void* a, void* b, void* c, int64_t n, hipStream_t st) {
+    if (!aligned16(a) || !aligned16(b) || !aligned16(c)) return UAMD_ERR_ALIGN;
+    const int var = uamd_tuning_get(UAMD_TUNE_GLU_VAR), mode = uamd_tuning_get(UAMD_TUNE_STREAM_NT) ^ 1;
     const int64_t nvec = n / Vec16<T>::N;
-    if (var == 2 && (nvec + 511) / 512 < 0x7fffffffLL)
-        hipLaunchKernelGGL((glu_fwd2_kernel<T, ACT>), dim3((unsigned)((nvec + 511) / 512 > 0 ? (nvec + 511) / 512 : 1)),
-                           dim3(256), 0, st, (const T*)e, (const T*)g, (T*)h, n, uamd_tuning_get(UAMD_TUNE_STREAM_NT) ^ 1);
-    else
-        hipLaunchKernelGGL((glu_fwd_kernel<T, ACT>), dim3(grid_for(nvec, var)), dim3(256), 0, st,
-                           (const T*)e, (const T*)g, (T*)h, n, uamd_tuning_get(UAMD_TUNE_STREAM_NT) ^ 1);
-    return uamd_launch_status();
-}
-template <typename T, int ACT>
-int launch_bwd(void* dw, void* e, void* g, int64_t n, hipStream_t st) {
-    if (!aligned16(dw) || !aligned16(e) || !aligned16(g)) return UAMD_ERR_ALIGN;
-    const int var = uamd_tuning_get(UAMD_TUNE_GLU_VAR);
-    const int64_t nvec = n / Vec16<T>::N;
-    if (var == 2 && (nvec + 511) / 512 < 0x7fffffffLL)
-        hipLaunchKernelGGL((glu_bwd2_kernel<T, ACT>), dim3((unsigned)((nvec + 511) / 512 > 0 ? (nvec + 511) / 512 : 1)),
-                           dim3(256), 0, st, (T*)dw, (T*)e, (T*)g, n, uamd_tuning_get(UAMD_TUNE_STREAM_NT) ^ 1);
-    else
-        hipLaunchKernelGGL((glu_bwd_kernel<T, ACT>), dim3(grid_for(nvec, var)), dim3(256), 0, st,
-                           (T*)dw, (T*)e, (T*)g, n, uamd_tuning_get(UAMD_TUNE_STREAM_NT) ^ 1);
+    // (the forward's NV = 2 is one pass: a tensor of more trips than a grid has blocks takes the one-vector loop)
+    uamd_with_iters<1, 2>(var == 2 && (nvec + 511) / 512 <= 0x7fffffffLL ? 2 : 1, [&](auto nv) {
+        constexpr int NV = decltype(nv)::value;
+        const int64_t trips = (nvec + 256 * NV - 1) / (256 * NV);
+        const int64_t cap = var == 0 ? 256 * 8 : 0x7fffffffLL;  // 256 CUs x 8 resident 256-thread blocks
+        const dim3 grid((unsigned)(trips < 1 ? 1 : trips < cap ? trips : cap));
+        if constexpr (BWD) hipLaunchKernelGGL((glu_bwd_kernel<T, ACT, NV>), grid, dim3(256), 0, st, (T*)a, (T*)b, (T*)c, n, mode);
+        else hipLaunchKernelGGL((glu_fwd_kernel<T, ACT, NV>), grid, dim3(256), 0, st, (const T*)a, (const T*)b, (T*)c, n, mode);
+    });
     return uamd_launch_status();
 }
 
-template <int ACT>
-int fwd(const void* e, const void* g, void* h, int64_t n, int dtype, void* stream) {
+template <int ACT, bool BWD>
+int glu(void* a, void* b, void* c, int64_t n, int dtype, void* stream) {
     if (n < 0) return UAMD_ERR_ARG;
     if (n == 0) return UAMD_OK;
-    UAMD_DISPATCH_FLOAT(dtype, return (launch_fwd<T, ACT>(e, g, h, n, (hipStream_t)stream)))
-    return UAMD_ERR_DTYPE;
-}
-template <int ACT>
-int bwd(void* dw, void* e, void* g, int64_t n, int dtype, void* stream) {
-    if (n < 0) return UAMD_ERR_ARG;
-    if (n == 0) return UAMD_OK;
-    UAMD_DISPATCH_FLOAT(dtype, return (launch_bwd<T, ACT>(dw, e, g, n, (hipStream_t)stream)))
+    UAMD_DISPATCH_FLOAT(dtype, return (launch_glu<T, ACT, BWD>(a, b, c, n, (hipStream_t)stream)))
     return UAMD_ERR_DTYPE;
 }
 
@@ -388,13 +327,8 @@ glu_xa_kernel(T* __restrict__ DW, T* __restrict__ E, T* __restrict__ G, T* __res
             const int kk = kc + l4 * 8 + 8 <= K ? kc : 0;
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-#if UAMD_GLU_KNOCK & 1     /* knock-out build (tools/glu_xa_ab.py): no factor-fragment loads */
-                r.wf0[q][t] = make_uint4(kk, kk, kk, kk);
-                if (NS > 1) r.wf1[q][t] = make_uint4(kk, kk, kk, kk);
-#else
                 r.wf0[q][t] = *reinterpret_cast<const uint4*>(W0 + woff0[t] + kk);
                 if (NS > 1) r.wf1[q][t] = *reinterpret_cast<const uint4*>(W1 + woff1[t] + kk);
-#endif
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -420,11 +354,7 @@ glu_xa_kernel(T* __restrict__ DW, T* __restrict__ E, T* __restrict__ G, T* __res
             v1.raw = make_uint4(0, 0, 0, 0);
             if (NS == 1) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    float f;
-                    act_fwd<ACT>(to_f32(r.e[v].e[j]), f);
-                    v0.e[j] = from_f32<T>(round_to<T>(f) * to_f32(r.g[v].e[j]));
-                }
+                for (int j = 0; j < 8; ++j) v0.e[j] = fwd_one<T, ACT>(r.e[v].e[j], r.g[v].e[j]);
                 if (col_ok && row_ok[v]) st16_nt(H + roff[v] + c, v0);
             } else {
                 Vec16<T> h;
@@ -440,16 +370,10 @@ glu_xa_kernel(T* __restrict__ DW, T* __restrict__ E, T* __restrict__ G, T* __res
                 v0.raw = make_uint4(0, 0, 0, 0);
                 v1.raw = make_uint4(0, 0, 0, 0);
             }
-#if !(UAMD_GLU_KNOCK & 2)
             unsigned char* dst = buf + ((16 / NV) * v + srow) * GX_LD + scol * 2;
             *reinterpret_cast<uint4*>(dst) = v0.raw;
             if (NS > 1) *reinterpret_cast<uint4*>(dst + GX_TILE) = v1.raw;
-#endif
         }
-#if UAMD_GLU_KNOCK & 2     /* knock-out build: no LDS hand-off, no barrier, no MFMA -- the activation on this tiling alone */
-        (void)buf;
-        return;
-#endif
         // the tile is complete (and buf ^ 1 is free again). NOT __syncthreads(): that drains vmcnt too, i.e. waits for
         // the NEXT tile's loads issued above -- the prefetch would buy nothing (first build: 4.1 / 4.65 TB/s)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -564,6 +488,9 @@ glu_xa_kernel(T* __restrict__ DW, T* __restrict__ E, T* __restrict__ G, T* __res
         if (tid == 0) __hip_atomic_store(counters + rg, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
+    // (`out` and `out_k` in loops of their own, apart from the split path's merged one: one loop for all three was built
+    // twice and cost registers both times -- more SGPRs in 25 resp. 34 of the 52 instances, one more VGPR in a default
+    // SwiGLU instance, more scratch in the rank-64 backward -- so the three stay)
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         const GluXaOut& o = s == 0 ? o0 : o1;
@@ -629,6 +556,8 @@ inline bool split_handoff_ok() {
 
 constexpr int GX_TPB = 4;     // (workspace sizing: parts of at least this many tiles)
 
+inline int xa_rank_tiles(int R) { return R <= 16 ? 1 : R <= 32 ? 2 : 4; }      // 16-rank tiles per product (the kernel's NT)
+
 template <typename T, int ACT, int NS>
 int launch_xa(void* dw, void* e, void* g, void* h, int M, int K, int64_t ld, const GluXaOut& o0, const GluXaOut& o1,
               hipStream_t st, float* ws, int* counters) {
@@ -662,46 +591,46 @@ int launch_xa(void* dw, void* e, void* g, void* h, int M, int K, int64_t ld, con
     const int64_t blocks = (int64_t)((M + 15) / 16) * nparts;
     if (blocks > 0x7fffffffLL) return UAMD_ERR_ARG;
     const dim3 grid((unsigned)blocks);
-#define GLU_XA_ARGS (T*)dw, (T*)e, (T*)g, (T*)h, M, K, ld, o0, o1, ws, counters, nparts, tpb
-#define GLU_XA_LAUNCH(NT_)                                                                                                   \
-    do {                                                                                                                     \
-        if constexpr (ACT != ACT_SWIGLU || (NS > 1 && NT_ > 1)) hipLaunchKernelGGL((glu_xa_kernel<T, ACT, NS, NT_, 1, 1>), grid, dim3(256), 0, st, GLU_XA_ARGS); \
-        else if (xv >= 2) hipLaunchKernelGGL((glu_xa_kernel<T, ACT, NS, NT_, 2, 2>), grid, dim3(512), 0, st, GLU_XA_ARGS);   \
-        else if (xv == 1) hipLaunchKernelGGL((glu_xa_kernel<T, ACT, NS, NT_, 2, 1>), grid, dim3(512), 0, st, GLU_XA_ARGS);   \
-        else hipLaunchKernelGGL((glu_xa_kernel<T, ACT, NS, NT_, 1, 1>), grid, dim3(256), 0, st, GLU_XA_ARGS);                \
-    } while (0)
-    if (R <= 16) GLU_XA_LAUNCH(1);
-    else if (R <= 32) GLU_XA_LAUNCH(2);
-    else GLU_XA_LAUNCH(4);
-#undef GLU_XA_LAUNCH
-#undef GLU_XA_ARGS
+    // the instance: NT rank tiles; 8 waves (KS = 2) and the depth-2 prefetch (PD = 2) only where the note above says so
+    uamd_with_iters<1, 2, 4>(xa_rank_tiles(R), [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        auto go = [&](auto ks, auto pd) {
+            constexpr int KS = decltype(ks)::value, PD = decltype(pd)::value;
+            hipLaunchKernelGGL((glu_xa_kernel<T, ACT, NS, NT, KS, PD>), grid, dim3(256 * KS), 0, st, (T*)dw, (T*)e, (T*)g, (T*)h,
+                               M, K, ld, o0, o1, ws, counters, nparts, tpb);
+        };
+        constexpr std::integral_constant<int, 1> c1{};
+        constexpr std::integral_constant<int, 2> c2{};
+        if constexpr (ACT != ACT_SWIGLU || (NS > 1 && NT > 1)) go(c1, c1);
+        else if (xv >= 2) go(c2, c2);
+        else if (xv == 1) go(c2, c1);
+        else go(c1, c1);
+    });
     return uamd_launch_status();
 }
 
-int check_xa_out(const GluXaOut& o, int K) {
+int check_xa_out(const GluXaOut& o) {
     if (!o.out || !o.W || o.R < 1 || o.R > 64 || o.out_cols < o.R) return UAMD_ERR_ARG;
     if ((o.ldw & 7) || !aligned16(o.W)) return UAMD_ERR_ALIGN;
     if (o.out_k && o.k_cols < o.R) return UAMD_ERR_ARG;
-    (void)K;
     return UAMD_OK;
 }
 
 // floats of workspace the column split needs for an [M, K] launch (uamd_glu_xa_workspace)
 int64_t xa_ws_floats(int M, int K, int NS, int R) {
-    const int NT = R <= 16 ? 1 : (R <= 32 ? 2 : 4);
     const int ntiles = (K + GX_TK - 1) / GX_TK;
-    return (int64_t)((M + 15) / 16) * ((ntiles + GX_TPB - 1) / GX_TPB) * 16 * (NS * NT * 16);
+    return (int64_t)((M + 15) / 16) * ((ntiles + GX_TPB - 1) / GX_TPB) * 16 * (NS * xa_rank_tiles(R) * 16);
 }
 
 template <int NS>
 int glu_xa_entry(int act, void* dw, void* e, void* g, void* h, int M, int K, int64_t ld, const GluXaOut& o0,
-                 const GluXaOut& o1, int dtype, void* stream, float* ws = nullptr, int64_t ws_floats = 0, int* counters = nullptr) {
+                 const GluXaOut& o1, int dtype, void* stream, float* ws, int64_t ws_floats, int* counters) {
     if (M < 0 || K <= 0 || !e || !g || (NS == 1 ? !h : !dw)) return UAMD_ERR_ARG;
     if (M == 0) return UAMD_OK;
     if ((K & 7) || (ld & 7) || !aligned16(e) || !aligned16(g) || (NS == 1 ? !aligned16(h) : !aligned16(dw))) return UAMD_ERR_ALIGN;
-    int rc = check_xa_out(o0, K);
+    int rc = check_xa_out(o0);
     if (rc) return rc;
-    if (NS > 1 && (rc = check_xa_out(o1, K))) return rc;
+    if (NS > 1 && (rc = check_xa_out(o1))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (ws != nullptr && ws_floats < xa_ws_floats(M, K, NS, NS > 1 ? (o0.R > o1.R ? o0.R : o1.R) : o0.R)) return UAMD_ERR_ARG;
     UAMD_DISPATCH_HALF(dtype,
@@ -720,8 +649,8 @@ int glu_xa_entry(int act, void* dw, void* e, void* g, void* h, int M, int K, int
 extern "C" int uamd_glu_fwd_xa(int act, const void* e, const void* g, void* h, int M, int K, int64_t ld, const void* W,
                                int64_t ldw, int R, float* out, int64_t ld_out, int out_cols, void* out_k, int64_t ld_k,
                                int k_cols, int dtype, void* stream) {
-    GluXaOut o0{out, ld_out, R, out_cols, out_k, ld_k, k_cols, W, ldw};
-    return glu_xa_entry<1>(act, nullptr, const_cast<void*>(e), const_cast<void*>(g), h, M, K, ld, o0, o0, dtype, stream);
+    return uamd_glu_fwd_xa_ws(act, e, g, h, M, K, ld, W, ldw, R, out, ld_out, out_cols, out_k, ld_k, k_cols, nullptr, 0, nullptr,
+                              dtype, stream);
 }
 
 // The in-place backward (DW <- h, e <- df, g <- de) AND P_u[M, R_u] = df @ Wu^T, P_g[M, R_g] = de @ Wg^T (Wu = B_up^T,
@@ -731,9 +660,8 @@ extern "C" int uamd_glu_bwd_xa(int act, void* DW, void* e, void* g, int M, int K
                                void* out_k_u, int64_t ld_k_u, int k_cols_u,
                                const void* Wg, int64_t ldwg, int Rg, float* out_g, int64_t ld_out_g, int out_cols_g,
                                void* out_k_g, int64_t ld_k_g, int k_cols_g, int dtype, void* stream) {
-    GluXaOut o0{out_u, ld_out_u, Ru, out_cols_u, out_k_u, ld_k_u, k_cols_u, Wu, ldwu};
-    GluXaOut o1{out_g, ld_out_g, Rg, out_cols_g, out_k_g, ld_k_g, k_cols_g, Wg, ldwg};
-    return glu_xa_entry<2>(act, DW, e, g, nullptr, M, K, ld, o0, o1, dtype, stream);
+    return uamd_glu_bwd_xa_ws(act, DW, e, g, M, K, ld, Wu, ldwu, Ru, out_u, ld_out_u, out_cols_u, out_k_u, ld_k_u, k_cols_u,
+                              Wg, ldwg, Rg, out_g, ld_out_g, out_cols_g, out_k_g, ld_k_g, k_cols_g, nullptr, 0, nullptr, dtype, stream);
 }
 
 // The same two calls with a workspace: `ws` = at least uamd_glu_xa_workspace(M, K, n_products, max rank) floats, `counters` =
@@ -817,20 +745,20 @@ extern "C" int uamd_quick_gelu_backward(const void* x, void* dy_dx, int64_t n, i
 }
 
 extern "C" int uamd_swiglu_fg(const void* e, const void* g, void* h, int64_t n, int dtype, void* stream) {
-    return fwd<ACT_SWIGLU>(e, g, h, n, dtype, stream);
+    return glu<ACT_SWIGLU, false>(const_cast<void*>(e), const_cast<void*>(g), h, n, dtype, stream);
 }
 extern "C" int uamd_swiglu_DWf_DW_dfg(void* DW, void* e, void* g, int64_t n, int dtype, void* stream) {
-    return bwd<ACT_SWIGLU>(DW, e, g, n, dtype, stream);
+    return glu<ACT_SWIGLU, true>(DW, e, g, n, dtype, stream);
 }
 extern "C" int uamd_geglu_exact_forward(const void* e, const void* g, void* h, int64_t n, int dtype, void* stream) {
-    return fwd<ACT_GEGLU_EXACT>(e, g, h, n, dtype, stream);
+    return glu<ACT_GEGLU_EXACT, false>(const_cast<void*>(e), const_cast<void*>(g), h, n, dtype, stream);
 }
 extern "C" int uamd_geglu_exact_backward(void* DW, void* e, void* g, int64_t n, int dtype, void* stream) {
-    return bwd<ACT_GEGLU_EXACT>(DW, e, g, n, dtype, stream);
+    return glu<ACT_GEGLU_EXACT, true>(DW, e, g, n, dtype, stream);
 }
 extern "C" int uamd_geglu_approx_forward(const void* e, const void* g, void* h, int64_t n, int dtype, void* stream) {
-    return fwd<ACT_GEGLU_APPROX>(e, g, h, n, dtype, stream);
+    return glu<ACT_GEGLU_APPROX, false>(const_cast<void*>(e), const_cast<void*>(g), h, n, dtype, stream);
 }
 extern "C" int uamd_geglu_approx_backward(void* DW, void* e, void* g, int64_t n, int dtype, void* stream) {
-    return bwd<ACT_GEGLU_APPROX>(DW, e, g, n, dtype, stream);
+    return glu<ACT_GEGLU_APPROX, true>(DW, e, g, n, dtype, stream);
 }
