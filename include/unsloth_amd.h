@@ -175,6 +175,25 @@ int uamd_glu_bwd_xa_ws(int act, void* DW, void* e, void* g, int M, int K, int64_
                        const void* Wg, int64_t ldwg, int Rg, float* out_g, int64_t ld_out_g, int out_cols_g,
                        void* out_k_g, int64_t ld_k_g, int k_cols_g, float* ws, int64_t ws_floats, int* counters,
                        int dtype, void* stream);
+/* The SwiGLU backward that also forms the MLP's three WIDE LoRA weight gradients, the contractions over tokens that would
+ * otherwise re-read h, df and de (uamd_lora_tn) -- one pass over DW, e, g (csrc/glu.hip glu_tn_kernel) and one small reduce:
+ *   e <- df, g <- de in place, bit-identical to uamd_swiglu_DWf_DW_dfg; DW is READ-ONLY (h is never stored);
+ *   out_rows: fp32 [M, ld_out], columns [0, Ru) = df @ Wu^T, [Ru, Ru + Rg) = de @ Wg^T (Wu = B_up^T, Wg = B_gate^T, [R, K]);
+ *   out_k (may be NULL): the same sums rounded to `dtype`, [M, ld_k], columns [Ru + Rg, k_cols) zero-filled;
+ *   dA_down [Rd, K] (+)= s_down * Pd^T @ h,  dB_up [K, Ru] (+)= s_up * df^T @ Pu,  dB_gate [K, Rg] (+)= s_gate * de^T @ Pg,
+ *   contiguous fp32; Pd = dY @ B_down, Pu = X @ A_up^T, Pg = X @ A_gate^T: fp32 [M, >= R], rounded to `dtype` on load as in
+ *   uamd_lora_tn; `accumulate` bit 0 / 1 / 2: add into dA_down / dB_up / dB_gate instead of overwriting it.
+ * DW, e, g share the row stride ld. Every rank is 8 or 16 (anything else: UAMD_ERR_ARG, nothing launched); K % 8 == 0,
+ * ld % 8 == 0, ldw % 8 == 0, ldp % 2 == 0, P 8-byte and ws 16-byte aligned (else UAMD_ERR_ALIGN, nothing launched).
+ * ws: uamd_glu_tn_workspace(M, K) BYTES (-1 for an [M, K] the call would reject), one per device and stream. Deterministic:
+ * both reductions run in a fixed order; no atomics. */
+int64_t uamd_glu_tn_workspace(int M, int K);
+int uamd_glu_bwd_tn_ws(const void* DW, void* e, void* g, int M, int K, int64_t ld,
+                       const void* Wu, int64_t ldwu, int Ru, const void* Wg, int64_t ldwg, int Rg,
+                       float* out_rows, int64_t ld_out, void* out_k, int64_t ld_k, int k_cols,
+                       const float* Pd, int64_t ldpd, int Rd, const float* Pu, int64_t ldpu, const float* Pg,
+                       int64_t ldpg, float* dA_down, float* dB_up, float* dB_gate, float s_down, float s_up,
+                       float s_gate, int accumulate, void* ws, int64_t ws_bytes, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Cross entropy.  Replaces cross_entropy_loss.py:35-111 / :114-199 (+ host logsumexp :366-370) and

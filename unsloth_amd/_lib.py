@@ -147,6 +147,11 @@ SIGNATURES = {
     "uamd_glu_bwd_xa_ws": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64]
                            + [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int] * 2
                            + [c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    "uamd_glu_tn_workspace": (c_int64, [c_int, c_int]),
+    "uamd_glu_bwd_tn_ws": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64]
+                           + [c_void_p, c_int64, c_int] * 2 + [c_void_p, c_int64, c_void_p, c_int64, c_int]
+                           + [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64]
+                           + [c_void_p] * 3 + [c_float] * 3 + [c_int, c_void_p, c_int64, c_int, c_void_p]),
     "uamd_adamw_shard": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + [ctypes.c_double] * 8
                          + [c_int, c_void_p]),
     "uamd_adamw8_flat": (c_int, [c_void_p] * 8 + [c_int64] + [ctypes.c_double] * 8 + [c_int, c_void_p]),

@@ -690,6 +690,365 @@ extern "C" int uamd_glu_bwd_xa_ws(int act, void* DW, void* e, void* g, int M, in
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The SwiGLU backward that ALSO forms the three wide LoRA weight gradients of the MLP (fast_lora.py:172-189):
+//     dA_down = s (dY B_down)^T h        dB_up = s df^T (X A_up^T)        dB_gate = s de^T (X A_gate^T)
+// Each is a contraction over TOKENS of an [M, I] activation that uamd_glu_bwd_xa has in registers once and that
+// uamd_lora_tn reads again afterwards (and h is written to DW only to be read by that launch): 940 MB of the group's 2.3 GB
+// per layer at 8192 x 14336. glu_xa_kernel's workgroups walk ALONG rows and cannot hold [16 ranks x row width] accumulators,
+// so this is its tile pipeline turned by 90 degrees: a workgroup owns a strip of GX_TK columns and a chunk of rows, walks
+// DOWN the chunk in 16-row tiles (register prefetch one tile ahead, the same two alternating register sets), stores df / de
+// in place (h is never stored: DW is read-only), stages the 16-bit h / df / de tiles in LDS, and
+//   * contracts them over the tile's rows with P^T (P = dY B_down, X A_up^T, X A_gate^T: fp32 [M, r], rounded to the
+//     activation dtype and transposed into LDS per tile; rows >= M and ranks >= R zeroed) on the matrix cores, the tile
+//     coming through the transposing read ds_read_b64_tr_b16 exactly as in lora_tn_kernel: 3 x 2 accumulators of
+//     [16 ranks x 16 columns] per wave stay in registers for the whole chunk and leave as ONE fp32 partial
+//     part_G[chunk][z][16][strips x GX_TK];
+//   * forms the strip's share of df B_up and de B_gate per tile (the factor fragments of a strip are loaded once): wave w
+//     = product w & 1, k-steps 2 (w >> 1) .. + 1; the four partial [16 x 16] tiles of a product are summed in wave order
+//     through LDS one tile LATER (behind the next tile's barrier: no second barrier per tile) and leave as
+//     part_rows[strip][m][up 16 | gate 16].
+// glu_tn_reduce_kernel then sums part_rows over strips (ascending) into the GluXaOut contract of uamd_glu_bwd_xa (fp32
+// [M, r_up + r_gate] + the 16-bit rank block) and part_G over chunks (ascending), times the LoRA scale, into the gradients
+// (fresh, or += into a given fp32 target). No atomics, no counters, no fences; both sums in fixed order.
+// blockIdx = chunk * strips + strip: the strips of a row chunk run together and sweep whole rows (the note on the grid's
+// memory sweep in front of launch_xa).
+namespace {
+typedef __attribute__((ext_vector_type(4))) __bf16 glu_bf16x4_t;
+typedef __attribute__((ext_vector_type(4))) _Float16 glu_f16x4_t;
+typedef __attribute__((ext_vector_type(4))) short glu_s16x4_t;
+typedef __attribute__((address_space(3))) glu_s16x4_t glu_lds_s16x4;
+template <typename T> struct GluMfma16;
+template <> struct GluMfma16<bf16_t> {
+    typedef glu_bf16x4_t frag;
+    static __device__ __forceinline__ glu_f32x4_t run(frag a, frag b, glu_f32x4_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct GluMfma16<f16_t> {
+    typedef glu_f16x4_t frag;
+    static __device__ __forceinline__ glu_f32x4_t run(frag a, frag b, glu_f32x4_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
+    }
+};
+
+#ifndef UAMD_GT_RPC_MAX
+#define UAMD_GT_RPC_MAX 512       // most rows of one chunk (lora_tn's rows_per_wave: fewer, longer chunks = fewer fp32 partials)
+#endif
+#ifndef UAMD_GT_MIN_WGS
+#define UAMD_GT_MIN_WGS 512       // ... as long as the launch keeps this many workgroups (two 8-wave workgroups per CU)
+#endif
+constexpr int GT_PT = 4 * 16 * 16 * 2;                 // P^T images of a tile: [3 products + 1 unused][16 ranks][16 rows], 16-bit
+constexpr int GT_RED = 8 * 16 * 16 * 4;                // the eight waves' partial row products of a tile, fp32
+constexpr int GT_BUF = 3 * GX_TILE + GT_PT + GT_RED;   // one of the two buffers
+constexpr int GT_LDS = 2 * GT_BUF;                     // 71,168 B: two workgroups per CU
+
+struct GluTnArgs {
+    const void* DW;
+    void* E;
+    void* G;
+    int M, K;
+    int64_t ld;
+    const void* W[2];            // B_up^T, B_gate^T: [R, K], K contiguous
+    int64_t ldw[2];
+    int Rw[2];
+    const float* P[3];           // z = 0: dY B_down (with h), 1: X A_up^T (with df), 2: X A_gate^T (with de); fp32 [M, >= R]
+    int64_t ldp[3];
+    int Rp[3];
+    int rpc, S, n_strips;        // rows per chunk, chunks, strips
+    float* part_rows;            // [n_strips][M][32]
+    float* part_G;               // [S][3][16][n_strips * GX_TK]
+    // the reduce
+    float* out_rows;             // fp32 [M, ld_out]: columns [0, Ru) = df B_up, [Ru, Ru + Rg) = de B_gate
+    int64_t ld_out;
+    void* out_k;                 // the same sums in the activation dtype, columns [Ru + Rg, k_cols) zero; may be null
+    int64_t ld_k;
+    int k_cols;
+    float* grad[3];              // dA_down [Rd, K], dB_up [K, Ru], dB_gate [K, Rg]
+    float scale[3];
+    int accumulate;              // bit z: grad[z] += instead of =
+};
+
+template <typename T>
+__global__ void __launch_bounds__(512, 4) glu_tn_kernel(GluTnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    typedef typename GluMfma<T>::frag frag_t;
+    typedef typename GluMfma16<T>::frag frag4_t;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int chunk = (int)(blockIdx.x / (unsigned)a.n_strips);
+    const int strip = (int)(blockIdx.x - (unsigned)chunk * (unsigned)a.n_strips);
+    const int M = a.M, K = a.K;
+    const int64_t ld = a.ld;
+    const T* DW = (const T*)a.DW;
+    T* E = (T*)a.E;
+    T* G = (T*)a.G;
+    const int m_base = chunk * a.rpc;
+    const int m_end = min(m_base + a.rpc, M);
+    const int ntiles = (m_end - m_base + 15) >> 4;
+    // streaming side: thread = row (tid >> 5) of the tile, 8 columns at 8 (tid & 31) of the strip
+    const int srow = tid >> 5, scol = (tid & 31) * 8;
+    const int c = strip * GX_TK + scol;
+    const bool col_ok = c + 8 <= K;                                      // columns past K: read column 0, never stored, zero in LDS
+    const int cc = col_ok ? c : 0;
+    // P side: thread = product (tid >> 7; 3 = the unused image: p_d once more), row ((tid & 127) >> 3) of the tile, ranks 2 (tid & 7) ..
+    const int pz = tid >> 7, prow = (tid & 127) >> 3, prank = (tid & 7) * 2;
+    const int pzz = pz < 3 ? pz : 0;
+    const float* Pz = pzz == 1 ? a.P[1] : pzz == 2 ? a.P[2] : a.P[0];
+    const int64_t ldp = pzz == 1 ? a.ldp[1] : pzz == 2 ? a.ldp[2] : a.ldp[0];
+    const int Rp = pzz == 1 ? a.Rp[1] : pzz == 2 ? a.Rp[2] : a.Rp[0];
+    const bool rank_ok = prank + 2 <= Rp;                                // (ranks are multiples of 8: a pair is in or out)
+    const int pcol = rank_ok ? prank : 0;
+    // the strip's factor fragments, once: product wave & 1, k-steps 2 (wave >> 1) + q; rank rows past R re-read the last valid row
+    // (their sums are never reduced), columns past K are zero
+    const int rp = wave & 1, ks0 = (wave >> 1) * 2;
+    uint4 wf[2];
+    {
+        const T* W = (const T*)a.W[rp];
+        const int64_t wo = (int64_t)min(l15, a.Rw[rp] - 1) * a.ldw[rp];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int kc = strip * GX_TK + (ks0 + q) * 32 + l4 * 8;
+            wf[q] = kc + 8 <= K ? *reinterpret_cast<const uint4*>(W + wo + kc) : make_uint4(0, 0, 0, 0);
+        }
+    }
+    glu_f32x4_t acc[3][2];
+#pragma unroll
+    for (int z = 0; z < 3; ++z)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[z][b] = glu_f32x4_t{0.f, 0.f, 0.f, 0.f};
+    // per-lane LDS offsets inside a buffer
+    const int st_off = srow * GX_LD + scol * 2;                                          // this thread's vector in a tile
+    const int pt_off = 3 * GX_TILE + ((pz * 16 + prank) * 16 + prow) * 2;                // P^T[pz][prank][prow] (+ 32 B: the next rank)
+    const int pa_off = 3 * GX_TILE + (l15 * 16 + 4 * l4) * 2;                            // A operand: P^T[z][l15][4 l4 ..] (+ 512 z)
+    const int tr_off = (4 * l4 + (l15 >> 2)) * GX_LD + (wave * 32 + (l15 & 3) * 4) * 2;  // B operand: rows 4 l4 .., block 2 wave (+ 32 B)
+    const int ra_off = l15 * GX_LD + (ks0 * 32 + l4 * 8) * 2;                            // row products' A operand (+ 64 B per k-step)
+    const int rw_off = 3 * GX_TILE + GT_PT + ((wave * 16 + 4 * l4) * 16 + l15) * 4;      // this wave's partial [16 x 16] (+ 64 B per row)
+    // emitting a tile's row products: thread = row (tid >> 5), product (tid >> 4) & 1, rank tid & 15
+    const int er_off = 3 * GX_TILE + GT_PT + ((((tid >> 4) & 1) * 16 + srow) * 16 + (tid & 15)) * 4;   // wave = product + 2 q
+    float* prow_out = a.part_rows + ((int64_t)strip * M) * 32 + (tid & 31);
+
+    struct Regs {
+        Vec16<T> e, g, dw;
+        float2 p;
+    };
+    Regs A, B;
+    auto load_tile = [&](int it, Regs& r) {
+        const int m0 = m_base + it * 16;
+        const int64_t o = (int64_t)min(m0 + srow, M - 1) * ld + cc;      // clamped rows are computed and never stored
+        r.e = ld16_nt(E + o);
+        r.g = ld16_nt(G + o);
+        r.dw = ld16_nt(DW + o);
+        r.p = *reinterpret_cast<const float2*>(Pz + (int64_t)min(m0 + prow, M - 1) * ldp + pcol);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto emit_rows = [&](int it) {                                       // the row products of tile `it`, summed in wave order
+        const float* q = reinterpret_cast<const float*>(smem + (it & 1) * GT_BUF + er_off);
+        const float v = ((q[0] + q[2 * 256]) + q[4 * 256]) + q[6 * 256];
+        const int m = m_base + it * 16 + srow;
+        if (m < M) prow_out[(int64_t)m * 32] = v;
+    };
+    auto tile = [&](int it, Regs& r, Regs& rn, int it_next, auto emit_prev) {
+        unsigned char* buf = smem + (it & 1) * GT_BUF;
+        load_tile(it_next, rn);
+        const int m0 = m_base + it * 16;
+        Vec16<T> h, v0, v1;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) bwd_one<T, ACT_SWIGLU>(r.dw.e[j], r.e.e[j], r.g.e[j], h.e[j], v0.e[j], v1.e[j]);
+        if (col_ok && m0 + srow < M) {
+            const int64_t o = (int64_t)(m0 + srow) * ld + c;
+            st16_nt(E + o, v0);
+            st16_nt(G + o, v1);
+        }
+        if (!col_ok) {                                                   // columns past K contribute nothing
+            h.raw = make_uint4(0, 0, 0, 0);
+            v0.raw = make_uint4(0, 0, 0, 0);
+            v1.raw = make_uint4(0, 0, 0, 0);
+        }
+        *reinterpret_cast<uint4*>(buf + st_off) = h.raw;
+        *reinterpret_cast<uint4*>(buf + st_off + GX_TILE) = v0.raw;
+        *reinterpret_cast<uint4*>(buf + st_off + 2 * GX_TILE) = v1.raw;
+        const bool p_ok = rank_ok && m0 + prow < M;                      // rows >= M and ranks >= R: zero
+        *reinterpret_cast<T*>(buf + pt_off) = from_f32<T>(p_ok ? r.p.x : 0.f);
+        *reinterpret_cast<T*>(buf + pt_off + 32) = from_f32<T>(p_ok ? r.p.y : 0.f);
+        // the tile is complete (and the other buffer's tiles are free again). NOT __syncthreads(): see glu_xa_kernel
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        // (every wave has written the previous tile's partial row products before it arrived at this barrier)
+        if constexpr (decltype(emit_prev)::value) emit_rows(it - 1);
+        // ---- token contractions: G_z[rank][col] += sum_m P_z[m][rank] Z[m][col], columns 32 wave .. + 31 of the strip
+        union { uint2 r; frag4_t f; } pa[3];
+#pragma unroll
+        for (int z = 0; z < 3; ++z) pa[z].r = *reinterpret_cast<const uint2*>(buf + pa_off + z * 512);
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int z = 0; z < 3; ++z) {
+                union { glu_s16x4_t h; frag4_t f; } zb;
+                zb.h = __builtin_amdgcn_ds_read_tr16_b64_v4i16((glu_lds_s16x4*)(buf + z * GX_TILE + tr_off + b * 32));
+                acc[z][b] = GluMfma16<T>::run(pa[z].f, zb.f, acc[z][b]);
+            }
+        // ---- row products of this strip: [16 rows x 16 ranks] of product rp over this wave's two k-steps
+        glu_f32x4_t racc = glu_f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            union { uint4 r; frag_t f; } x, w;
+            x.r = *reinterpret_cast<const uint4*>(buf + (1 + rp) * GX_TILE + ra_off + q * 64);
+            w.r = wf[q];
+            racc = GluMfma<T>::run(x.f, w.f, racc);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<float*>(buf + rw_off + i * 64) = racc[i];
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    // the first tile apart (it has no previous tile to emit), then pairs of tiles in a branch-free body and an odd last tile
+    // after the loop; the last tile is simply fetched once more (glu_xa_kernel's loop)
+    load_tile(0, A);
+    tile(0, A, B, ntiles > 1 ? 1 : 0, no);
+    int it = 1;
+    for (; it + 1 < ntiles; it += 2) {
+        tile(it, B, A, it + 1, yes);
+        tile(it + 1, A, B, it + 2 < ntiles ? it + 2 : it + 1, yes);
+    }
+    if (it < ntiles) tile(it, B, A, it, yes);
+    __syncthreads();
+    emit_rows(ntiles - 1);
+    // ---- the chunk's partial gradients. acc[z][b][i] = G_z[rank 4 l4 + i][column 32 wave + 16 b + l15 of the strip]
+    const int64_t kpad = (int64_t)a.n_strips * GX_TK;
+    float* pg = a.part_G + ((int64_t)chunk * 3 * 16 + 4 * l4) * kpad + strip * GX_TK + wave * 32 + l15;
+#pragma unroll
+    for (int z = 0; z < 3; ++z)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) pg[((int64_t)z * 16 + i) * kpad + b * 16] = acc[z][b][i];
+}
+
+// blocks [0, nb_rows): out_rows / out_k = sum over strips of part_rows; the rest: grad[z] (+)= scale[z] * sum over chunks of part_G
+template <typename T>
+__global__ void __launch_bounds__(256) glu_tn_reduce_kernel(GluTnArgs a, int nb_rows) {
+    const int M = a.M, K = a.K;
+    const int Ru = a.Rw[0], Rg = a.Rw[1];
+    if ((int)blockIdx.x < nb_rows) {
+        const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;          // over M x 32
+        if (idx >= (int64_t)M * 32) return;
+        const int64_t m = idx >> 5;
+        const int cl = (int)(idx & 31), p = cl >> 4, rank = cl & 15;
+        const float* q = a.part_rows + idx;
+        const int64_t sstride = (int64_t)M * 32;
+        // (a plain loop's order, 8 loads in flight per round: lora_tn_reduce_kernel)
+        float v = 0.f;
+        int s = 0;
+        for (; s + 8 <= a.n_strips; s += 8) {
+            float t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) t[u] = q[(int64_t)(s + u) * sstride];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v += t[u];
+        }
+        for (; s < a.n_strips; ++s) v += q[(int64_t)s * sstride];
+        if (rank < (p ? Rg : Ru)) {
+            const int col = (p ? Ru : 0) + rank;
+            a.out_rows[m * a.ld_out + col] = v;
+            if (a.out_k != nullptr) ((T*)a.out_k)[m * a.ld_k + col] = from_f32<T>(v);
+        }
+        if (a.out_k != nullptr)
+            for (int cz = Ru + Rg + cl; cz < a.k_cols; cz += 32) ((T*)a.out_k)[m * a.ld_k + cz] = from_f32<T>(0.f);
+        return;
+    }
+    const int64_t idx = (int64_t)(blockIdx.x - nb_rows) * 256 + threadIdx.x;  // over 3 x 16 x K
+    if (idx >= (int64_t)48 * K) return;
+    const int zr = (int)(idx / K), n = (int)(idx - (int64_t)zr * K);
+    const int z = zr >> 4, r = zr & 15;
+    const int R = a.Rp[z];
+    if (r >= R) return;
+    const int64_t kpad = (int64_t)a.n_strips * GX_TK;
+    const float* q = a.part_G + (int64_t)zr * kpad + n;
+    const int64_t sstride = 48 * kpad;
+    float v = 0.f;
+    int s = 0;
+    for (; s + 8 <= a.S; s += 8) {
+        float t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t[u] = q[(int64_t)(s + u) * sstride];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v += t[u];
+    }
+    for (; s < a.S; ++s) v += q[(int64_t)s * sstride];
+    v *= a.scale[z];
+    float* o = z == 0 ? a.grad[0] + (int64_t)r * K + n : a.grad[z] + (int64_t)n * R + r;
+    *o = ((a.accumulate >> z) & 1) ? *o + v : v;
+}
+
+// rows per chunk: as many as keep UAMD_GT_MIN_WGS workgroups in the launch
+inline void tn_plan(int M, int K, int& rpc, int& S, int& n_strips) {
+    n_strips = (K + GX_TK - 1) / GX_TK;
+    rpc = UAMD_GT_RPC_MAX;
+    while (rpc > 128 && (int64_t)n_strips * ((M + rpc - 1) / rpc) < UAMD_GT_MIN_WGS) rpc >>= 1;
+    S = (M + rpc - 1) / rpc;
+}
+inline int64_t tn_rows_floats(int M, int n_strips) { return (int64_t)n_strips * M * 32; }
+inline int64_t tn_grad_floats(int S, int n_strips) { return (int64_t)S * 48 * n_strips * GX_TK; }
+
+template <typename T>
+int launch_tn(GluTnArgs& a, hipStream_t st) {
+    const int64_t blocks = (int64_t)a.S * a.n_strips;
+    const int64_t nb_rows = ((int64_t)a.M * 32 + 255) / 256, nb_grad = ((int64_t)48 * a.K + 255) / 256;
+    if (blocks > 0x7fffffffLL || nb_rows + nb_grad > 0x7fffffffLL) return UAMD_ERR_ARG;
+    if (int rc = uamd_launch_lds<&glu_tn_kernel<T>>(dim3((unsigned)blocks), dim3(512), GT_LDS, st, a)) return rc;
+    hipLaunchKernelGGL((glu_tn_reduce_kernel<T>), dim3((unsigned)(nb_rows + nb_grad)), dim3(256), 0, st, a, (int)nb_rows);
+    return uamd_launch_status();
+}
+
+}  // namespace
+
+// Bytes of workspace uamd_glu_bwd_tn_ws needs for an [M, K] launch; -1 for arguments it would reject.
+extern "C" int64_t uamd_glu_tn_workspace(int M, int K) {
+    if (M < 0 || K < 8 || (K & 7)) return -1;
+    int rpc, S, n_strips;
+    tn_plan(M > 0 ? M : 1, K, rpc, S, n_strips);
+    return 4 * (tn_rows_floats(M, n_strips) + tn_grad_floats(S, n_strips));
+}
+
+extern "C" int uamd_glu_bwd_tn_ws(const void* DW, void* e, void* g, int M, int K, int64_t ld,
+                                  const void* Wu, int64_t ldwu, int Ru, const void* Wg, int64_t ldwg, int Rg,
+                                  float* out_rows, int64_t ld_out, void* out_k, int64_t ld_k, int k_cols,
+                                  const float* Pd, int64_t ldpd, int Rd, const float* Pu, int64_t ldpu, const float* Pg,
+                                  int64_t ldpg, float* dA_down, float* dB_up, float* dB_gate, float s_down, float s_up,
+                                  float s_gate, int accumulate, void* ws, int64_t ws_bytes, int dtype, void* stream) {
+    if (M < 0 || K < 8 || !DW || !e || !g || !Wu || !Wg || !out_rows || !Pd || !Pu || !Pg || !dA_down || !dB_up || !dB_gate || !ws)
+        return UAMD_ERR_ARG;
+    for (int R : {Ru, Rg, Rd})
+        if (R != 8 && R != 16) return UAMD_ERR_ARG;                          // whole 8-rank groups of one 16-rank tile
+    if (ld < K || ldwu < K || ldwg < K || ld_out < Ru + Rg || ldpd < Rd || ldpu < Ru || ldpg < Rg) return UAMD_ERR_ARG;
+    if (out_k && (k_cols < Ru + Rg || ld_k < k_cols)) return UAMD_ERR_ARG;
+    if (M == 0) return UAMD_OK;
+    if ((K & 7) || (ld & 7) || (ldwu & 7) || (ldwg & 7) || !aligned16(DW) || !aligned16(e) || !aligned16(g) || !aligned16(Wu) ||
+        !aligned16(Wg))
+        return UAMD_ERR_ALIGN;
+    if ((ldpd & 1) || (ldpu & 1) || (ldpg & 1) || ((uintptr_t)Pd & 7) || ((uintptr_t)Pu & 7) || ((uintptr_t)Pg & 7) ||
+        ((uintptr_t)ws & 15))
+        return UAMD_ERR_ALIGN;
+    GluTnArgs a;
+    a.DW = DW; a.E = e; a.G = g; a.M = M; a.K = K; a.ld = ld;
+    a.W[0] = Wu; a.W[1] = Wg; a.ldw[0] = ldwu; a.ldw[1] = ldwg; a.Rw[0] = Ru; a.Rw[1] = Rg;
+    a.P[0] = Pd; a.P[1] = Pu; a.P[2] = Pg; a.ldp[0] = ldpd; a.ldp[1] = ldpu; a.ldp[2] = ldpg;
+    a.Rp[0] = Rd; a.Rp[1] = Ru; a.Rp[2] = Rg;
+    tn_plan(M, K, a.rpc, a.S, a.n_strips);
+    const int64_t rows_f = tn_rows_floats(M, a.n_strips);
+    if (ws_bytes < 4 * (rows_f + tn_grad_floats(a.S, a.n_strips))) return UAMD_ERR_ARG;
+    a.part_rows = (float*)ws;
+    a.part_G = (float*)ws + rows_f;
+    a.out_rows = out_rows; a.ld_out = ld_out; a.out_k = out_k; a.ld_k = ld_k; a.k_cols = out_k ? k_cols : 0;
+    a.grad[0] = dA_down; a.grad[1] = dB_up; a.grad[2] = dB_gate;
+    a.scale[0] = s_down; a.scale[1] = s_up; a.scale[2] = s_gate;
+    a.accumulate = accumulate;
+    UAMD_DISPATCH_HALF(dtype, return launch_tn<T>(a, (hipStream_t)stream))
+    return UAMD_ERR_DTYPE;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // QuickGELU, y = x * sigmoid(1.702 x): the activation of Qwen2-VL's vision MLP (fc1 -> act -> fc2; BASELINE config 4). The
 // reference leaves it to the zoo compiler's fused graph (unsloth/models/vision.py:881-1990); here one streaming kernel each way,
 // fp32 arithmetic, one rounding: forward y from x; backward dx = dy * (s + 1.702 x s (1 - s)), s = sigmoid(1.702 x), written IN

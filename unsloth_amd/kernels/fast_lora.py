@@ -13,15 +13,16 @@ What changes is the launch structure (kernels/utils.py): gate+up and q+k+v are o
 launch each, the LoRA term rides in that launch as extra K tiles (rank block), every dX is one
 transposing-dequant launch + one GEMM (q/k/v: ONE K-concatenated GEMM), and all rank-r gradient
 products of a block are ONE `uamd_lora_tn` launch (csrc/lora_side.hip) that can add straight into
-the data-parallel gradient arena. Each block also exists as a pair of plain functions
-(`mlp_forward` / `mlp_backward`, ...) for the whole-layer Function with selective recompute
-(models/fast_layer.py).
+the data-parallel gradient arena -- in the MLP block the three that contract h, df, de over tokens
+are formed by the activation backward itself (utils.glu_bwd_tn) and the launch carries the other
+three. Each block also exists as a pair of plain functions (`mlp_forward` / `mlp_backward`, ...)
+for the whole-layer Function with selective recompute (models/fast_layer.py).
 """
 import os
 
 import torch
 
-from .utils import _same_rows, alloc_rows, glu_bwd_terms, glu_fwd_xa
+from .utils import _same_rows, alloc_rows, glu_bwd_terms, glu_bwd_tn, glu_fwd_xa, glu_tn_takes
 from .utils import (
     GRAD_SINKS,
     grad_sink,
@@ -89,6 +90,28 @@ def _lora_grads_fused(items):
     return [(None, None) if k is None else (outs[k], outs[k + 1]) for k in slots]
 
 
+def _mlp_grads_tn(act, DW, e, g, dY, X2, xas, p_d, gate, up, down):
+    """mlp_backward through glu_bwd_tn: (df, de, [p_u, p_g], (d_gateA, d_gateB, d_upA, d_upB, d_downA, d_downB)), the grad
+    sinks served for all six parameters as in _lora_grads_fused; None when glu_bwd_tn does not take the shape."""
+    xa_g, xa_u, xa_d = xas
+    wide = [down[2], up[3], gate[3]]                 # dA_down, dB_up, dB_gate: formed by the activation pass
+    narrow = [down[3], up[2], gate[2]]               # dB_down, dA_up, dA_gate: one lora_tn launch
+    sinks = [(grad_sink(prm), prm) for prm in wide + narrow]
+    targets = [sk.grad_view(prm) if sk is not None else None for sk, prm in sinks]
+    res = glu_bwd_tn(act, DW, e, g, up, gate, down, p_d, xa_u, xa_g, targets[:3])
+    if res is None:
+        return None
+    df, de, (p_u, p_g), outs = res
+    outs = outs + lora_tn([(xa_d, dY, down[2].shape[0], True, down[4]), (p_u, X2, up[2].shape[0], False, up[4]),
+                           (p_g, X2, gate[2].shape[0], False, gate[4])],
+                          targets[3:] if any(t is not None for t in targets[3:]) else None)
+    for sk, prm in sinks:
+        if sk is not None:
+            sk.ready(prm)                            # the gradient is in the arena: autograd gets None for it
+    d_downA, d_upB, d_gateB, d_downB, d_upA, d_gateA = [None if sk[0] is not None else o for o, sk in zip(outs, sinks)]
+    return df, de, [p_u, p_g], (d_gateA, d_gateB, d_upA, d_upB, d_downA, d_downB)
+
+
 # ---- the blocks as plain functions (forward returns what the backward needs; nothing here touches autograd), used by
 #      the autograd.Function wrappers below AND by the whole-layer Function of models/fast_layer.py, which decides
 #      per tensor whether to keep it or to recompute it in the backward.
@@ -153,6 +176,14 @@ def mlp_backward(dY, X, e, g, xas, gate, up, down, act_bwd, inplace=True):
     DW = lora_linear_dx([dY], [down], terms=[p_d],
                         out=alloc_rows(e.shape[0], e.shape[1], e.dtype, e.device, ld=e.stride(0)) if padded else None)
     act = _ACT_NAMES.get(act_bwd)
+    if act is not None and DW.dim() == 2 and glu_tn_takes(act, DW, e, g, up, gate, down) and lora_tn_supported([dY, X2]):
+        # activation backward + df @ B_up, de @ B_gate + the three gradients that contract h, df, de over tokens, in one pass
+        # (h is never written); what is left -- dB_down, and dA_up / dA_gate, which need the finished p_u / p_g -- is ONE launch
+        tn = _mlp_grads_tn(act, DW, e, g, dY, X2, xas, p_d, gate, up, down)
+        if tn is not None:
+            df, de, (p_u, p_g), grads = tn
+            dX = lora_linear_dx([df, de], [up, gate], out=X2 if (inplace and X2.is_contiguous()) else None, terms=[p_u, p_g])
+            return dX.view(shape), grads
     fused = glu_bwd_terms(act, DW, e, g, up, gate) if (act is not None and DW.dim() == 2) else None
     if fused is not None:                                          # activation backward + df @ B_up, de @ B_gate in one pass
         h, df, de, (p_u, p_g) = fused

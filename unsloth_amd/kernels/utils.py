@@ -1113,6 +1113,81 @@ def glu_bwd_terms(act, DW, e, g, up, gate):
     return DW, e, g, [pu, pg]
 
 
+# The SwiGLU backward that also forms the MLP's three wide LoRA gradients (csrc/glu.hip glu_tn_kernel): glu_bwd_terms writes h
+# only for uamd_lora_tn to read it, df and de back; here the contraction over tokens happens while the tiles are on chip.
+# GLU_TN = False switches fast_lora.mlp_backward back to glu_bwd_terms + the six-problem lora_tn launch.
+GLU_TN = True
+_GLU_TN_WS = {}     # (device index, stream) -> the fp32 partials of glu_tn_kernel (uamd_glu_tn_workspace bytes)
+
+
+def glu_tn_takes(act, DW, e, g, up, gate, down):
+    """Does glu_bwd_tn take this backward? SwiGLU on a shape the fused activation kernels take (GLU_FUSED, GLU_FUSED_MIN_ROWS),
+    all three adapters present, every rank 8 or 16."""
+    if not GLU_TN or act != "swiglu" or any(p[2] is None or p[3] is None for p in (up, gate, down)):
+        return False
+    ranks = [p[2].shape[0] for p in (up, gate, down)]
+    return (all(r <= 16 and r % 8 == 0 for r in ranks) and _glu_fusable(e.dtype, [DW, e, g], ranks, True)
+            and lora_tn_supported([DW, e, g]))
+
+
+def _tn_factor(P, R):
+    """P (fp32 [M, >= R]) as glu_tn_kernel fetches it: unit column stride, rows of whole float2s from an 8-byte aligned start"""
+    if P.dtype == torch.float32 and P.stride(1) == 1 and P.stride(0) % 2 == 0 and P.data_ptr() % 8 == 0:
+        return P
+    return P[:, :R].float().contiguous()
+
+
+def glu_bwd_tn(act, DW, e, g, up, gate, down, p_d, xa_u, xa_g, targets=None):
+    """The in-place SwiGLU backward (e <- df, g <- de; DW is left as it is: h is never written) AND, in the same pass,
+        p_up = df @ B_up, p_gate = de @ B_gate                 (fp32 [M, r] + the dX GEMM's rank block, as glu_bwd_terms)
+        dA_down = s (p_d^T h), dB_up = s (df^T xa_u), dB_gate = s (de^T xa_g)      (fp32, as lora_tn returns them)
+    with p_d = dY @ B_down, xa_u = X @ A_up^T, xa_g = X @ A_gate^T (fp32 [M, >= r]). `targets`: three contiguous fp32 tensors
+    (or None each) to ACCUMULATE dA_down / dB_up / dB_gate into. Returns (df, de, [p_up, p_gate], [dA_down, dB_up, dB_gate]),
+    or None -- nothing launched, nothing touched -- when the shape is not taken (glu_tn_takes)."""
+    if not glu_tn_takes(act, DW, e, g, up, gate, down):
+        return None
+    M, K = e.shape
+    dtype, dev = e.dtype, e.device
+    ru, rg, rd = up[2].shape[0], gate[2].shape[0], down[2].shape[0]
+    if any(P.dim() != 2 or P.shape[0] != M or P.shape[1] < r for P, r in ((p_d, rd), (xa_u, ru), (xa_g, rg))):
+        raise ValueError("glu_bwd_tn: p_d / xa_u / xa_g must be fp32 [M, >= rank]")
+    Kin = [(p[1].shape[1] if p[1] is not None else p[0].shape[1]) for p in (up, gate)]
+    want_k = all(_use_gemm256(M, 64, [k]) for k in Kin)
+    But, Bgt = cast_lora_t(up[3], dtype), cast_lora_t(gate[3], dtype)                # [r, K]
+    p_d, xa_u, xa_g = _tn_factor(p_d, rd), _tn_factor(xa_u, ru), _tn_factor(xa_g, rg)
+    shapes = [(rd, K), (K, ru), (K, rg)]
+    targets = list(targets) if targets is not None else [None] * 3
+    grads, acc = [], 0
+    for i, (tgt, shp) in enumerate(zip(targets, shapes)):
+        if tgt is not None:
+            assert tgt.dtype == torch.float32 and tgt.is_contiguous() and tgt.device == dev and tuple(tgt.shape) == shp
+            acc |= 1 << i
+        grads.append(tgt if tgt is not None else torch.empty(shp, dtype=torch.float32, device=dev))
+    shared = torch.empty((M, ru + rg), dtype=torch.float32, device=dev)
+    xk = torch.empty((M, _rank_width(ru + rg)), dtype=dtype, device=dev) if want_k else None
+    with _lib.device_ctx(e):
+        need = int(_lib.lib().uamd_glu_tn_workspace(M, K))
+        key = (dev.index, int(torch.cuda.current_stream(dev).cuda_stream))
+        ws = _GLU_TN_WS.get(key)
+        if need >= 0 and (ws is None or ws.numel() < need):
+            ws = _GLU_TN_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+        rc = -2 if need < 0 else _lib.lib().uamd_glu_bwd_tn_ws(
+            _lib.ptr(DW), _lib.ptr(e), _lib.ptr(g), M, K, e.stride(0),
+            _lib.ptr(But), But.stride(0), ru, _lib.ptr(Bgt), Bgt.stride(0), rg,
+            _lib.ptr(shared), shared.stride(0), _lib.ptr(xk), xk.stride(0) if want_k else 0, xk.shape[1] if want_k else 0,
+            _lib.ptr(p_d), p_d.stride(0), rd, _lib.ptr(xa_u), xa_u.stride(0), _lib.ptr(xa_g), xa_g.stride(0),
+            _lib.ptr(grads[0]), _lib.ptr(grads[1]), _lib.ptr(grads[2]), float(down[4]), float(up[4]), float(gate[4]), acc,
+            _lib.ptr(ws), ws.numel(), _lib.dtype_code(dtype), _lib.stream_of(e))
+    if rc in _lib._ERR:         # one of the library's own codes: rejected before any launch -- "not supported", not "failed"
+        return None
+    _lib.check(rc, "uamd_glu_bwd_tn_ws")
+    pu, pg = shared[:, :ru], shared[:, ru:]
+    if want_k:
+        pu._uamd_xk = (xk, 0)
+        pg._uamd_xk = (xk, ru)
+    return e, g, [pu, pg], grads
+
+
 def dense_dw(dY, X, out=None, accumulate=False):
     """dW[out, in] (+)= dY[T, out]^T @ X[T, in]: the weight gradient of a trainable dense projection (full fine-tuning;
     torch.nn.Linear's `grad_output.t().mm(input)`). `dY` may be several projections' gradients side by side in one buffer
