@@ -23,6 +23,7 @@
 //   * Bank conflicts: K rows are read 16 bytes per lane down a column -> 16-byte slot ^= row & 15; V rows are
 //     read by the transposing 8-byte reads, 4 rows x 64 B per 32 lanes -> slot ^= (row & 3) << 2. Both swizzles
 //     are applied on the per-lane DMA SOURCE address (the DMA destination is lane-linear).
+#include <initializer_list>
 #include <mutex>
 #include <type_traits>
 #include <utility>
@@ -212,16 +213,9 @@ __device__ __forceinline__ void store_rows_x4(T* row, const f32x16_t (&acc)[4], 
             uint32_t ay = pack_pair2<T>(acc[dt][qd * 4 + 2] * mul, acc[dt][qd * 4 + 3] * mul);
             uint32_t bx = pack_pair2<T>(acc[dt][qd * 4 + 4] * mul, acc[dt][qd * 4 + 5] * mul);
             uint32_t by = pack_pair2<T>(acc[dt][qd * 4 + 6] * mul, acc[dt][qd * 4 + 7] * mul);
-#ifdef UAMD_ATTN_NARROW_STORE
-            if (live) {
-                *reinterpret_cast<uint2*>(row + dt * 32 + qd * 8 + lh * 4) = make_uint2(ax, ay);
-                *reinterpret_cast<uint2*>(row + dt * 32 + qd * 8 + 8 + lh * 4) = make_uint2(bx, by);
-            }
-#else
             const auto rx = __builtin_amdgcn_permlane32_swap(ax, bx, false, false);
             const auto ry = __builtin_amdgcn_permlane32_swap(ay, by, false, false);
             if (live && dt * 32 + qd * 8 + lh * 8 < D) *reinterpret_cast<uint4*>(row + dt * 32 + qd * 8 + lh * 8) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
-#endif
         }
 }
 
@@ -242,6 +236,178 @@ __device__ __forceinline__ int slot_in(int s, int D) { return s * 8 < D ? s : 0;
 
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }     // one v_max3_f32
 
+// ---- what the kernels below share: one tiling (8 waves x 32 query rows against 64-key tiles), one LDS image, one band logic.
+
+__device__ __forceinline__ void zero(f32x16_t& a) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a[r] = 0.f;
+}
+
+// register r of a 32 x 32 MFMA C tile -> its row (lane half lh; the column is the lane's l31)
+__device__ __forceinline__ int c_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
+
+// the dQ and dK / dV kernels' swizzle of a 256-byte row's 16-byte slots (see attn_bwd_dq_kernel)
+__device__ __forceinline__ int swz_c(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
+
+// Per-lane LDS byte addresses inside a tile of 256-byte rows; k-step ks / d-tile dt then select by XOR (ks * 32, dt << 6).
+// Forward: K A-operand (lane -> key l31 (+32 kt), 16 B at slot 2 ks + lh): (l31*256 + x'*16) ^ (ks*32), K rows swizzled by row & 15
+__device__ __forceinline__ int k_lane_addr(int lane) {
+    const int l31 = lane & 31, lh = lane >> 5, kx = l31 & 15;
+    return l31 * 256 + (((kx & 14) | (lh ^ (kx & 1))) << 4);
+}
+// Forward: V^T A-operand via ds_read_b64_tr_b16. 16-lane group g = lane>>4 -> (d half = g&1, key half = g>>1 = lh);
+// lane s = lane&15 supplies row (s>>2) of the 4-row block, 8 B at columns 4 (s&3). V rows swizzled by (row & 3) << 2
+__device__ __forceinline__ int v_lane_addr(int lane) {
+    const int lh = lane >> 5, sg = lane & 15, gh = (lane >> 4) & 1;
+    return (4 * lh + (sg >> 2)) * 256 + ((((sg >> 2) << 2) | (gh << 1) | ((sg >> 1) & 1)) << 4) + (sg & 1) * 8;
+}
+
+// LDS fragment reads: 16 bytes of a row (ds_read_b128), and a transposing pair (2 x ds_read_b64_tr_b16: 4-row blocks at a0, a1)
+template <typename T>
+__device__ __forceinline__ typename MfmaA<T>::frag lds_row_frag(const unsigned char* a) {
+    union { uint4 r; typename MfmaA<T>::frag f; } u;
+    u.r = *reinterpret_cast<const uint4*>(a);
+    return u.f;
+}
+template <typename T>
+__device__ __forceinline__ typename MfmaA<T>::frag lds_tr_frag(const unsigned char* a0, const unsigned char* a1) {
+    union { s16x4_t h[2]; typename MfmaA<T>::frag f; } t;
+    t.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a0);
+    t.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a1);
+    return t.f;
+}
+
+// 16 bytes of a global row as an operand fragment: the 8 elements at column 16 ks + 8 lh (row = the row's pointer + 8 lh).
+// MASKED = head dims below 128: fragments past D are zero. The load stays UNCONDITIONAL -- a lane past D re-reads the row's
+// first 16 bytes -- and the zeroing is an AND with a lane mask, not an `if`: behind per-lane branches hipcc waits for each
+// load before it issues the next (the dQ kernel's 24 prologue loads one by one: +9 % on the whole kernel at head_dim 128,
+// profiles/r06zm_attn_bisect.txt). head_dim 128 (a wave-uniform test at the call sites) keeps the plain loads.
+// ZERO = false: the bytes past D stay what was re-read (for a factor whose partner is zeroed).
+template <bool MASKED, bool ZERO = true, typename T>
+__device__ __forceinline__ uint4 load_cols16(const T* row, int ks, int lh, int D) {
+    const bool in = !MASKED || ks * 16 + lh * 8 < D;
+    uint4 r = *reinterpret_cast<const uint4*>(in ? row + ks * 16 : row - lh * 8);
+    if constexpr (MASKED && ZERO) {
+        const unsigned keep = in ? 0xffffffffu : 0u;
+        r.x &= keep; r.y &= keep; r.z &= keep; r.w &= keep;
+    }
+    return r;
+}
+
+// registers 8 c .. 8 c + 7 of a C tile, rounded to T, as a B-operand fragment (PK2: through pack_pair2, else pack_pair)
+template <typename T, bool PK2 = true>
+__device__ __forceinline__ typename MfmaA<T>::frag pack8(const f32x16_t& s, int c) {
+    union { uint32_t w[4]; typename MfmaA<T>::frag f; } b;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        b.w[j] = PK2 ? pack_pair2<T>(s[8 * c + 2 * j], s[8 * c + 2 * j + 1]) : pack_pair<T>(s[8 * c + 2 * j], s[8 * c + 2 * j + 1]);
+    return b.f;
+}
+
+// The 32 query rows of a wave: wave w of a work item (q tile of QT rows, KV head kvh) serves query head kvh G + w % G and the
+// (w / G)-th 32-row slice of the tile; rows past the end load the last row (q_ld) and are never stored
+struct WaveRows { int head, qs, q_pos, q_ld; };
+__device__ __forceinline__ WaveRows wave_rows(int kvh, int qtile, int QT, int G, int wave, int l31, int T) {
+    WaveRows w;
+    w.head = kvh * G + (wave % G);
+    w.qs = qtile * QT + (wave / G) * 32;                             // first q position of this wave
+    w.q_pos = w.qs + l31;
+    w.q_ld = w.q_pos < T ? w.q_pos : T - 1;
+    return w;
+}
+
+// Band edges of a wave's rows. Lower edge (packed documents / sliding window): per-lane, and -- lo being non-decreasing --
+// lane 0 / lane 31 give the wave's min / max, the block's first row the block's min (t_first: its key tile). Upper edge: the
+// query itself (causal) or, `full`, the band's `hi` (non-causal attention inside documents; BAND builds only).
+// BAND = false: plain causal attention, the band bookkeeping folds away at compile time (it costs ~50 VGPRs).
+struct BandEdges { int lo_q, lo_w0, lo_w1, t_first, lim_q, lim_w0, lim_w1, lim_blk; };
+template <bool BAND>
+__device__ __forceinline__ BandEdges band_edges(const int* lo, const int* hi, bool full_, int b, int T, int q0_blk, int QT,
+                                                const WaveRows& w) {
+    BandEdges e;
+    e.lo_q = BAND ? lo[(int64_t)b * T + w.q_ld] : 0;
+    e.lo_w0 = BAND ? __builtin_amdgcn_readfirstlane(e.lo_q) : 0;
+    e.lo_w1 = BAND ? __builtin_amdgcn_readlane(e.lo_q, 31) : 0;
+    e.t_first = BAND ? lo[(int64_t)b * T + min(q0_blk, T - 1)] / KT : 0;
+    const bool full = BAND && full_;
+    e.lim_q = full ? hi[(int64_t)b * T + w.q_ld] : w.q_pos;
+    e.lim_w0 = full ? __builtin_amdgcn_readfirstlane(e.lim_q) : w.qs;
+    e.lim_w1 = full ? __builtin_amdgcn_readlane(e.lim_q, 31) : min(w.qs + 31, T - 1);
+    e.lim_blk = full ? hi[(int64_t)b * T + min(q0_blk + QT - 1, T - 1)] : q0_blk + QT - 1;
+    return e;
+}
+
+// Key tiles of a work item, [t_first, nkv_blk), as a wave sees them: tiles outside [first_tile_wave, last_tile_wave] are fully
+// masked for it (nothing to add); tiles that start below the wave's largest band edge are a masked prefix [.., t_pre_end);
+// tiles that touch the diagonal or run past T a masked suffix [t_suf, ..); the interior needs no mask.
+struct TileRange { int first_tile_wave, last_tile_wave, t_pre_end, t_suf; };
+__device__ __forceinline__ int key_tiles(int lim_blk, int T) { return min(lim_blk / KT + 1, (T + KT - 1) / KT); }   // keys <= the last row's upper edge
+__device__ __forceinline__ TileRange tile_range(const BandEdges& e, int nkv_blk, int T) {
+    TileRange r;
+    r.last_tile_wave = e.lim_w1 / KT;
+    r.first_tile_wave = e.lo_w0 / KT;
+    r.t_pre_end = min(nkv_blk, (e.lo_w1 + KT - 1) / KT);
+    const int t_diag = (e.lim_w0 + 1) / KT, t_rag = (T % KT) ? T / KT : nkv_blk;
+    r.t_suf = max(r.t_pre_end, min(min(t_diag, t_rag), nkv_blk));
+    return r;
+}
+// The loops over this range stay in the kernels (attn_fwd_kernel, attn_bwd_dq_kernel): the mask is a COMPILE-TIME flag of their
+// step and the band builds split the range by hand into [band-edge tiles | interior tiles | diagonal / ragged tiles] -- with a
+// run-time `need_mask` that depends on the band the compiler keeps both paths' registers alive in one loop body (+50 VGPRs,
+// spills). Plain causal: ONE loop with the (monotone) mask test around the masking statement only -- hipcc splits the range
+// itself and needs far fewer registers than with the hand-split loops. (Behind a shared driver that takes the step as a functor
+// the band forward gains 40 VALU instructions and 13 waits and is 3.5 % slower, profiles/attn_helpers_ab.jsonl.)
+
+// K / V LDS-DMA of one 64-key tile, this wave's share: a stage = K tile (64 rows x 256 B) then V tile. One DMA instruction = 4
+// rows. Wave w issues pieces 2w, 2w+1 (rows 8w .. 8w+7) of K and of V. lane -> (row = 4 piece + (lane>>4), stored slot =
+// lane & 15); the stored slot holds logical slot s ^ KSwz(row) (K) / s ^ VSwz(row) (V): the swizzle is applied on the per-lane
+// SOURCE offset, the destination is lane-linear. D < 128: a lane whose slot lies past D re-reads slot 0 of its row.
+struct SwzK { static __device__ __forceinline__ int of(int row) { return row & 15; } };               // forward, K rows
+struct SwzV { static __device__ __forceinline__ int of(int row) { return (row & 3) << 2; } };         // forward, V rows
+struct SwzC { static __device__ __forceinline__ int of(int row) { return swz_c(row); } };             // backward, both
+// source byte offset of piece i. CLAMP: rows past rmax re-read row rmax (ragged last tile: rows past the end re-read the last
+// key, they are masked). `ln` = the lane id, which the callers that recompute the offsets at every issue pass as an OPAQUE copy
+// (see attn_fwd_ps_kernel). 32-bit products (host: stride <= 2^22 elements)
+template <typename Swz, bool CLAMP>
+__device__ __forceinline__ unsigned dma_src_off(int wave, int i, int ln, int stride, int D, int rmax = 0) {
+    const int row = (wave * 2 + i) * 4 + (ln >> 4);
+    const int r = CLAMP ? min(row, rmax) : row;
+    return (unsigned)(r * stride * 2 + slot_in((ln & 15) ^ Swz::of(row), D) * 16);
+}
+// the two-instruction issue per tensor: kt / vt = the tile's first K / V row, d = this wave's destination in the stage
+__device__ __forceinline__ void dma_issue_kv(const void* kt, const void* vt, const unsigned (&ko)[2], const unsigned (&vo)[2], unsigned d) {
+    dma16x2(kt, ko[0], ko[1], d, d + 1024);
+    dma16x2(vt, vo[0], vo[1], d + TILE_B, d + TILE_B + 1024);
+}
+
+// Online softmax, the rescale: O / l are rescaled only when some row's max rose (wave-uniform test; after the first tiles it
+// rarely does). mt = the tile's row max, already scaled. Returns the exponent's reference.
+template <int NDT>
+__device__ __forceinline__ float rescale(float mt, float& m_run, float& l_run, f32x16_t (&o_acc)[4]) {
+    if (__builtin_amdgcn_ballot_w64(mt > m_run) != 0) {
+        const float m_new = fmaxf(m_run, mt);
+        // a row whose band starts after this tile has seen only masked keys so far: keep the exponent finite
+        const float alpha = __builtin_amdgcn_exp2f(m_run - (m_new == -INFINITY ? 0.f : m_new));   // first tile: exp2(-inf) = 0
+        m_run = m_new;
+        l_run *= alpha;
+#pragma unroll
+        for (int i = 0; i < NDT; ++i) o_acc[i] *= alpha;
+    }
+    return m_run == -INFINITY ? 0.f : m_run;
+}
+
+// The forward kernels' epilogue of a lane's row q_row (live: inside the sequence): O = O^T / l, LSE = ln2 * (m + log2 l)
+template <typename T>
+__device__ __forceinline__ void store_o_lse(const AttnArgs& p, int b, int head, int q_row, bool live, int lh, const f32x16_t (&o_acc)[4],
+                                            float m_run, float l_run, int D) {
+    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+    const float inv = 1.0f / l_tot;
+    T* op = (T*)p.O + b * p.o_sb + (int64_t)q_row * p.o_st + (int64_t)head * p.o_sh;
+    if (D == AD) store_rows_x4<T>(op, o_acc, inv, lh, live);
+    else store_rows_x4<T>(op, o_acc, inv, lh, live, D);
+    if (lh == 0 && live) p.LSE[((int64_t)b * p.Hq + head) * p.lse_st + q_row] = (m_run + log2f(l_tot)) * 0.6931471805599453f;
+}
+
 template <typename T, bool BAND, int DC>
 __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -258,41 +424,21 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
     block_to_work((int)blockIdx.x, npairs, rank_, pair_);
     const int qtile = p.nqt - 1 - rank_;                              // heaviest q tiles first
     const int kvh = pair_ % p.Hk, b = pair_ / p.Hk;
-    const int head = kvh * G + (wave % G);
-    const int qs = qtile * QT + (wave / G) * 32;                      // first q position of this wave
-    const int q_pos = qs + l31;
-    const int q_ld = q_pos < T_ ? q_pos : T_ - 1;
-    // band lower edge (packed documents / sliding window): per-lane, and -- lo being non-decreasing -- lane 0 /
-    // lane 31 give the wave's min / max, the block's first row the block's min
-    const int lo_q = BAND ? p.lo[(int64_t)b * T_ + q_ld] : 0;
-    const int lo_w0 = BAND ? __builtin_amdgcn_readfirstlane(lo_q) : 0, lo_w1 = BAND ? __builtin_amdgcn_readlane(lo_q, 31) : 0;
-    const int t_first = BAND ? p.lo[(int64_t)b * T_ + min(qtile * QT, T_ - 1)] / KT : 0;
-    // upper edge: the query itself (causal) or the band's `hi` (non-causal attention inside documents; BAND builds only)
-    const bool full = BAND && p.hi != nullptr;
-    const int lim_q = full ? p.hi[(int64_t)b * T_ + q_ld] : q_pos;
-    const int lim_w0 = full ? __builtin_amdgcn_readfirstlane(lim_q) : qs;
-    const int lim_w1 = full ? __builtin_amdgcn_readlane(lim_q, 31) : min(qs + 31, T_ - 1);
-    const int lim_blk = full ? p.hi[(int64_t)b * T_ + min(qtile * QT + QT - 1, T_ - 1)] : qtile * QT + QT - 1;
+    const WaveRows wr = wave_rows(kvh, qtile, QT, G, wave, l31, T_);
+    const int head = wr.head, qs = wr.qs, q_pos = wr.q_pos, q_ld = wr.q_ld;
+    const BandEdges e = band_edges<BAND>(p.lo, p.hi, p.hi != nullptr, b, T_, qtile * QT, QT, wr);
+    const int lo_q = e.lo_q, lim_q = e.lim_q, t_first = e.t_first;
 
     // ---- Q^T operand fragments (B operand: lane -> q = l31, 8 d at 16 ks + 8 lh), kept for the whole tile loop
     frag_t qf[8];
     {
         const T* qp = (const T*)p.Q + b * p.q_sb + (int64_t)q_ld * p.q_st + (int64_t)head * p.q_sh + lh * 8;
-        // MASKED = head dims below 128: fragments past D are zero. The load stays UNCONDITIONAL -- a lane past D re-reads the row's
-        // first 16 bytes -- and the zeroing is an AND with a lane mask, not an `if`: behind per-lane branches hipcc waits for each
-        // load before it issues the next (the dQ kernel's 24 prologue loads one by one: +9 % on the whole kernel at head_dim 128,
-        // profiles/r06zm_attn_bisect.txt). head_dim 128 (a wave-uniform test) keeps the plain loads.
+        // head dims below 128: fragments past D are zero (load_cols16)
         auto load_q = [&](auto masked_c) __attribute__((always_inline)) {
-            constexpr bool MASKED = decltype(masked_c)::value;
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) {
-                const bool in = !MASKED || ks * 16 + lh * 8 < p.D;
                 union { uint4 r; frag_t f; } u;
-                u.r = *reinterpret_cast<const uint4*>(in ? qp + ks * 16 : qp - lh * 8);
-                if constexpr (MASKED) {
-                    const unsigned keep = in ? 0xffffffffu : 0u;
-                    u.r.x &= keep; u.r.y &= keep; u.r.z &= keep; u.r.w &= keep;
-                }
+                u.r = load_cols16<decltype(masked_c)::value>(qp, ks, lh, p.D);
                 qf[ks] = u.f;
             }
         };
@@ -300,20 +446,13 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
         else load_q(std::true_type{});
     }
 
-    // ---- DMA plan: a stage = K tile (64 rows x 256 B) then V tile. One DMA instruction = 4 rows. Wave w issues
-    //      pieces 2w, 2w+1 (rows 8w .. 8w+7) of K and of V. lane -> (row = 4 piece + (lane>>4), stored slot =
-    //      lane & 15); the stored slot holds logical slot  s ^ (row & 15)  (K)  /  s ^ ((row & 3) << 2)  (V).
-    const int nkv_blk = min(lim_blk / KT + 1, (T_ + KT - 1) / KT);                     // keys <= the last row's upper edge
-    int drow[2], dks[2], dvs[2];
+    // ---- DMA plan (dma_src_off): K rows swizzled by row & 15, V rows by (row & 3) << 2
+    const int nkv_blk = key_tiles(e.lim_blk, T_);
     unsigned koff[2], voff[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int row = (wave * 2 + i) * 4 + (lane >> 4);
-        drow[i] = row;
-        dks[i] = slot_in((lane & 15) ^ (row & 15), p.D) * 16;
-        dvs[i] = slot_in((lane & 15) ^ ((row & 3) << 2), p.D) * 16;
-        koff[i] = (unsigned)((int64_t)row * p.k_st * 2 + dks[i]);
-        voff[i] = (unsigned)((int64_t)row * p.v_st * 2 + dvs[i]);
+        koff[i] = dma_src_off<SwzK, false>(wave, i, lane, (int)p.k_st, p.D);
+        voff[i] = dma_src_off<SwzV, false>(wave, i, lane, (int)p.v_st, p.D);
     }
     const int kvr = p.kvm == 1 ? kvh : kvh / p.kvm;                                     // the K / V head behind a virtual one
     const T* kbase = (const T*)p.K + b * p.k_sb + (int64_t)kvr * p.k_sh;
@@ -324,36 +463,23 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
         const int k0 = t * KT;
         const unsigned d = dst_w + stage * STAGE_B;
         if (k0 + KT <= T_) {
-            dma16x2(kbase + (int64_t)k0 * p.k_st, koff[0], koff[1], d, d + 1024);
-            dma16x2(vbase + (int64_t)k0 * p.v_st, voff[0], voff[1], d + TILE_B, d + TILE_B + 1024);
+            dma_issue_kv(kbase + (int64_t)k0 * p.k_st, vbase + (int64_t)k0 * p.v_st, koff, voff, d);
         } else {
-            // ragged last tile: rows past the end re-read the last key (they are masked)
-            unsigned ko[2], vo[2];
+            unsigned ko[2], vo[2];                                      // ragged last tile: rows clamped
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const int r = min(drow[i], T_ - 1 - k0);
-                ko[i] = (unsigned)((int64_t)r * p.k_st * 2 + dks[i]);
-                vo[i] = (unsigned)((int64_t)r * p.v_st * 2 + dvs[i]);
+                ko[i] = dma_src_off<SwzK, true>(wave, i, lane, (int)p.k_st, p.D, T_ - 1 - k0);
+                vo[i] = dma_src_off<SwzV, true>(wave, i, lane, (int)p.v_st, p.D, T_ - 1 - k0);
             }
-            dma16x2(kbase + (int64_t)k0 * p.k_st, ko[0], ko[1], d, d + 1024);
-            dma16x2(vbase + (int64_t)k0 * p.v_st, vo[0], vo[1], d + TILE_B, d + TILE_B + 1024);
+            dma_issue_kv(kbase + (int64_t)k0 * p.k_st, vbase + (int64_t)k0 * p.v_st, ko, vo, d);
         }
     };
 
-    // ---- per-lane LDS addresses
-    // K A-operand (lane -> key l31 (+32 kt), 16 B at slot 2 ks + lh): (l31*256 + x'*16) ^ (ks*32)
-    const int kx = l31 & 15;
-    const int k_lane = l31 * 256 + (((kx & 14) | (lh ^ (kx & 1))) << 4);
-    // V^T A-operand via ds_read_b64_tr_b16. 16-lane group g = lane>>4 -> (d half = g&1, key half = g>>1 = lh);
-    // lane s = lane&15 supplies row (s>>2) of the 4-row block, 8 B at columns 4 (s&3).
-    const int sg = lane & 15, gh = (lane >> 4) & 1;
-    const int v_lane = (4 * lh + (sg >> 2)) * 256 + ((((sg >> 2) << 2) | (gh << 1) | ((sg >> 1) & 1)) << 4) + (sg & 1) * 8;
+    const int k_lane = k_lane_addr(lane), v_lane = v_lane_addr(lane);       // per-lane LDS addresses
 
     f32x16_t o_acc[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o_acc[i][r] = 0.f;
+    for (int i = 0; i < 4; ++i) zero(o_acc[i]);
     float m_run = -INFINITY, l_run = 0.f;      // running max (log2 domain, both lane halves agree) / partial sum
 
 #ifdef UAMD_ATTN_TRACE
@@ -366,9 +492,8 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
     issue(t_first, 0);
     if (nt > 1) issue(t_first + 1, 1);
 
-    const int last_tile_wave = lim_w1 / KT;                          // tiles beyond are fully masked for this wave
-    const int first_tile_wave = lo_w0 / KT;                          // ... and tiles before
-    // One tile step; MASKED is compile-time and the tile range is split by hand (see attn_bwd_dq_kernel).
+    const TileRange tr = tile_range(e, nkv_blk, T_);
+    // One tile step; the mask is compile-time (see tile_range).
     // DC (template) = head-dim class, 64 / 96 / 128 columns: the k-steps of S^T and the d-tiles of O^T past it are not computed (the
     // Q fragments there are zero and the rows are never stored anyway: same results, half the MFMAs and LDS reads at head_dim 64)
     auto step = [&](int ti, auto mode_c, bool rt_mask) {       // mode 0: no mask, 1: mask, 2: mask iff rt_mask
@@ -384,7 +509,7 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
         ASTAMP(ti, 2);
         if (ti + 2 < nt) issue(t + 2, (ti + 2) % NST);              // its stage was last read before this barrier
         ASTAMP(ti, 3);
-        if (t > last_tile_wave || t < first_tile_wave) return;       // wave-uniform: nothing to add
+        if (t > tr.last_tile_wave || t < tr.first_tile_wave) return;       // wave-uniform: nothing to add
         const unsigned char* sk = smem + (ti % NST) * STAGE_B;
         const unsigned char* sv = sk + TILE_B;
 
@@ -392,14 +517,10 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
         f32x16_t st[2];
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
+            zero(st[kt]);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) st[kt][r] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-                union { uint4 r; frag_t f; } u;
-                u.r = *reinterpret_cast<const uint4*>(sk + kt * 32 * 256 + (k_lane ^ (ks * 32)));
-                st[kt] = MfmaA<T>::run(u.f, qf[ks], st[kt]);
-            }
+            for (int ks = 0; ks < NKS; ++ks)
+                st[kt] = MfmaA<T>::run(lds_row_frag<T>(sk + kt * 32 * 256 + (k_lane ^ (ks * 32))), qf[ks], st[kt]);
         }
         ASTAMP(ti, 4);
         // ---- (plain-causal build, which has the registers for it) the V^T operands of the first two 16-key steps
@@ -413,10 +534,7 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) {
                 const int a0 = (u * 16) * 256 + (v_lane ^ (dt << 6));
-                union { s16x4_t h[2]; frag_t f; } va;
-                va.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sv + a0));
-                va.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sv + a0 + 8 * 256));
-                dst[dt] = va.f;
+                dst[dt] = lds_tr_frag<T>(sv + a0, sv + a0 + 8 * 256);
             }
         };
         frag_t va0[4], va1[4], va2[4];
@@ -436,22 +554,12 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 if (MODE == 1 || (MODE == 2 && rt_mask)) {
-                    const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int key = k0 + kt * 32 + c_row(r, lh);
                     if (key > lim_q || key >= T_ || key < lo_q) st[kt][r] = -INFINITY;
                 }
                 mt = fmaxf(mt, st[kt][r]);
             }
-        mt = max_across_halves(mt) * p.scale_log2;
-        if (__builtin_amdgcn_ballot_w64(mt > m_run) != 0) {
-            const float m_new = fmaxf(m_run, mt);
-            // a row whose band starts after this tile has seen only masked keys so far: keep the exponent finite
-            const float alpha = __builtin_amdgcn_exp2f(m_run - (m_new == -INFINITY ? 0.f : m_new));   // first tile: exp2(-inf) = 0
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int i = 0; i < NDT; ++i) o_acc[i] *= alpha;
-        }
-        const float m_ref = m_run == -INFINITY ? 0.f : m_run;
+        const float m_ref = rescale<NDT>(max_across_halves(mt) * p.scale_log2, m_run, l_run, o_acc);
         float ls = 0.f;
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
@@ -467,12 +575,9 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
         // ---- O^T[d][q] += V^T P^T : per 16-key step u = 2 kt + c; lane half lh contracts keys
         //      16 u + {4 lh .. 4 lh + 3, 8 + 4 lh .. 8 + 4 lh + 3} = registers 8c .. 8c+7 of st[kt]
         auto pv = [&](int u, const frag_t* vsrc) {
-            const int kt = u >> 1, c = u & 1;
-            union { uint32_t w[4]; frag_t f; } pb;
+            const frag_t pb = pack8<T>(st[u >> 1], u & 1);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) pb.w[j] = pack_pair2<T>(st[kt][8 * c + 2 * j], st[kt][8 * c + 2 * j + 1]);
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) o_acc[dt] = MfmaA<T>::run(vsrc[dt], pb.f, o_acc[dt]);
+            for (int dt = 0; dt < NDT; ++dt) o_acc[dt] = MfmaA<T>::run(vsrc[dt], pb, o_acc[dt]);
         };
         if (PREFETCH) {                                               // operand fetch two steps ahead, 3 buffers
             load_v(2, va2);
@@ -493,20 +598,13 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
         }
         ASTAMP(ti, 6);
     };
-    {
-        const int t_pre_end = min(nkv_blk, (lo_w1 + KT - 1) / KT);       // tiles that start below the band edge
-        const int t_diag = (lim_w0 + 1) / KT, t_rag = (T_ % KT) ? T_ / KT : nkv_blk;
-        const int t_suf = max(t_pre_end, min(min(t_diag, t_rag), nkv_blk));
-        if constexpr (BAND) {
-            int ti = 0;
-            for (; t_first + ti < t_pre_end; ++ti) step(ti, std::integral_constant<int, 1>{}, true);
-            for (; t_first + ti < t_suf; ++ti) step(ti, std::integral_constant<int, 0>{}, false);
-            for (; ti < nt; ++ti) step(ti, std::integral_constant<int, 1>{}, true);
-        } else {
-            // plain causal: ONE loop with the (monotone) mask test around the masking statement only -- hipcc
-            // splits the range itself and needs far fewer registers than with the hand-split loops
-            for (int ti = 0; ti < nt; ++ti) step(ti, std::integral_constant<int, 2>{}, ti >= t_suf);
-        }
+    if constexpr (BAND) {
+        int ti = 0;
+        for (; t_first + ti < tr.t_pre_end; ++ti) step(ti, std::integral_constant<int, 1>{}, true);
+        for (; t_first + ti < tr.t_suf; ++ti) step(ti, std::integral_constant<int, 0>{}, false);
+        for (; ti < nt; ++ti) step(ti, std::integral_constant<int, 1>{}, true);
+    } else {
+        for (int ti = 0; ti < nt; ++ti) step(ti, std::integral_constant<int, 2>{}, ti >= tr.t_suf);
     }
 
 #ifdef UAMD_ATTN_TRACE
@@ -515,15 +613,7 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_kernel(AttnArgs p) {
         for (int i = 0; i < 16; ++i) g_attn_trace[(blockIdx.x * 8 + wave) * 16 + i] = ats[i];
     }
 #endif
-    // ---- epilogue: O = O^T / l, LSE = ln2 * (m + log2 l)
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
-    {
-        T* op = (T*)p.O + b * p.o_sb + (int64_t)q_ld * p.o_st + (int64_t)head * p.o_sh;
-        if (p.D == AD) store_rows_x4<T>(op, o_acc, inv, lh, q_pos < T_);
-        else store_rows_x4<T>(op, o_acc, inv, lh, q_pos < T_, p.D);
-        if (lh == 0 && q_pos < T_) p.LSE[((int64_t)b * p.Hq + head) * p.lse_st + q_pos] = (m_run + log2f(l_tot)) * 0.6931471805599453f;
-    }
+    store_o_lse<T>(p, b, head, q_ld, q_pos < T_, lh, o_acc, m_run, l_run, p.D);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -603,11 +693,10 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
     const unsigned dst_w = lds_base + wave * 2048;
     const unsigned qdst_w = lds_base + QSTAGE_OFF + wave * 8192;
     // one K/V tile of item `it` into ring stage `stage` (this wave's 4 pieces)
-    // DMA plan: a stage = K tile (64 rows x 256 B) then V tile; one instruction = 4 rows; wave w issues pieces 2w, 2w + 1 (rows
-    // 8w .. 8w + 7) of K and of V; lane -> (row = 4 piece + (lane >> 4), stored slot = lane & 15), the stored slot holds logical
-    // slot s ^ (row & 15) (K) / s ^ ((row & 3) << 2) (V). The per-lane source offsets are RECOMPUTED at every issue from an
-    // opaque copy of the lane id (a dozen VALU instructions per tile): kept in registers across the tile loop they are the first
-    // thing hipcc spills, and a scratch reload in front of the DMA drains vmcnt (= the ring)
+    // The DMA plan of dma_src_off (head_dim 128: every slot inside the row); the two dma16x2 stay written out -- through
+    // dma_issue_kv this kernel spills 8 more SGPRs to VGPR lanes (+21 VALU instructions). The per-lane source offsets are
+    // RECOMPUTED at every issue from an opaque copy of the lane id (a dozen VALU instructions per tile): kept in registers across
+    // the tile loop they are the first thing hipcc spills, and a scratch reload in front of the DMA drains vmcnt (= the ring)
     auto issue_tile = [&](const Item& it, int t, int stage) {
         const T* kbase = (const T*)p.K + it.b * p.k_sb + (int64_t)it.kvr * p.k_sh;
         const T* vbase = (const T*)p.V + it.b * p.v_sb + (int64_t)it.kvr * p.v_sh;
@@ -615,14 +704,11 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
         const unsigned d = dst_w + stage * STAGE_B;
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        const int rmax = T_ - 1 - k0;
         unsigned ko[2], vo[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = (wave * 2 + i) * 4 + (ln >> 4);
-            const int r = min(row, rmax);
-            ko[i] = (unsigned)(r * (int)p.k_st * 2 + ((ln & 15) ^ (row & 15)) * 16);
-            vo[i] = (unsigned)(r * (int)p.v_st * 2 + ((ln & 15) ^ ((row & 3) << 2)) * 16);
+        for (int i = 0; i < 2; ++i) {                                  // (rows past the end of the sequence clamped)
+            ko[i] = dma_src_off<SwzK, true>(wave, i, ln, (int)p.k_st, AD, T_ - 1 - k0);
+            vo[i] = dma_src_off<SwzV, true>(wave, i, ln, (int)p.v_st, AD, T_ - 1 - k0);
         }
         dma16x2(kbase + (int64_t)k0 * p.k_st, ko[0], ko[1], d, d + 1024);
         dma16x2(vbase + (int64_t)k0 * p.v_st, vo[0], vo[1], d + TILE_B, d + TILE_B + 1024);
@@ -652,9 +738,8 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
     unsigned kof[2], vof[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int row = (wave * 2 + i) * 4 + (lane >> 4);
-        kof[i] = (unsigned)(row * (int)p.k_st * 2 + ((lane & 15) ^ (row & 15)) * 16);
-        vof[i] = (unsigned)(row * (int)p.v_st * 2 + ((lane & 15) ^ ((row & 3) << 2)) * 16);
+        kof[i] = dma_src_off<SwzK, false>(wave, i, lane, (int)p.k_st, AD);
+        vof[i] = dma_src_off<SwzV, false>(wave, i, lane, (int)p.v_st, AD);
     }
     const int64_t kstep = (int64_t)KT * p.k_st, vstep = (int64_t)KT * p.v_st;       // elements per tile
     auto issue_fast = [&](const T* kq, const T* vq, int stage) {
@@ -662,10 +747,7 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
         dma16x2(kq, kof[0], kof[1], d, d + 1024);
         dma16x2(vq, vof[0], vof[1], d + TILE_B, d + TILE_B + 1024);
     };
-    const int kx = l31 & 15;
-    const int k_lane = l31 * 256 + (((kx & 14) | (lh ^ (kx & 1))) << 4);
-    const int sg = lane & 15, gh = (lane >> 4) & 1;
-    const int v_lane = (4 * lh + (sg >> 2)) * 256 + ((((sg >> 2) << 2) | (gh << 1) | ((sg >> 1) & 1)) << 4) + (sg & 1) * 8;
+    const int k_lane = k_lane_addr(lane), v_lane = v_lane_addr(lane);
     auto bar = [&]() {
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -674,11 +756,7 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
     frag_t qf[8];
     auto read_q = [&]() {                 // Q^T operand fragments from the wave's staging area (same lane map as the K rows)
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            union { uint4 r; frag_t f; } u;
-            u.r = *reinterpret_cast<const uint4*>(smem + QSTAGE_OFF + wave * 8192 + (k_lane ^ (ks * 32)));
-            qf[ks] = u.f;
-        }
+        for (int ks = 0; ks < 8; ++ks) qf[ks] = lds_row_frag<T>(smem + QSTAGE_OFF + wave * 8192 + (k_lane ^ (ks * 32)));
         wait_lgkm0();
     };
 
@@ -737,27 +815,18 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
             has_next = nxt_idx < nitems;
             if (has_next) nxt = decode_at(nxt_idx, __builtin_amdgcn_readfirstlane((int)(unsigned)(m >> 32)));
         };
-        const int head = cur.kvh * G + (wave % G);
-        const int qs = cur.qtile * QT + (wave / G) * 32;
-        const int q_pos = qs + l31;
-        const int q_ld = q_pos < T_ ? q_pos : T_ - 1;
-        const int lo_q = BAND ? p.lo[(int64_t)cur.b * T_ + q_ld] : 0;
-        const int lo_w0 = BAND ? __builtin_amdgcn_readfirstlane(lo_q) : 0, lo_w1 = BAND ? __builtin_amdgcn_readlane(lo_q, 31) : 0;
-        const int nkv_blk = cur.t_first + cur.nt;
-        const int last_tile_wave = min(qs + 31, T_ - 1) / KT;
-        const int first_tile_wave = lo_w0 / KT;
-        const int t_pre_end = min(nkv_blk, (lo_w1 + KT - 1) / KT);
-        const int t_diag = (qs + 1) / KT, t_rag = (T_ % KT) ? T_ / KT : nkv_blk;
-        const int t_suf = max(t_pre_end, min(min(t_diag, t_rag), nkv_blk));
+        const WaveRows wr = wave_rows(cur.kvh, cur.qtile, QT, G, wave, l31, T_);
+        const int head = wr.head, qs = wr.qs, q_pos = wr.q_pos, q_ld = wr.q_ld;
+        const BandEdges e = band_edges<BAND>(p.lo, nullptr, false, cur.b, T_, cur.qtile * QT, QT, wr);     // (causal: no upper edge)
+        const int lo_q = e.lo_q;
+        const TileRange tr = tile_range(e, cur.t_first + cur.nt, T_);
         const int nt = cur.nt;
         // K / V rows of tile ti + 2 (running: + one tile per step)
         const T* kq = (const T*)p.K + cur.b * p.k_sb + (int64_t)cur.kvr * p.k_sh + (int64_t)(cur.t_first + 2) * kstep;
         const T* vq = (const T*)p.V + cur.b * p.v_sb + (int64_t)cur.kvr * p.v_sh + (int64_t)(cur.t_first + 2) * vstep;
         read_q();
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o_acc[i][r] = 0.f;
+        for (int i = 0; i < 4; ++i) zero(o_acc[i]);
         float m_run = -INFINITY, l_run = 0.f;
         auto softmax_piece = [&](int u, float m_ref, float& ls0, float& ls1) {
             const int kt = u >> 1, c = u & 1;
@@ -775,7 +844,7 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
         for (int ti = 0; ti < nt; ++ti) {
             const int t = cur.t_first + ti;
             const int sx = s_ + ti;                                              // stream index
-            const bool live = !(t > last_tile_wave || t < first_tile_wave);     // wave-uniform
+            const bool live = !(t > tr.last_tile_wave || t < tr.first_tile_wave);     // wave-uniform
             const unsigned char* sk = smem + stg * STAGE_B;
             const unsigned char* sv = sk + TILE_B;
             const int stg2 = stg == 0 ? 2 : stg - 1;                            // (sx + 2) % 3
@@ -794,19 +863,14 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-                    for (int ks = 0; ks < 8; ++ks) {
-                        union { uint4 r; frag_t f; } u;
-                        u.r = *reinterpret_cast<const uint4*>(sk + kt * 32 * 256 + (k_lane ^ (ks * 32)));
-                        kv[kt * 8 + ks] = u.f;
-                    }
+                    for (int ks = 0; ks < 8; ++ks) kv[kt * 8 + ks] = lds_row_frag<T>(sk + kt * 32 * 256 + (k_lane ^ (ks * 32)));
                 wait_lgkm0();
             }
             bar();
             // ---------------- P2 (matrix): S^T = K Q^T; in its shadow the DMA of stream tile sx + 2 (this item's tile ti + 2, or
             //                  the NEXT item's tile ti + 2 - nt) and, once per item, the next item's Q rows
             if (live) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) st[0][r] = 0.f;
+                zero(st[0]);
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) st[0] = MfmaA<T>::run(kv[ks], qf[ks], st[0]);
                 __builtin_amdgcn_sched_barrier(0);
@@ -838,8 +902,7 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
                 for (int ks = 4; ks < 8; ++ks) st[0] = MfmaA<T>::run(kv[ks], qf[ks], st[0]);
                 // (zeroed HERE, in the block of its first MFMA: the C operand becomes the inline constant 0 -- set in the block
                 // above, across the DMA code, hipcc built the 16 zeros through 16 s_mov + 8 v_mov_b64 per tile step)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) st[1][r] = 0.f;
+                zero(st[1]);
 #pragma unroll
                 for (int ks = 0; ks < 8; ++ks) st[1] = MfmaA<T>::run(kv[8 + ks], qf[ks], st[1]);
             }
@@ -848,32 +911,25 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
             float m_ref = 0.f, ls0 = 0.f, ls1 = 0.f;
             if (live) {
                 const int k0 = t * KT;
-                const bool need_mask = BAND ? (t < t_pre_end || t >= t_suf) : (t >= t_suf);
+                const bool need_mask = BAND ? (t < tr.t_pre_end || t >= tr.t_suf) : (t >= tr.t_suf);
                 if (need_mask) {
 #pragma unroll
                     for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
-                            const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                            const int key = k0 + kt * 32 + c_row(r, lh);
                             if (key > q_pos || key >= T_ || key < lo_q) st[kt][r] = -INFINITY;
                         }
                 }
-                float m8[8];
+                float m8[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
 #pragma unroll
                     for (int dt = 0; dt < 4; ++dt) {
                         const int a0 = (u * 16) * 256 + (v_lane ^ (dt << 6));
-                        union { s16x4_t h[2]; frag_t f; } va;
-                        va.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sv + a0));
-                        va.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sv + a0 + 8 * 256));
-                        kv[u * 4 + dt] = va.f;
+                        kv[u * 4 + dt] = lds_tr_frag<T>(sv + a0, sv + a0 + 8 * 256);
                     }
                     const int kt = u >> 1, c = u & 1;
-#ifdef UAMD_ATTN_MAX_TREE2
-                    m8[2 * u] = fmaxf(fmaxf(st[kt][8 * c], st[kt][8 * c + 1]), fmaxf(st[kt][8 * c + 2], st[kt][8 * c + 3]));
-                    m8[2 * u + 1] = fmaxf(fmaxf(st[kt][8 * c + 4], st[kt][8 * c + 5]), fmaxf(st[kt][8 * c + 6], st[kt][8 * c + 7]));
-#else
                     // four independent chains of v_max3_f32 (a chain link takes in TWO new scores): 18 instructions for the 32
                     // scores of a lane instead of the pairwise tree's 31 -- the kernel is bound by instruction count
 #define SP_(i) st[kt][8 * c + (i)]
@@ -883,23 +939,9 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
                     else { m8[0] = max3f(m8[0], SP_(0), SP_(1)); m8[1] = max3f(m8[1], SP_(2), SP_(3));
                            m8[2] = max3f(m8[2], SP_(4), SP_(5)); m8[3] = max3f(m8[3], SP_(6), SP_(7)); }
 #undef SP_
-#endif
                 }
-#ifdef UAMD_ATTN_MAX_TREE2
-                float mt = fmaxf(fmaxf(fmaxf(m8[0], m8[1]), fmaxf(m8[2], m8[3])), fmaxf(fmaxf(m8[4], m8[5]), fmaxf(m8[6], m8[7])));
-#else
                 float mt = fmaxf(max3f(m8[0], m8[1], m8[2]), m8[3]);
-#endif
-                mt = max_across_halves(mt) * p.scale_log2;
-                if (__builtin_amdgcn_ballot_w64(mt > m_run) != 0) {
-                    const float m_new = fmaxf(m_run, mt);
-                    const float alpha = __builtin_amdgcn_exp2f(m_run - (m_new == -INFINITY ? 0.f : m_new));
-                    m_run = m_new;
-                    l_run *= alpha;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) o_acc[i] *= alpha;
-                }
-                m_ref = m_run == -INFINITY ? 0.f : m_run;
+                m_ref = rescale<4>(max_across_halves(mt) * p.scale_log2, m_run, l_run, o_acc);
                 softmax_piece(0, m_ref, ls0, ls1);
                 __builtin_amdgcn_sched_barrier(0);
                 wait_lgkm0();
@@ -933,13 +975,9 @@ __global__ void __launch_bounds__(512, 2) attn_fwd_ps_kernel(AttnArgs p) {
             else pend = 0x7fffffff;                                             // behind the stores below)
         }
         {
-            const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-            const float inv = 1.0f / l_tot;
             int qr = q_ld;
             asm volatile("" : "+v"(qr));
-            T* op = (T*)p.O + cur.b * p.o_sb + (int64_t)qr * p.o_st + (int64_t)head * p.o_sh;
-            store_rows_x4<T>(op, o_acc, inv, lh, q_pos < T_);
-            if (lh == 0 && q_pos < T_) p.LSE[((int64_t)cur.b * p.Hq + head) * p.lse_st + qr] = (m_run + log2f(l_tot)) * 0.6931471805599453f;
+            store_o_lse<T>(p, cur.b, head, qr, q_pos < T_, lh, o_acc, m_run, l_run, AD);
         }
         if (!has_next) break;
         pre = nt == 1 ? 1 : 2;
@@ -983,8 +1021,6 @@ struct AttnBwdArgs {
     int no_asm;                          // attn_bwd_dkdv4_kernel: 1 = no step takes the generated loop (UAMD_TUNE_ATTN_VAR bit 2)
 };
 
-__device__ __forceinline__ int swz_c(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-
 template <typename T, bool BAND, int DC>
 __global__ void __launch_bounds__(512, 2) attn_bwd_dq_kernel(AttnBwdArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -999,10 +1035,8 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dq_kernel(AttnBwdArgs p) {
     block_to_work((int)blockIdx.x, npairs, rank_, pair_);
     const int qtile = p.nqt - 1 - rank_;                              // heaviest q tiles first
     const int kvh = pair_ % p.Hk, b = pair_ / p.Hk;
-    const int head = kvh * G + (wave % G);
-    const int qs = qtile * QT + (wave / G) * 32;
-    const int q_pos = qs + l31;
-    const int q_ld = q_pos < T_ ? q_pos : T_ - 1;
+    const WaveRows wr = wave_rows(kvh, qtile, QT, G, wave, l31, T_);
+    const int head = wr.head, qs = wr.qs, q_pos = wr.q_pos, q_ld = wr.q_ld;
 
     frag_t qf[8], dof[8];
     float delta = 0.f;
@@ -1010,23 +1044,15 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dq_kernel(AttnBwdArgs p) {
         const T* qp = (const T*)p.Q + b * p.q_sb + (int64_t)q_ld * p.q_st + (int64_t)head * p.q_sh + lh * 8;
         const T* dp_ = (const T*)p.dO + b * p.do_sb + (int64_t)q_ld * p.do_st + (int64_t)head * p.do_sh + lh * 8;
         const T* op = (const T*)p.O + b * p.o_sb + (int64_t)q_ld * p.o_st + (int64_t)head * p.o_sh + lh * 8;
-        // MASKED = head dims below 128: zero registers past D. The loads stay unconditional (a lane past D re-reads the row's
-        // first 16 bytes) and the zeroing is an AND, see attn_fwd_kernel; head_dim 128 (a wave-uniform test) keeps the plain loads.
+        // head dims below 128: zero registers past D in Q and dO (load_cols16; O meets the zeros of dO in Delta)
         auto load_rows = [&](auto masked_c) __attribute__((always_inline)) {
             constexpr bool MASKED = decltype(masked_c)::value;
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) {
                 union { uint4 r; frag_t f; T e[8]; } u, d, o;
-                const bool in = !MASKED || ks * 16 + lh * 8 < p.D;
-                const int co = in ? ks * 16 : -lh * 8;
-                u.r = *reinterpret_cast<const uint4*>(qp + co);
-                d.r = *reinterpret_cast<const uint4*>(dp_ + co);
-                o.r = *reinterpret_cast<const uint4*>(op + co);
-                if constexpr (MASKED) {
-                    const unsigned keep = in ? 0xffffffffu : 0u;
-                    u.r.x &= keep; u.r.y &= keep; u.r.z &= keep; u.r.w &= keep;
-                    d.r.x &= keep; d.r.y &= keep; d.r.z &= keep; d.r.w &= keep;
-                }
+                u.r = load_cols16<MASKED>(qp, ks, lh, p.D);
+                d.r = load_cols16<MASKED>(dp_, ks, lh, p.D);
+                o.r = load_cols16<MASKED, false>(op, ks, lh, p.D);
                 qf[ks] = u.f;
                 dof[ks] = d.f;
 #pragma unroll
@@ -1051,16 +1077,9 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dq_kernel(AttnBwdArgs p) {
     f32x16_t ndelta;
 #pragma unroll
     for (int r = 0; r < 16; ++r) ndelta[r] = -delta;
-    const int lo_q = BAND ? p.lo[(int64_t)b * T_ + q_ld] : 0;
-    const int lo_w0 = BAND ? __builtin_amdgcn_readfirstlane(lo_q) : 0, lo_w1 = BAND ? __builtin_amdgcn_readlane(lo_q, 31) : 0;
-    const int t_first = BAND ? p.lo[(int64_t)b * T_ + min(qtile * QT, T_ - 1)] / KT : 0;
-    const bool full = BAND && p.noncausal;           // non-causal inside documents: keys lo[q] .. hi[q]
-    const int lim_q = full ? p.hi[(int64_t)b * T_ + q_ld] : q_pos;
-    const int lim_w0 = full ? __builtin_amdgcn_readfirstlane(lim_q) : qs;
-    const int lim_w1 = full ? __builtin_amdgcn_readlane(lim_q, 31) : min(qs + 31, T_ - 1);
-    const int lim_blk = full ? p.hi[(int64_t)b * T_ + min(qtile * QT + QT - 1, T_ - 1)] : qtile * QT + QT - 1;
-
-    const int nkv_blk = min(lim_blk / KT + 1, (T_ + KT - 1) / KT);
+    const BandEdges e = band_edges<BAND>(p.lo, p.hi, p.noncausal != 0, b, T_, qtile * QT, QT, wr);   // non-causal inside documents: keys lo[q] .. hi[q]
+    const int lo_q = e.lo_q, lim_q = e.lim_q, t_first = e.t_first;
+    const int nkv_blk = key_tiles(e.lim_blk, T_);
     const int kvr = p.kvm == 1 ? kvh : kvh / p.kvm;                                     // the K / V head behind a virtual one
     const T* kbase = (const T*)p.K + b * p.k_sb + (int64_t)kvr * p.k_sh;
     const T* vbase = (const T*)p.V + b * p.v_sb + (int64_t)kvr * p.v_sh;
@@ -1075,18 +1094,13 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dq_kernel(AttnBwdArgs p) {
         const unsigned d = dst_w + stage * STAGE_B;
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        const int rmax = T_ - 1 - k0;                                  // ragged last tile: rows past the end re-read the last key
         unsigned ko[2], vo[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = (wave * 2 + i) * 4 + (ln >> 4);
-            const int r = min(row, rmax);
-            const int sw = slot_in((ln & 15) ^ swz_c(row), p.D) * 16;
-            ko[i] = (unsigned)(r * (int)p.k_st * 2 + sw);
-            vo[i] = (unsigned)(r * (int)p.v_st * 2 + sw);
+        for (int i = 0; i < 2; ++i) {                                  // ragged last tile: rows past the end re-read the last key
+            ko[i] = dma_src_off<SwzC, true>(wave, i, ln, (int)p.k_st, p.D, T_ - 1 - k0);
+            vo[i] = dma_src_off<SwzC, true>(wave, i, ln, (int)p.v_st, p.D, T_ - 1 - k0);
         }
-        dma16x2(kbase + (int64_t)k0 * p.k_st, ko[0], ko[1], d, d + 1024);
-        dma16x2(vbase + (int64_t)k0 * p.v_st, vo[0], vo[1], d + TILE_B, d + TILE_B + 1024);
+        dma_issue_kv(kbase + (int64_t)k0 * p.k_st, vbase + (int64_t)k0 * p.v_st, ko, vo, d);
     };
 
     // Plain-causal build (which has the registers): whole tiles take a short issue -- constant per-lane offsets, running K / V
@@ -1095,10 +1109,8 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dq_kernel(AttnBwdArgs p) {
     if constexpr (!BAND) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int row = (wave * 2 + i) * 4 + (lane >> 4);
-            const int sw = slot_in((lane & 15) ^ swz_c(row), p.D) * 16;
-            kof[i] = (unsigned)(row * (int)p.k_st * 2 + sw);
-            vof[i] = (unsigned)(row * (int)p.v_st * 2 + sw);
+            kof[i] = dma_src_off<SwzC, false>(wave, i, lane, (int)p.k_st, p.D);
+            vof[i] = dma_src_off<SwzC, false>(wave, i, lane, (int)p.v_st, p.D);
         }
     }
     const int64_t kstep = (int64_t)KT * p.k_st, vstep = (int64_t)KT * p.v_st;
@@ -1106,27 +1118,23 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dq_kernel(AttnBwdArgs p) {
     const T* vq = vbase + (int64_t)(t_first + 2) * vstep;
     int stg = 0;                                                    // ring stage of the current tile = ti % 3, counted
 
+    // per-lane LDS addresses, swizzle C (written out: through helpers like k_lane_addr the band instances take 1-2 VGPRs more)
     // row reads (K for S^T, V for dP^T): lane -> row l31 (+32 kt), 16 B at logical slot 2 ks + lh
+    // transposing reads of K (A operand of dQ^T): second 4-row block = (addr ^ 32) + 8 rows
     const int r_lane = l31 * 256 + ((swz_c(l31 & 15) ^ lh) << 4);
-    // transposing reads of K (A operand of dQ^T), swizzle C: second 4-row block = (addr ^ 32) + 8 rows
     const int sg = lane & 15, gh = (lane >> 4) & 1;
     const int t_lane = (4 * lh + (sg >> 2)) * 256 +
                        ((((sg >> 2) << 2) | (((gh << 1) | ((sg >> 1) & 1)) ^ lh)) << 4) + (sg & 1) * 8;
 
     f32x16_t dq_acc[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dq_acc[i][r] = 0.f;
+    for (int i = 0; i < 4; ++i) zero(dq_acc[i]);
 
     const int nt = nkv_blk - t_first;
     issue(t_first, 0);
     if (nt > 1) issue(t_first + 1, 1);
-    const int last_tile_wave = lim_w1 / KT;
-    const int first_tile_wave = lo_w0 / KT;
-    // One tile step. MASKED is a compile-time flag and the tile range is split by hand into
-    // [band-edge tiles | interior tiles | diagonal / ragged tiles]: with a run-time `need_mask` that depends on
-    // the band the compiler keeps both paths' registers alive in one loop body (+50 VGPRs, spills).
+    const TileRange tr = tile_range(e, nkv_blk, T_);
+    // One tile step; the mask is compile-time (see tile_range).
     // (DC: the head-dim class, see attn_fwd_kernel -- k-steps of S^T / dP^T and d-tiles of dQ^T past it are not computed)
     auto step = [&](int ti, auto mode_c, bool rt_mask) {       // mode 0: no mask, 1: mask, 2: mask iff rt_mask
         constexpr int MODE = decltype(mode_c)::value;
@@ -1140,39 +1148,36 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dq_kernel(AttnBwdArgs p) {
         stg = stg == NST - 1 ? 0 : stg + 1;
         if (ti + 2 < nt) {
             if (!BAND && (t + 3) * KT <= T_) {
-                const unsigned d = dst_w + stg2 * STAGE_B;
-                dma16x2(kq, kof[0], kof[1], d, d + 1024);
-                dma16x2(vq, vof[0], vof[1], d + TILE_B, d + TILE_B + 1024);
+                dma_issue_kv(kq, vq, kof, vof, dst_w + stg2 * STAGE_B);
             } else {
                 issue(t + 2, stg2);
             }
             kq += kstep;
             vq += vstep;
         }
-        if (t > last_tile_wave || t < first_tile_wave) return;
+        if (t > tr.last_tile_wave || t < tr.first_tile_wave) return;
         const unsigned char* sk = smem + stg_cur * STAGE_B;
         const unsigned char* sv = sk + TILE_B;
         const int k0 = t * KT;
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
             f32x16_t st, dp;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { st[r] = 0.f; dp[r] = 0.f; }
+            zero(st);
+            zero(dp);
             if constexpr (CFOLD) dp = ndelta;
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks) {
-                union { uint4 r; frag_t f; } u, w;
-                u.r = *reinterpret_cast<const uint4*>(sk + kt * 32 * 256 + (r_lane ^ (ks * 32)));
-                w.r = *reinterpret_cast<const uint4*>(sv + kt * 32 * 256 + (r_lane ^ (ks * 32)));
-                st = MfmaA<T>::run(u.f, qf[ks], st);
-                dp = MfmaA<T>::run(w.f, dof[ks], dp);
+                const frag_t u = lds_row_frag<T>(sk + kt * 32 * 256 + (r_lane ^ (ks * 32)));
+                const frag_t w = lds_row_frag<T>(sv + kt * 32 * 256 + (r_lane ^ (ks * 32)));
+                st = MfmaA<T>::run(u, qf[ks], st);
+                dp = MfmaA<T>::run(w, dof[ks], dp);
             }
             // dS^T = P^T (dP^T - Delta) * scale, masked entries 0
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], p.scale_log2, -lse2));
                 if (MODE == 1 || (MODE == 2 && rt_mask)) {
-                    const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int key = k0 + kt * 32 + c_row(r, lh);
                     if (key > lim_q || key >= T_ || key < lo_q) pv = 0.f;
                 }
                 if constexpr (CFOLD) st[r] = pv * dp[r];
@@ -1180,37 +1185,22 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dq_kernel(AttnBwdArgs p) {
             }
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                union { uint32_t w[4]; frag_t f; } sb;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) sb.w[j] = BAND ? pack_pair<T>(st[8 * c + 2 * j], st[8 * c + 2 * j + 1])   // (the packed form spills in the band build)
-                                       : pack_pair2<T>(st[8 * c + 2 * j], st[8 * c + 2 * j + 1]);
+                const frag_t sb = pack8<T, !BAND>(st, c);              // (the packed conversion spills in the band build)
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt) {
                     const int a0 = (kt * 32 + c * 16) * 256 + (t_lane ^ (dt << 6));
-                    union { s16x4_t h[2]; frag_t f; } ka;
-                    ka.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sk + a0));
-                    ka.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sk + (a0 ^ 32) + 8 * 256));
-                    dq_acc[dt] = MfmaA<T>::run(ka.f, sb.f, dq_acc[dt]);
+                    dq_acc[dt] = MfmaA<T>::run(lds_tr_frag<T>(sk + a0, sk + (a0 ^ 32) + 8 * 256), sb, dq_acc[dt]);
                 }
             }
         }
     };
-    {
-        // tiles whose first key lies below the wave's largest band edge: a prefix; tiles that touch the diagonal
-        // or run past T: a suffix
-        const int t_pre_end = min(nkv_blk, (lo_w1 + KT - 1) / KT);
-        const int t_diag = (lim_w0 + 1) / KT, t_rag = (T_ % KT) ? T_ / KT : nkv_blk;
-        const int t_suf = max(t_pre_end, min(min(t_diag, t_rag), nkv_blk));
-        if constexpr (BAND) {
-            int ti = 0;
-            for (; t_first + ti < t_pre_end; ++ti) step(ti, std::integral_constant<int, 1>{}, true);
-            for (; t_first + ti < t_suf; ++ti) step(ti, std::integral_constant<int, 0>{}, false);
-            for (; ti < nt; ++ti) step(ti, std::integral_constant<int, 1>{}, true);
-        } else {
-            // plain causal: ONE loop with the (monotone) mask test around the masking statement only -- hipcc
-            // splits the range itself and needs far fewer registers than with the hand-split loops
-            for (int ti = 0; ti < nt; ++ti) step(ti, std::integral_constant<int, 2>{}, ti >= t_suf);
-        }
+    if constexpr (BAND) {
+        int ti = 0;
+        for (; t_first + ti < tr.t_pre_end; ++ti) step(ti, std::integral_constant<int, 1>{}, true);
+        for (; t_first + ti < tr.t_suf; ++ti) step(ti, std::integral_constant<int, 0>{}, false);
+        for (; ti < nt; ++ti) step(ti, std::integral_constant<int, 1>{}, true);
+    } else {
+        for (int ti = 0; ti < nt; ++ti) step(ti, std::integral_constant<int, 2>{}, ti >= tr.t_suf);
     }
     {
         int qr = q_ld;                       // (the row address formed HERE: hoisted, the pointer pair is spilled around the loop)
@@ -1249,12 +1239,8 @@ __global__ void __launch_bounds__(512, 2) attn_bwd_dq_kernel(AttnBwdArgs p) {
 // LDS tile formats and swizzles as the old kernel; same fixed-order reduction of the 4 units at the end.
 // LDS map: [V tile 16 KiB][stats 2 KiB: (stage, unit) x (32 LSE2 | 32 Delta)][ring: unit x stage x (Q 8 KiB | dO 8 KiB)]
 // -- the ring is unit-major so that stage / operand / k-step select an IMMEDIATE offset (< 64 KiB) on a per-lane constant.
-#ifndef UAMD_KD4_DMA_CHUNK
-#define UAMD_KD4_DMA_CHUNK 0      // first of the five chunks that carry the next step's LDS-DMA (0: beside the S MFMAs)
-#endif
-#ifndef UAMD_KD4_PF
-#define UAMD_KD4_PF 2             // operand prefetch distance in chunks (LDS round trip vs 64 MFMA cycles per chunk)
-#endif
+constexpr int KD4_DMA_CHUNK = 0;                      // first of the five chunks that carry the next step's LDS-DMA (0: beside the S MFMAs)
+constexpr int KD4_PF = 2;                             // operand prefetch distance in chunks (LDS round trip vs 64 MFMA cycles per chunk)
 constexpr int KD4_STATS_OFF = TILE_B;                 // 16 KiB
 constexpr int KD4_RING_OFF = KD4_STATS_OFF + 2048;    // 18 KiB
 constexpr int KD4_LDS = KD4_RING_OFF + 4 * 32768;     // 149,504 B
@@ -1369,11 +1355,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         const T* kp = (const T*)p.K + b * p.k_sb + (int64_t)key_ld * p.k_st + (int64_t)kvh * p.k_sh + lh * 8;
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-            const bool in = ks * 16 + lh * 8 < p.D;                    // (head dims below 128: zero past D; unconditional loads)
             union { uint4 r; frag_t f; } u;
-            const unsigned keep = in ? 0xffffffffu : 0u;
-            u.r = *reinterpret_cast<const uint4*>(in ? kp + ks * 16 : kp - lh * 8);
-            u.r.x &= keep; u.r.y &= keep; u.r.z &= keep; u.r.w &= keep;
+            u.r = load_cols16<true>(kp, ks, lh, p.D);                  // (head dims below 128: zero past D; unconditional loads)
             kf[kh][ks] = u.f;
         }
     }
@@ -1398,6 +1381,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     // ---- per-lane ABSOLUTE LDS byte addresses (swizzle C; the dynamic region's base included), made opaque once:
     //      stage / operand / k-step / c are immediates on them
     const unsigned ring_u = lds_base + KD4_RING_OFF + unit * 32768;
+    // (r_lane / t_lane as in attn_bwd_dq_kernel, written out: through a helper this kernel's register allocation moves)
     const int r_lane = l31 * 256 + ((swz_c(l31 & 15) ^ lh) << 4);
     const int sg = lane & 15, gh = (lane >> 4) & 1;
     const int t_lane = (4 * lh + (sg >> 2)) * 256 +
@@ -1450,13 +1434,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         // tile, the workgroups that run side by side on an XCD (the heaviest-first order starts them together) then stream the
         // SAME Q / dO rows at the same time -- one L2 fill serves them all. Upwards from each block's own diagonal, a row was
         // re-read two steps after its first use, with the XCD's whole traffic of two steps (4 MB = its L2) in between.
-#ifdef UAMD_KD4_UPWARD
-        auto q0_of = [&](int step) { return (q32_first + step * nslice + slice) * 32; };
-        constexpr int SWEEP = 1;
-#else
         auto q0_of = [&](int step) { return (q32_first + (nsteps - 1 - step) * nslice + slice) * 32; };
         constexpr int SWEEP = -1;
-#endif
         // tile a step's DMA fetches: its own q tile, or (idle slice at the end of the sequence) the last valid one
         auto fetch_q0 = [&](int step) {
             const int q0 = q0_of(step);
@@ -1501,7 +1480,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
         //   chunks 9-15  P = exp2(S c - LSE2) and its packing, pair by pair (S is complete after chunk 7)
         //   chunks 17-23 dS' = P (dP - Delta) and its packing (dP is complete after chunk 15)
         //   chunks 0-4   the next step's LDS-DMA (4 x 4 KiB of Q / dO + the stats line), beside the S MFMAs that have no VALU
-        //                work of their own (UAMD_KD4_DMA_CHUNK)
+        //                work of their own (KD4_DMA_CHUNK)
         // A VALU read of an MFMA result is always >= 2 MFMA issue slots behind the chain's last MFMA (the XDL write -> VALU
         // read wait states are covered by the MFMAs in between). Placement is pinned with EMPTY volatile asm statements
         // (volatile asms keep their order, and every MFMA is one): inputs are made opaque AFTER the chunk's MFMAs -- a pure
@@ -1514,7 +1493,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
             constexpr int SO = STAGE * 16384;
             f32x16_t sc[2], dp[2];
             union { uint32_t w[8]; frag_t f[2]; } pb[2], sb[2];   // P / dS' as B operands: f[c] = rows 16 c .. 16 c + 15
-            constexpr int PF = UAMD_KD4_PF;
+            constexpr int PF = KD4_PF;
             frag_t ob[PF + 1][3];
             float2 st2[2][3];                                     // stats of the pairs of the next chunk (ping-pong)
             auto rd128 = [&](unsigned addr) {
@@ -1576,7 +1555,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
                     float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[kh][2 * j + e], p.scale_log2, -lv[e]));
                     if (MASK) {
                         const int r = 2 * j + e;
-                        const int q = q0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        const int q = q0 + c_row(r, lh);
                         if (q < qlo_k[kh] || q >= T_ || key[kh] >= T_ || q > hi_k[kh]) pv = 0.f;
                     }
                     x[e] = pv;
@@ -1632,8 +1611,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
                         st2[(k + 1) & 1][1] = stat_pair(std::integral_constant<int, first + 1>{}, 0);
                         if constexpr (count == 3) st2[(k + 1) & 1][2] = stat_pair(std::integral_constant<int, first + 2>{}, 0);
                     }
-                    if constexpr (k >= UAMD_KD4_DMA_CHUNK && k < UAMD_KD4_DMA_CHUNK + 5)
-                        issue(qn, STAGE ^ 1, k - UAMD_KD4_DMA_CHUNK, std::false_type{});
+                    if constexpr (k >= KD4_DMA_CHUNK && k < KD4_DMA_CHUNK + 5)
+                        issue(qn, STAGE ^ 1, k - KD4_DMA_CHUNK, std::false_type{});
                 }
             };
             // dP starts at -Delta[q] (plane 0 of the scratch holds the negated row sums): dP' = dO V^T - Delta comes out of the
@@ -1806,61 +1785,99 @@ extern "C" int uamd_debug_attn_trace(unsigned* buf) {
 }
 #endif
 
+// ---- host side: what the forward and the backward entry check and derive in the same way, in the order the errors are reported.
+// 8 waves = G query heads x 8 / G q-subtiles, G the largest of 1, 2, 4, 8 dividing the group size; a KV head's other head
+// groups are work items of their own over the same K / V head (virtual KV heads, AttnArgs::kvm): group sizes 3, 5, 6, 7
+struct AttnShape {
+    int G, kvm, nsub, nqt;
+    bool empty;                          // empty batch: nothing to read (pointers may be null), the entry returns UAMD_OK
+    dim3 grid;                           // one block per (q tile, batch, virtual KV head)
+};
+// ptrs: the tensors that must be there, the first `naligned` of them 16-byte aligned; strides: [ntensors][3] = (batch, token, head);
+// limited: bit i = tensor i is addressed with 32-bit per-lane byte offsets inside a tile, its token stride is at most 2^22;
+// lse_mask: bits of lse_stride that must be clear
+static int attn_setup(AttnShape& s, std::initializer_list<const void*> ptrs, int naligned, const int64_t* strides, int ntensors,
+                      unsigned limited, int B, int T, int Hq, int Hk, int D, int lse_stride, int lse_mask, int causal,
+                      const int* lo, const int* hi) {
+    s.empty = B == 0 || T == 0;
+    if (B < 0 || T < 0 || Hq <= 0 || Hk <= 0) return UAMD_ERR_ARG;
+    if (s.empty) return UAMD_OK;
+    for (const void* q : ptrs)
+        if (!q) return UAMD_ERR_ARG;
+    if (!strides) return UAMD_ERR_ARG;
+    if (D < 8 || D > AD || (D & 7) || Hq % Hk || lse_stride < T || (lse_stride & lse_mask)) return UAMD_ERR_ARG;
+    if (!causal && !(lo && hi)) return UAMD_ERR_ARG;          // non-causal: the (lo, hi) band of the documents is required
+    const int Gr = Hq / Hk;
+    if (Gr > 8) return UAMD_ERR_ARG;
+    s.G = (Gr & 7) == 0 ? 8 : (Gr & 3) == 0 ? 4 : (Gr & 1) == 0 ? 2 : 1;
+    s.kvm = Gr / s.G;
+    for (int i = 0; i < 3 * ntensors; ++i)
+        if (strides[i] & 7) return UAMD_ERR_ALIGN;
+    int k = 0;
+    for (const void* q : ptrs)
+        if (k++ < naligned && !aligned16(q)) return UAMD_ERR_ALIGN;
+    for (int i = 0; i < ntensors; ++i)
+        if (((limited >> i) & 1) && strides[3 * i + 1] > (1 << 22)) return UAMD_ERR_ARG;
+    s.nsub = 8 / s.G;
+    s.nqt = (T + 32 * s.nsub - 1) / (32 * s.nsub);
+    s.grid = dim3((unsigned)(s.nqt * Hk * s.kvm * B));
+    return UAMD_OK;
+}
+// the shape fields AttnArgs and AttnBwdArgs share
+template <typename A>
+static void attn_set_shape(A& a, const AttnShape& s, int B, int T, int Hq, int Hk, int D, int lse_stride) {
+    a.B = B; a.T = T; a.Hq = Hq; a.Hk = Hk * s.kvm; a.G = s.G; a.nsub = s.nsub; a.kvm = s.kvm; a.nqt = s.nqt;
+    a.lse_st = lse_stride; a.D = D;
+}
+static void set_strides3(int64_t& sb, int64_t& st, int64_t& sh, const int64_t* strides, int i) {
+    sb = strides[3 * i]; st = strides[3 * i + 1]; sh = strides[3 * i + 2];
+}
+// f(band_c, dc_c) for the kernel instance of a launch: band or plain causal x head-dim class (64 / 96 / 128 columns computed,
+// attn_fwd_kernel's DC)
+template <typename F>
+static int by_band_and_class(bool band, int D, F&& f) {
+    auto cls = [&](auto band_c) -> int {
+        if (D > 96) return f(band_c, std::integral_constant<int, 128>{});
+        if (D > 64) return f(band_c, std::integral_constant<int, 96>{});
+        return f(band_c, std::integral_constant<int, 64>{});
+    };
+    return band ? cls(std::true_type{}) : cls(std::false_type{});
+}
+
 extern "C" int uamd_attn_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO,
                              const float* LSE, void* dQ, void* dK, void* dV, float* Delta,
                              const int64_t* strides, int B, int T, int Hq, int Hk, int D, int lse_stride,
                              float scale, int causal, const int* lo, const int* hi, int dtype, void* stream) {
     if ((lo == nullptr) != (hi == nullptr)) return UAMD_ERR_ARG;
-    if (B < 0 || T < 0 || Hq <= 0 || Hk <= 0) return UAMD_ERR_ARG;
-    if (B == 0 || T == 0) return UAMD_OK;                     // empty batch: nothing to read (pointers may be null)
-    if (!Q || !K || !V || !O || !dO || !LSE || !dQ || !dK || !dV || !Delta || !strides) return UAMD_ERR_ARG;
-    if (D < 8 || D > AD || (D & 7) || Hq % Hk || lse_stride < T || (lse_stride & 31)) return UAMD_ERR_ARG;
-    if (!causal && !(lo && hi)) return UAMD_ERR_ARG;          // non-causal: the (lo, hi) band of the documents is required
-    const int G = Hq / Hk;
-    if (G > 8) return UAMD_ERR_ARG;
-    // dQ kernel: 8 waves = Gq query heads x 8 / Gq q-subtiles, Gq the largest of 1, 2, 4, 8 dividing G; the other G / Gq - 1 head
-    // groups of a KV head are blocks of their own that read the same K / V head (virtual KV heads, AttnArgs::kvm)
-    const int Gq = (G & 7) == 0 ? 8 : (G & 3) == 0 ? 4 : (G & 1) == 0 ? 2 : 1, kvm = G / Gq;
-    for (int i = 0; i < 24; ++i)
-        if (strides[i] & 7) return UAMD_ERR_ALIGN;
-    if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O) || !aligned16(dO) || !aligned16(dQ) ||
-        !aligned16(dK) || !aligned16(dV) || !aligned16(LSE) || !aligned16(Delta))
-        return UAMD_ERR_ALIGN;
-    if (strides[1] > (1 << 22) || strides[4] > (1 << 22) || strides[7] > (1 << 22) || strides[13] > (1 << 22))
-        return UAMD_ERR_ARG;
+    AttnShape s;                                              // 32-bit offsets: the token strides of Q, K, V and dO
+    if (int rc = attn_setup(s, {Q, K, V, O, dO, dQ, dK, dV, LSE, Delta}, 10, strides, 8, 0x17, B, T, Hq, Hk, D, lse_stride, 31,
+                            causal, lo, hi); rc || s.empty)
+        return rc;
     AttnBwdArgs a;
     a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.LSE = LSE; a.dQ = dQ; a.dK = dK; a.dV = dV; a.Delta = Delta;
     a.lo = lo; a.hi = hi;
-    a.q_sb = strides[0]; a.q_st = strides[1]; a.q_sh = strides[2];
-    a.k_sb = strides[3]; a.k_st = strides[4]; a.k_sh = strides[5];
-    a.v_sb = strides[6]; a.v_st = strides[7]; a.v_sh = strides[8];
-    a.o_sb = strides[9]; a.o_st = strides[10]; a.o_sh = strides[11];
-    a.do_sb = strides[12]; a.do_st = strides[13]; a.do_sh = strides[14];
-    a.dq_sb = strides[15]; a.dq_st = strides[16]; a.dq_sh = strides[17];
-    a.dk_sb = strides[18]; a.dk_st = strides[19]; a.dk_sh = strides[20];
-    a.dv_sb = strides[21]; a.dv_st = strides[22]; a.dv_sh = strides[23];
-    a.B = B; a.T = T; a.Hq = Hq; a.Hk = Hk * kvm; a.G = Gq; a.nsub = 8 / Gq; a.kvm = kvm; a.lse_st = lse_stride; a.D = D;
+    set_strides3(a.q_sb, a.q_st, a.q_sh, strides, 0);
+    set_strides3(a.k_sb, a.k_st, a.k_sh, strides, 1);
+    set_strides3(a.v_sb, a.v_st, a.v_sh, strides, 2);
+    set_strides3(a.o_sb, a.o_st, a.o_sh, strides, 3);
+    set_strides3(a.do_sb, a.do_st, a.do_sh, strides, 4);
+    set_strides3(a.dq_sb, a.dq_st, a.dq_sh, strides, 5);
+    set_strides3(a.dk_sb, a.dk_st, a.dk_sh, strides, 6);
+    set_strides3(a.dv_sb, a.dv_st, a.dv_sh, strides, 7);
+    attn_set_shape(a, s, B, T, Hq, Hk, D, lse_stride);
     a.scale = scale; a.scale_log2 = scale * 1.4426950408889634f;
     a.noncausal = causal ? 0 : 1;
     a.no_asm = (uamd_tuning_get(UAMD_TUNE_ATTN_VAR) & 4) ? 1 : 0;
     if ((int64_t)B * Hq * lse_stride * 4 >= (1ll << 31)) return UAMD_ERR_ARG;      // 32-bit lane offset between the two stat planes
-    const int QT = 32 * a.nsub;
-    a.nqt = (T + QT - 1) / QT;
-    dim3 grid_q((unsigned)(a.nqt * a.Hk * B));
     dim3 grid_k((unsigned)(((T + KT - 1) / KT) * Hk * B));
     AttnBwdArgs ak = a;                                       // dK / dV: the real KV heads, all G query heads of each
-    ak.Hk = Hk; ak.G = G; ak.kvm = 1;
+    ak.Hk = Hk; ak.G = Hq / Hk; ak.kvm = 1;
     hipStream_t st = (hipStream_t)stream;
     // two launches: dQ (+ Delta, LSE log2 e) with the forward's tiling, then dK / dV with one wave per SIMD x 64 keys
     UAMD_DISPATCH_HALF(dtype,
-        // head-dim class of the dQ kernel: 64 / 96 / 128 columns computed (attn_fwd_kernel's DC)
-        auto dq = [&](auto band_c) -> int {
-            constexpr bool BAND = decltype(band_c)::value;
-            if (D > 96) return uamd_launch_lds<&attn_bwd_dq_kernel<T, BAND, 128>>(grid_q, dim3(512), ATTN_LDS, st, a);
-            if (D > 64) return uamd_launch_lds<&attn_bwd_dq_kernel<T, BAND, 96>>(grid_q, dim3(512), ATTN_LDS, st, a);
-            return uamd_launch_lds<&attn_bwd_dq_kernel<T, BAND, 64>>(grid_q, dim3(512), ATTN_LDS, st, a);
-        };
-        if (int rc = lo ? dq(std::true_type{}) : dq(std::false_type{})) return rc;
+        if (int rc = by_band_and_class(lo != nullptr, D, [&](auto band_c, auto dc_c) {
+                return uamd_launch_lds<&attn_bwd_dq_kernel<T, decltype(band_c)::value, decltype(dc_c)::value>>(s.grid, dim3(512), ATTN_LDS, st, a);
+            })) return rc;
         return uamd_launch_lds<&attn_bwd_dkdv4_kernel<T>>(grid_k, dim3(256), KD4_LDS, st, ak))
     return UAMD_ERR_DTYPE;
 }
@@ -1892,33 +1909,19 @@ static int* attn_ctr_slot(int dev, hipStream_t st) {
 static int attn_fwd_impl(const void* Q, const void* K, const void* V, void* O, float* LSE,
                          const int64_t* strides, int B, int T, int Hq, int Hk, int D, int lse_stride,
                          float scale, int causal, const int* lo, const int* hi, int dtype, void* stream) {
-    if (B < 0 || T < 0 || Hq <= 0 || Hk <= 0) return UAMD_ERR_ARG;
-    if (B == 0 || T == 0) return UAMD_OK;                     // empty batch: nothing to read (pointers may be null)
-    if (!Q || !K || !V || !O || !LSE || !strides) return UAMD_ERR_ARG;
-    if (D < 8 || D > AD || (D & 7) || Hq % Hk || lse_stride < T) return UAMD_ERR_ARG;
-    if (!causal && !(lo && hi)) return UAMD_ERR_ARG;          // non-causal: the (lo, hi) band of the documents is required
+    AttnShape s;                                              // 32-bit offsets inside a 64-key tile: the token strides of K and V
+    if (int rc = attn_setup(s, {Q, K, V, O, LSE}, 4, strides, 4, 0x6, B, T, Hq, Hk, D, lse_stride, 0, causal, lo, hi); rc || s.empty)
+        return rc;
     if (causal) hi = nullptr;
-    const int Gr = Hq / Hk;
-    if (Gr > 8) return UAMD_ERR_ARG;
-    // 8 waves = G query heads x 8 / G q-subtiles, G the largest of 1, 2, 4, 8 dividing the group size; a KV head's other head
-    // groups are work items of their own over the same K / V head (virtual KV heads, AttnArgs::kvm): group sizes 3, 5, 6, 7
-    const int G = (Gr & 7) == 0 ? 8 : (Gr & 3) == 0 ? 4 : (Gr & 1) == 0 ? 2 : 1, kvm = Gr / G;
-    for (int i = 0; i < 12; ++i)
-        if (strides[i] & 7) return UAMD_ERR_ALIGN;
-    if (!aligned16(Q) || !aligned16(K) || !aligned16(V) || !aligned16(O)) return UAMD_ERR_ALIGN;
-    // 32-bit per-lane byte offsets inside a 64-key tile
-    if (strides[4] > (1 << 22) || strides[7] > (1 << 22)) return UAMD_ERR_ARG;
     AttnArgs a;
     a.Q = Q; a.K = K; a.V = V; a.O = O; a.LSE = LSE; a.lo = lo; a.hi = hi;
-    a.q_sb = strides[0]; a.q_st = strides[1]; a.q_sh = strides[2];
-    a.k_sb = strides[3]; a.k_st = strides[4]; a.k_sh = strides[5];
-    a.v_sb = strides[6]; a.v_st = strides[7]; a.v_sh = strides[8];
-    a.o_sb = strides[9]; a.o_st = strides[10]; a.o_sh = strides[11];
-    a.B = B; a.T = T; a.Hq = Hq; a.Hk = Hk * kvm; a.G = G; a.nsub = 8 / G; a.kvm = kvm; a.lse_st = lse_stride; a.D = D;
+    set_strides3(a.q_sb, a.q_st, a.q_sh, strides, 0);
+    set_strides3(a.k_sb, a.k_st, a.k_sh, strides, 1);
+    set_strides3(a.v_sb, a.v_st, a.v_sh, strides, 2);
+    set_strides3(a.o_sb, a.o_st, a.o_sh, strides, 3);
+    attn_set_shape(a, s, B, T, Hq, Hk, D, lse_stride);
     a.scale_log2 = scale * 1.4426950408889634f;
-    const int QT = 32 * a.nsub;
-    a.nqt = (T + QT - 1) / QT;
-    dim3 grid((unsigned)(a.nqt * a.Hk * B));
+    const dim3 grid = s.grid;
     hipStream_t st = (hipStream_t)stream;
     const int n_cu = uamd_cu_count_or_256();
     // Plain causal batches with at least two work items per CU take the PERSISTENT kernel (one workgroup per CU walks the items,
@@ -1943,14 +1946,10 @@ static int attn_fwd_impl(const void* Q, const void* K, const void* V, void* O, f
             return lo ? uamd_launch_lds<&attn_fwd_ps_kernel<T, true, false>>(nwg, dim3(512), ATTN_PS_LDS, st, a)
                       : uamd_launch_lds<&attn_fwd_ps_kernel<T, false, false>>(nwg, dim3(512), ATTN_PS_LDS, st, a);
         }
-        // one block per item, by head-dim class: 64 / 96 / 128 columns computed
-        auto fwd = [&](auto band_c) -> int {
-            constexpr bool BAND = decltype(band_c)::value;
-            if (D > 96) return uamd_launch_lds<&attn_fwd_kernel<T, BAND, 128>>(grid, dim3(512), ATTN_LDS, st, a);
-            if (D > 64) return uamd_launch_lds<&attn_fwd_kernel<T, BAND, 96>>(grid, dim3(512), ATTN_LDS, st, a);
-            return uamd_launch_lds<&attn_fwd_kernel<T, BAND, 64>>(grid, dim3(512), ATTN_LDS, st, a);
-        };
-        return lo ? fwd(std::true_type{}) : fwd(std::false_type{}))
+        // one block per item
+        return by_band_and_class(lo != nullptr, D, [&](auto band_c, auto dc_c) {
+            return uamd_launch_lds<&attn_fwd_kernel<T, decltype(band_c)::value, decltype(dc_c)::value>>(grid, dim3(512), ATTN_LDS, st, a);
+        }))
     return UAMD_ERR_DTYPE;
 }
 

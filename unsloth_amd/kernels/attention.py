@@ -135,22 +135,8 @@ def document_band(T, batch=1, seq_lengths=None, device="cpu"):
     """(lo, hi) int32 [batch, T] of NON-CAUSAL attention inside documents: position t attends every position of its own document,
     lo[t] = first, hi[t] = last position of it. `seq_lengths`: document lengths back to back over the flattened batch (the
     `cu_seqlens` windows of a vision tower: one entry per image / frame); None = every batch row is one document. Documents are
-    cut at row boundaries like attention_band's. Integer work with torch ops; exact."""
-    total = batch * T
-    g = torch.arange(total, dtype=torch.int64, device=device)
-    row0 = (g // T) * T
-    if seq_lengths is not None:
-        lens = torch.as_tensor(seq_lengths, dtype=torch.int64, device=device).flatten()
-        lens = lens[lens > 0]
-        ends = torch.cumsum(lens, 0).clamp_(max=total)
-        doc = torch.searchsorted(ends, g, right=True)
-        ends = torch.cat([ends, ends.new_full((1,), total)])
-        starts = torch.cat([ends.new_zeros(1), ends[:-1]])
-        lo = torch.maximum(starts[doc], row0) - row0
-        hi = torch.minimum(ends[doc] - 1, row0 + (T - 1)) - row0
-    else:
-        lo, hi = torch.zeros_like(g), torch.full_like(g, T - 1)
-    return lo.to(torch.int32).view(batch, T).contiguous(), hi.to(torch.int32).view(batch, T).contiguous()
+    cut at row boundaries: attention_band's documents without a window. Integer work with torch ops; exact."""
+    return attention_band(T, batch, seq_lengths, None, device)
 
 
 def padding_mask_documents(attention_mask):
