@@ -239,7 +239,8 @@ void cdequantize_blockwise_fp32_nf4(float* code, unsigned char* A, float* absmax
  *   absmax_f32[k] = code2[absmax_u8[k]] * absmax2[k / blocksize2] + offset        (:650-659)
  *   W[j]          = NF4[nibble_j] * absmax_f32[j / blocksize]                     (:662-675)
  * Give EITHER absmax_f32 (not nested / pre-dequantised) OR the nested triple.
- * transpose_out != 0 writes out[c * ld_out + r] (W^T, for the contraction over `out` in dX = dY @ W).
+ * transpose_out != 0 writes out[c * ld_out + r] (W^T, for the contraction over `out` in dX = dY @ W): 16-bit dtypes,
+ * cols % 8 == 0 and blocksize % 8 == 0 (every 8 packed codes share one absmax), else UAMD_ERR_ARG and nothing is launched.
  */
 int uamd_dequantize_absmax(const float* code2, const uint8_t* absmax_u8, const float* absmax2,
                            float offset, float* out, int blocksize2, int64_t n, void* stream);
@@ -329,8 +330,9 @@ int uamd_gemm_tn_256(const void* A, int64_t lda, int M, int K, const uamd_gemm_g
                                  * per trip, grid capped at 2048 blocks, 1 = one vector, uncapped grid, 2 = two vectors, uncapped */
 #define UAMD_TUNE_GROUP_M 1
 #define UAMD_TUNE_STREAM_NT 2   /* streaming kernels: bit0 non-temporal loads, bit1 n.t. stores */
-#define UAMD_TUNE_DEQUANT_T 3   /* transposing NF4 dequant: 1 = 64x256 tile kernel, 0 = 64x64, 2 = 64x256 with
-                                 * the row tile as the fastest grid index (adjacent output segments written together) */
+#define UAMD_TUNE_DEQUANT_T 3   /* transposing NF4 dequant (64x256 tiles; blocksize % 8 == 0 or UAMD_ERR_ARG): 1 = the column tile as
+                                 * the fastest grid index (default), 2 = the row tile (adjacent output segments written together);
+                                 * any other value behaves as 1 (0 selected a 64x64-tile kernel, since removed) */
 #define UAMD_TUNE_ATTN_VAR 4    /* (UAMD_ATTN_VAR) attention forward: 0 = by shape (plain causal batches with >= 2 work items per CU take
                                  * attn_fwd_ps_kernel -- one persistent workgroup per CU, ping-pong wave groups -- everything else
                                  * attn_fwd_kernel, one block per work item); bit 0 = attn_fwd_kernel always; bit 1 = attn_fwd_ps_kernel

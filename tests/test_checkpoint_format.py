@@ -173,8 +173,9 @@ def test_nf4_code_table_is_the_published_quantile_construction():
     the QLoRA paper's "k-bit NormalFloat") from quantiles of N(0, 1) -- 8 positive levels norm.ppf(linspace(offset, 0.5, 9)[:-1]),
     7 negative ones -norm.ppf(linspace(offset, 0.5, 8)[:-1]), an exact zero, normalised by the largest. Re-deriving them here
     (torch.linspace in fp32, as bitsandbytes does) must give, BIT FOR BIT, the table of the oracle (oracle/ref_ops.py), of the
-    host module (unsloth_amd/nf4.py) and of the HIP kernels (csrc/nf4.hip kNF4): the one part of the third-party NF4 format
-    that can be pinned to its published algorithm without bitsandbytes installed."""
+    host module (unsloth_amd/nf4.py) and of the HIP kernels (csrc/nf4_decode.h kNF4, the one definition every kernel file
+    includes): the one part of the third-party NF4 format that can be pinned to its published algorithm without bitsandbytes
+    installed."""
     import re
     import numpy as np
     from scipy.stats import norm
@@ -188,15 +189,12 @@ def test_nf4_code_table_is_the_published_quantile_construction():
     assert levels.shape == (16,) and levels[7] == 0.0 and levels[0] == -1.0 and levels[15] == 1.0
     assert np.array_equal(levels, np.asarray(ORACLE_CODE, dtype=np.float32))
     assert np.array_equal(levels, np.asarray(HOST_CODE, dtype=np.float32))
-    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(ROOT, "unsloth_amd", "csrc", "nf4.hip")).read()
+    CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "unsloth_amd", "csrc")
+    src = open(os.path.join(CSRC, "nf4_decode.h")).read()
     body = re.search(r"kNF4\[16\]\s*=\s*\{([^}]*)\}", src).group(1)
     hip = np.array([float(t.strip().rstrip("f")) for t in body.split(",") if t.strip()], dtype=np.float32)
     assert np.array_equal(levels, hip)
-    # the decode GEMV carries its own copy of the table (csrc/decode.hip)
-    dec = open(os.path.join(ROOT, "unsloth_amd", "csrc", "decode.hip")).read()
-    m = re.search(r"kNF4d\[16\]\s*=\s*\{([^}]*)\}", dec)
-    assert m is not None
-    if m:
-        dtab = np.array([float(t.strip().rstrip("f")) for t in m.group(1).split(",") if t.strip()], dtype=np.float32)
-        assert np.array_equal(levels, dtab)
+    # ... and that is the only table in the C sources: every kernel file (nf4.hip, gemm.hip, decode.hip) takes it from that
+    # header, so a second copy -- which nothing above would pin -- fails here
+    holders = [f for f in sorted(os.listdir(CSRC)) if "0.6961928009986877" in open(os.path.join(CSRC, f), errors="replace").read()]
+    assert holders == ["nf4_decode.h"] and src.count("0.6961928009986877") == 1, holders

@@ -69,7 +69,7 @@ def test_nf4_dequantize_bit_exact(dtype, nested):
 @pytest.mark.parametrize("nested", [False, True])
 @pytest.mark.parametrize("rows,cols", [(128, 64), (192, 320), (520, 1032), (4096, 14336)])
 def test_nf4_dequantize_four_groups_per_lane_kernel_is_bit_identical(rows, cols, nested, blocksize):
-    """nf4_dequant_x4_kernel (knob 8, the default for 16-bit outputs of >= 8192 elements) against the one-group kernel
+    """nf4_dequant_trip_kernel launched with one segment (knob 8, the default for 16-bit outputs of >= 8192 elements) against the one-group kernel
     and, at the sizes the CPU restatement finishes quickly, the oracle: whole trips only (128 x 64 = one trip), trips + a
     group remainder, absmax blocks that straddle trips (blocksize 256), nested and plain statistics, the [14336, 4096]
     weight of the step (7168 trips over 1792 blocks)."""
@@ -123,11 +123,47 @@ def test_nf4_dequantize_group_launch_is_bit_identical(shapes, nested):
             assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_nf4_dequantize_group_launch_uses_each_members_level_table(dtype):
+    """Two one-trip weights (64 x 128) in one group launch, the second with another 16-entry table (the levels reversed)
+    in its quant_state.code: each member must be decoded with its OWN table, not member 0's -- against the single launches
+    and the CPU restatement, which reads quant_state.code too."""
+    from unsloth_amd.nf4 import quantize_nf4, dequantize_nf4, dequantize_nf4_group
+    pks, qss = [], []
+    for i in range(2):
+        W = (torch.randn(64, 128, generator=g(70 + i)) * 0.02).to(dtype)
+        pk, qs = quantize_nf4(W.to(DEV), compress_statistics=False)
+        pks.append(pk)
+        qss.append(qs)
+    plain = dequantize_nf4(pks[1], qss[1]).clone()
+    qss[1].code = qss[1].code.flip(0).contiguous()
+    singles = [dequantize_nf4(pk, qs).clone() for pk, qs in zip(pks, qss)]
+    assert not torch.equal(singles[1], plain)                              # (the reversed table does change the result)
+    got = dequantize_nf4_group(pks, qss, [torch.full((64, 128), 7.0, dtype=dtype, device=DEV) for _ in range(2)])
+    for a, b, pk, qs in zip(got, singles, pks, qss):
+        assert torch.equal(a, b)
+        assert torch.equal(a.cpu(), R.nf4_dequantize_state(pk, qs))
+
+
+def test_nf4_dequantize_transposed_refuses_a_blocksize_below_8():
+    """transpose_out with blocksize % 8 != 0 (no quantiser or checkpoint of this project produces one): UAMD_ERR_ARG before
+    any launch, the output untouched."""
+    from unsloth_amd import _lib
+    packed = torch.zeros(64 * 64 // 2, dtype=torch.uint8, device=DEV)
+    absmax = torch.ones(64 * 64 // 4, dtype=torch.float32, device=DEV)
+    out = torch.full((64, 64), 7.0, dtype=torch.bfloat16, device=DEV)
+    rc = _lib.lib().uamd_nf4_dequantize(_lib.ptr(packed), _lib.ptr(absmax), None, None, None, 0.0, 0, None, _lib.ptr(out),
+                                        64, 64, 4, _lib.dtype_code(torch.bfloat16), 1, 64, _lib.stream_of(out))
+    torch.cuda.synchronize()
+    assert rc == -2                                                        # UAMD_ERR_ARG
+    assert bool((out == 7.0).all())
+
+
 @pytest.mark.parametrize("rows,cols", [(1024, 4096), (200, 264), (64, 256), (136, 1032)])
-@pytest.mark.parametrize("knob", [0, 1])
+@pytest.mark.parametrize("knob", [1, 2])
 def test_nf4_dequantize_transposed_kernels_bit_exact(rows, cols, knob):
-    """Both transposing kernels (64x64 tile, 64x256 tile) against the CPU restatement; ragged rows/cols, absmax
-    blocks that straddle W rows (cols % 64 != 0), nested statistics."""
+    """The transposing kernel (64x256 tile) under both grid orders of knob 3 (column tile fastest, row tile fastest)
+    against the CPU restatement; ragged rows/cols, absmax blocks that straddle W rows (cols % 64 != 0), nested statistics."""
     from unsloth_amd import _lib
     from unsloth_amd.nf4 import quantize_nf4, dequantize_nf4
     W = (torch.randn(rows, cols, generator=g(4)) * 0.02).to(torch.bfloat16)

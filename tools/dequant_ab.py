@@ -58,6 +58,36 @@ def main():
                               "copies": copies, "bit_identical": ok}), flush=True)
         del ws
         torch.cuda.empty_cache()
+    gemm_nf4(L, g)
+
+
+def gemm_nf4(L, g, M=256, N=4096, K=4096):
+    """The decode INSIDE the GEMM (uamd_gemm_nt_nf4: what a launch below 512 tokens takes) through the C entry itself, over
+    enough distinct weights that none is served from the cache."""
+    from unsloth_amd.kernels.utils import _group
+    from unsloth_amd.nf4 import absmax_f32
+    X = torch.randn(M, K, generator=g).to(torch.bfloat16).to(DEV)
+    Y = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
+    ws = [quantize_nf4((torch.randn(N, K, generator=g) * 0.02).to(torch.bfloat16).to(DEV)) for _ in range(40)]
+    groups = [_group(p, Y, N, K, absmax=absmax_f32(q)) for p, q in ws]
+
+    def run():
+        for grp in groups:
+            rc = L.uamd_gemm_nt_nf4(_lib.ptr(X), K, M, K, grp, 1, 0, _lib.dtype_code(X.dtype), _lib.stream_of(X))
+            assert rc == 0, rc
+    us = []
+    for _ in range(3):
+        run()
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(5):
+            run()
+        e.record()
+        torch.cuda.synchronize()
+        us.append(s.elapsed_time(e) * 1e3 / (5 * len(groups)))
+    print(json.dumps({"kernel": "gemm_nt_nf4", "M": M, "N": N, "K": K, "us": round(sorted(us)[1], 2),
+                      "TFLOPs": round(2 * M * N * K / sorted(us)[1] / 1e6, 1)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -24,18 +24,12 @@
 //   * attention: grid (split, kv head, batch); the G query heads of a KV head share every K / V row read; each split
 //     keeps an online-softmax partial (m, l, o[D]) that a second tiny kernel combines. The split count is fixed at
 //     capture time; splits past the current length exit immediately.
-#include "common.h"
+#include "nf4_decode.h"
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
 
 namespace {
-
-__constant__ float kNF4d[16] = {
-    -1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f,
-    -0.28444138169288635f, -0.18477343022823334f, -0.09105003625154495f, 0.0f,
-    0.07958029955625534f, 0.16093020141124725f, 0.24611230194568634f, 0.33791524171829224f,
-    0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f, 1.0f};
 
 template <typename T> struct Dot2;
 template <> struct Dot2<bf16_t> {
@@ -352,7 +346,7 @@ __global__ void __launch_bounds__(GEMV_THREADS, NIT <= 16 ? 4 : 2) gemv_kernel(G
             if (gi < p.n_groups && c2) c2v[q] = c2[i & 255];
         }
     }
-    const float nf_hi = kNF4d[(tid >> 4) & 15], nf_lo = kNF4d[tid & 15];      // (constant MEMORY: two more loads that belong up here)
+    const float nf_hi = kNF4[(tid >> 4) & 15], nf_lo = kNF4[tid & 15];      // (constant MEMORY: two more loads that belong up here)
     DSTAMP(12);
     int trip = t_block ? total_trips : ((int)blockIdx.x - n_tb) * (GEMV_THREADS / 64) + wave_u;
     if (trip < total_trips) load_rows(trip, 0, RB);

@@ -27,7 +27,7 @@
 // ds_read_b128 fragment reads (16 rows x 4 k-slots per 16-lane group) are bank-conflict free.
 // MFMA operands are passed swapped (W rows as the A operand) so each lane ends up with 4
 // consecutive output columns -> 8-byte stores.
-#include "common.h"
+#include "nf4_decode.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
@@ -77,12 +77,6 @@ __device__ __forceinline__ int swz(int row, int slot) {   // byte offset inside 
     return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4);
 }
 
-__constant__ float kNF4g[16] = {
-    -1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f,
-    -0.28444138169288635f, -0.18477343022823334f, -0.09105003625154495f, 0.0f,
-    0.07958029955625534f, 0.16093020141124725f, 0.24611230194568634f, 0.33791524171829224f,
-    0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f, 1.0f};
-
 template <typename T, bool NF4>
 __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -104,9 +98,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(GemmArgs p) {
     const int M = p.M, K = p.K, N = g.N;
 
     float* lut = reinterpret_cast<float*>(smem + SMEM_BYTES);   // NF4 only (16 floats after the tiles)
-    if (NF4) {
-        if (tid < 16) lut[tid] = kNF4g[tid];
-    }
+    if (NF4) nf4_stage_tables(lut, nullptr, nullptr, nullptr);
 
     f32x4_t acc[4][4];
 #pragma unroll
@@ -218,12 +210,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(GemmArgs p) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {          // 4 bytes -> 8 elements -> one 16-byte slot
                 Vec16<T> o;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const uint32_t byte = (w4[q] >> (8 * b)) & 0xff;
-                    o.e[2 * b] = from_f32<T>(lut[byte >> 4] * rb_absmax);       // high nibble = even element
-                    o.e[2 * b + 1] = from_f32<T>(lut[byte & 15] * rb_absmax);
-                }
+                nf4_decode8(w4[q], lut, rb_absmax, o.e);
                 *reinterpret_cast<uint4*>(sb + swz(row, half * 4 + q)) = o.raw;
             }
         }

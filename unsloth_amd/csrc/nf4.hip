@@ -20,16 +20,10 @@
 //
 // HBM-bound: 0.516 B/param read + 2 B/param written. A lane owns 8 elements: one 4-byte load,
 // eight LDS LUT reads (16 distinct banks: conflict-free, identical codes broadcast), one fully
-// coalesced 16-byte store.
-#include "common.h"
+// coalesced 16-byte store. The level table, its staging into LDS and the packed-word decode are in nf4_decode.h.
+#include "nf4_decode.h"
 
 namespace {
-
-__constant__ float kNF4[16] = {
-    -1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f,
-    -0.28444138169288635f, -0.18477343022823334f, -0.09105003625154495f, 0.0f,
-    0.07958029955625534f, 0.16093020141124725f, 0.24611230194568634f, 0.33791524171829224f,
-    0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f, 1.0f};
 
 // out[i] = code[A[i]] * absmax[i / blocksize]   (8-bit blockwise, bnb kDequantizeBlockwise General8bit)
 __global__ void __launch_bounds__(256)
@@ -58,31 +52,42 @@ __device__ __forceinline__ float absmax_at(const AbsmaxSrc& a, const float* code
     return code2_lds[a.u8[k]] * a.absmax2[k / a.blocksize2] + a.offset;
 }
 
-// 8 elements per lane, row-major output identical in shape to the logical weight.
+// The ragged tail of the row-major kernels: the elements past the last whole group of 8 (n is always even for packed data,
+// odd handled too), one per lane of block 0. block_of(e) = e / blocksize, however the kernel forms it.
+template <typename T, typename BlockOf>
+__device__ __forceinline__ void decode_tail(const uint8_t* packed, const AbsmaxSrc& am, const float* lut,
+                                            const float* code2, T* out, int64_t n, BlockOf block_of) {
+    if (blockIdx.x != 0) return;
+    for (int64_t e = (n / 8) * 8 + threadIdx.x; e < n; e += 256) {
+        const uint8_t byte = packed[e >> 1];
+        const int c = (e & 1) ? (byte & 15) : (byte >> 4);
+        out[e] = from_f32<T>(lut[c] * absmax_at(am, code2, block_of(e)));
+    }
+}
+
+// 8 elements per lane, row-major output identical in shape to the logical weight. The general kernel: any output dtype,
+// any blocksize, any n.
 template <typename T>
 __global__ void __launch_bounds__(256)
 nf4_dequant_kernel(const uint8_t* __restrict__ packed, AbsmaxSrc am, const float* __restrict__ lut_g,
                    T* __restrict__ out, int64_t n, int blocksize) {
     __shared__ float lut[16];
     __shared__ float code2[256];
-    if (threadIdx.x < 16) lut[threadIdx.x] = lut_g ? lut_g[threadIdx.x] : kNF4[threadIdx.x];
-    if (am.u8) code2[threadIdx.x] = am.code2[threadIdx.x];
+    nf4_stage_tables(lut, lut_g, code2, am.u8 ? am.code2 : nullptr);
     __syncthreads();
     const int64_t ngroups = n / 8;
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += stride) {
         const uint32_t w = *reinterpret_cast<const uint32_t*>(packed + g * 4);
         const int64_t e0 = g * 8;
-        float a0 = absmax_at(am, code2, e0 / blocksize);
+        // the fp32 products of both branches meet here and are rounded to T in ONE place, in pairs (v_cvt_pk_*): with the
+        // rounding inside the branches hipcc formed one fp16 element of eight with v_fma_mixlo_f16 instead, and rare
+        // elements came out a last bit away from the trip kernel's
+        const float a0 = absmax_at(am, code2, e0 / blocksize);    // (ahead of the branch: requested beside the codes)
         float res[8];
         if ((blocksize & 7) == 0) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const uint32_t byte = (w >> (8 * b)) & 0xff;
-                res[2 * b] = lut[byte >> 4] * a0;        // high nibble first
-                res[2 * b + 1] = lut[byte & 15] * a0;
-            }
-        } else {
+            nf4_decode8(w, lut, a0, res);
+        } else {                                    // the 8 elements straddle absmax blocks: one absmax per element
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const uint32_t byte = (w >> (8 * b)) & 0xff;
@@ -100,14 +105,7 @@ nf4_dequant_kernel(const uint8_t* __restrict__ packed, AbsmaxSrc am, const float
             for (int j = 0; j < 8; ++j) out[e0 + j] = from_f32<T>(res[j]);
         }
     }
-    // ragged tail: n not a multiple of 8 (n is always even for packed data, odd handled too)
-    if (blockIdx.x == 0) {
-        for (int64_t e = ngroups * 8 + threadIdx.x; e < n; e += 256) {
-            const uint8_t byte = packed[e >> 1];
-            const int c = (e & 1) ? (byte & 15) : (byte >> 4);
-            out[e] = from_f32<T>(lut[c] * absmax_at(am, code2, e / blocksize));
-        }
-    }
+    decode_tail(packed, am, lut, code2, out, n, [&](int64_t e) { return e / blocksize; });
 }
 
 // The same arithmetic with FOUR groups per lane per trip (blocksize a power of two >= 8, 16-bit output). The one-group
@@ -117,160 +115,85 @@ nf4_dequant_kernel(const uint8_t* __restrict__ packed, AbsmaxSrc am, const float
 // trip are issued before anything waits, every load / store instruction of a wave still covers one contiguous 256 B / 1 KB
 // piece, and the block index -> absmax index is a shift (the 64-bit division by a run-time blocksize was ~40 VALU
 // instructions per group).
-template <typename T>
-__global__ void __launch_bounds__(256)
-nf4_dequant_x4_kernel(const uint8_t* __restrict__ packed, AbsmaxSrc am, const float* __restrict__ lut_g,
-                      T* __restrict__ out, int64_t n, int shift /* log2(blocksize) - 3 */, int blocksize) {
-    __shared__ float lut[16];
-    __shared__ float code2[256];
-    if (threadIdx.x < 16) lut[threadIdx.x] = lut_g ? lut_g[threadIdx.x] : kNF4[threadIdx.x];
-    if (am.u8) code2[threadIdx.x] = am.code2[threadIdx.x];
-    __syncthreads();
-    const int64_t ngroups = n / 8;
-    const int64_t ntrips = ngroups / 1024;
-    const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(packed);
-    auto decode_store = [&](uint32_t w, float a0, int64_t g) {
-        Vec16<T> o;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const uint32_t byte = (w >> (8 * b)) & 0xff;
-            o.e[2 * b] = from_f32<T>(lut[byte >> 4] * a0);          // high nibble first
-            o.e[2 * b + 1] = from_f32<T>(lut[byte & 15] * a0);
-        }
-        st16(out + g * 8, o);
-    };
-    for (int64_t t = blockIdx.x; t < ntrips; t += gridDim.x) {
-        const int64_t g0 = t * 1024 + threadIdx.x;
-        uint32_t w[4];
-        float a[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = words[g0 + j * 256];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a[j] = absmax_at(am, code2, (g0 + j * 256) >> shift);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) decode_store(w[j], a[j], g0 + j * 256);
-    }
-    // the groups past the last whole trip, then the elements past the last whole group (as the one-group kernel)
-    for (int64_t g = ntrips * 1024 + (int64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * 256)
-        decode_store(words[g], absmax_at(am, code2, g >> shift), g);
-    if (blockIdx.x == 0) {
-        for (int64_t e = ngroups * 8 + threadIdx.x; e < n; e += 256) {
-            const uint8_t byte = packed[e >> 1];
-            const int c = (e & 1) ? (byte & 15) : (byte >> 4);
-            out[e] = from_f32<T>(lut[c] * absmax_at(am, code2, e / blocksize));
-        }
-    }
-}
-
-// Up to FOUR weights in ONE launch (q | k | v, gate | up: the weights of one grouped GEMM, decoded back to back). Alone, a
+// One launch takes up to FOUR weights (q | k | v, gate | up: the weights of one grouped GEMM, decoded back to back). Alone, a
 // [1024, 4096] weight is 512 trips -- a quarter of the chip's resident blocks, 5.5 us at 1.9 TB/s -- and a [4096, 4096] one
-// is a single round of one-trip blocks (9.5 us, 4.4 TB/s): latency, not bandwidth. The trips of the segments are dealt
-// to the blocks as one sequence (a block's trips are consecutive and may straddle a segment boundary); arithmetic and
-// stores are those of nf4_dequant_x4_kernel, so the output is bit-identical to the single launches.
-struct DqMulti {
-    const uint8_t* packed[4];
-    const float* absmax[4];
-    const float* lut[4];     // per weight (NULL: the NF4 levels)
-    void* out[4];
-    int64_t trip_end[4];     // running total of whole trips (numel / 8192) up to and including segment i
+// is a single round of one-trip blocks (9.5 us, 4.4 TB/s): latency, not bandwidth. The whole trips of the segments are one
+// sequence, dealt to the blocks grid-stride (a block's trips may fall in different segments); the output does not depend
+// on the deal.
+// NSEG is the most segments a launch can carry: 1 (uamd_nf4_dequantize: any size, nested statistics) or 4
+// (uamd_nf4_dequantize_multi: sizes of whole trips). It is a template parameter because a block lives for one to seven
+// trips: with one segment every argument sits at a fixed offset and is requested once, up front; picked by a run-time
+// index, the fields of a segment are scalar loads inside the trip loop, each behind the one before (measured with one
+// kernel for both: the [4096, 4096] decode 10.1 -> 10.8 us, profiles/nf4_refactor_ab.jsonl).
+struct TripSeg {
+    const uint8_t* packed;
+    AbsmaxSrc am;
+    const float* lut;        // this weight's level table (NULL: the NF4 levels)
+    void* out;
+    int64_t n;               // elements
+};
+template <int NSEG> struct TripArgs {
+    TripSeg seg[NSEG];
+    int64_t trip_end[NSEG];  // running total of whole trips (n / 8192) up to and including segment i; the total past nseg
     int nseg;
 };
-template <typename T>
+template <typename T, int NSEG>
 __global__ void __launch_bounds__(256)
-nf4_dequant_x4_multi_kernel(DqMulti m, int shift, int64_t per_block) {
-    __shared__ float luts[4][16];
-    if (threadIdx.x < 64) {
-        const float* lg = m.lut[threadIdx.x >> 4];
-        luts[threadIdx.x >> 4][threadIdx.x & 15] = lg ? lg[threadIdx.x & 15] : kNF4[threadIdx.x & 15];
+nf4_dequant_trip_kernel(TripArgs<NSEG> m, int shift /* log2(blocksize) - 3 */) {
+    __shared__ float luts[NSEG][16];
+    __shared__ float code2s[NSEG][256];
+    if (threadIdx.x < 16 * NSEG) {                  // 16 lanes per segment: every table requested at once
+        const int s = threadIdx.x >> 4;
+        if (NSEG == 1 || s < m.nseg) nf4_stage_level(luts[s], m.seg[s].lut, threadIdx.x & 15);
     }
+#pragma unroll
+    for (int s = 0; s < NSEG; ++s)
+        if ((NSEG == 1 || s < m.nseg) && m.seg[s].am.u8) code2s[s][threadIdx.x] = m.seg[s].am.code2[threadIdx.x];
     __syncthreads();
-    const int64_t total = m.trip_end[m.nseg - 1];
-    const int64_t t0 = (int64_t)blockIdx.x * per_block, t1 = min(t0 + per_block, total);
-    for (int64_t t = t0; t < t1; ++t) {
-        int seg = 0;
-        while (t >= m.trip_end[seg]) ++seg;
-        const int64_t g0 = (t - (seg ? m.trip_end[seg - 1] : 0)) * 1024 + threadIdx.x;
-        const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(m.packed[seg]);
-        const float* __restrict__ am = m.absmax[seg];
-        const float* lut = luts[seg];
-        T* __restrict__ out = (T*)m.out[seg];
+    auto decode_store = [&](uint32_t w, const float* lut, float a0, T* dst) {
+        Vec16<T> o;
+        nf4_decode8(w, lut, a0, o.e);
+        st16(dst, o);
+    };
+    for (int64_t t = blockIdx.x; t < m.trip_end[NSEG - 1]; t += gridDim.x) {
+        int s = 0;
+#pragma unroll
+        for (int i = 1; i < NSEG; ++i)
+            if (t >= m.trip_end[i - 1]) s = i;
+        const TripSeg& sg = m.seg[s];
+        const int64_t g0 = (t - (s ? m.trip_end[s - 1] : 0)) * 1024 + threadIdx.x;
+        const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(sg.packed);
+        T* __restrict__ out = (T*)sg.out;
         uint32_t w[4];
         float a[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) w[j] = words[g0 + j * 256];
+        // (one uniform branch per trip, not one per load: hipcc keeps the four apart, each with its own wait)
+        if (const float* __restrict__ af = sg.am.f32) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) a[j] = am[(g0 + j * 256) >> shift];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            Vec16<T> o;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const uint32_t byte = (w[j] >> (8 * b)) & 0xff;
-                o.e[2 * b] = from_f32<T>(lut[byte >> 4] * a[j]);
-                o.e[2 * b + 1] = from_f32<T>(lut[byte & 15] * a[j]);
-            }
-            st16(out + (g0 + j * 256) * 8, o);
-        }
-    }
-}
-
-// Transposed output: W is logically [rows, cols] (cols contiguous, packed); writes
-// out[c * ld_out + r].  Used to hand the backward GEMM (dX = dY @ W) a K-contiguous operand.
-// 64x64 tile through LDS; both the packed read and the transposed write are 16B/128B coalesced.
-template <typename T>
-__global__ void __launch_bounds__(256)
-nf4_dequant_t_kernel(const uint8_t* __restrict__ packed, AbsmaxSrc am, const float* __restrict__ lut_g,
-                     T* __restrict__ out, int rows, int cols, int64_t ld_out, int blocksize) {
-    constexpr int TP = 72;  // padded tile row (elements); 144 B keeps 16-byte alignment
-    __shared__ float lut[16];
-    __shared__ float code2[256];
-    __shared__ __attribute__((aligned(16))) T tile[64 * TP];
-    if (threadIdx.x < 16) lut[threadIdx.x] = lut_g ? lut_g[threadIdx.x] : kNF4[threadIdx.x];
-    if (am.u8) code2[threadIdx.x] = am.code2[threadIdx.x];
-    __syncthreads();
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int u = threadIdx.x + 256 * it;       // 512 units of 8 elements
-        const int r = u >> 3, cq = (u & 7) * 8;
-        const int gr = r0 + r, gc = c0 + cq;
-        Vec16<T> o;
-        if (gr < rows && gc < cols) {
-            const int64_t e0 = (int64_t)gr * cols + gc;
-            const uint32_t w = *reinterpret_cast<const uint32_t*>(packed + (e0 >> 1));
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const uint32_t byte = (w >> (8 * b)) & 0xff;
-                const float a_hi = absmax_at(am, code2, (e0 + 2 * b) / blocksize);
-                const float a_lo = absmax_at(am, code2, (e0 + 2 * b + 1) / blocksize);
-                o.e[2 * b] = from_f32<T>(lut[byte >> 4] * a_hi);
-                o.e[2 * b + 1] = from_f32<T>(lut[byte & 15] * a_lo);
-            }
+            for (int j = 0; j < 4; ++j) a[j] = af[(g0 + j * 256) >> shift];
         } else {
-            o.raw = make_uint4(0, 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = absmax_at(sg.am, code2s[s], (g0 + j * 256) >> shift);
         }
-        *reinterpret_cast<uint4*>(&tile[r * TP + cq]) = o.raw;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) decode_store(w[j], luts[s], a[j], out + (g0 + j * 256) * 8);
     }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int u = threadIdx.x + 256 * it;
-        const int c = u >> 3, rq = (u & 7) * 8;     // output row c (a column of W), 8 rows of W
-        const int gc = c0 + c, gr = r0 + rq;
-        if (gc < cols && gr < rows) {
-            Vec16<T> o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o.e[j] = tile[(rq + j) * TP + c];
-            if (gr + 8 <= rows && ((ld_out & 7) == 0)) {
-                st16(out + (int64_t)gc * ld_out + gr, o);
-            } else {
-                for (int j = 0; j < 8 && gr + j < rows; ++j) out[(int64_t)gc * ld_out + gr + j] = o.e[j];
-            }
-        }
+    // the groups past the last whole trip, then the elements past the last whole group (as the one-group kernel); a launch
+    // of several weights has neither
+    if constexpr (NSEG == 1) {
+        const TripSeg& sg = m.seg[0];
+        const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(sg.packed);
+        T* __restrict__ out = (T*)sg.out;
+        const int64_t ngroups = sg.n / 8;
+        for (int64_t g = (ngroups / 1024) * 1024 + (int64_t)blockIdx.x * 256 + threadIdx.x; g < ngroups; g += (int64_t)gridDim.x * 256)
+            decode_store(words[g], luts[0], absmax_at(sg.am, code2s[0], g >> shift), out + g * 8);
+        decode_tail(sg.packed, sg.am, luts[0], code2s[0], out, sg.n, [&](int64_t e) { return e >> (shift + 3); });
     }
 }
 
-// Transposed output, large-tile version (the one the backward uses): 64 rows x 256 columns per block.
+// Transposed output: W is logically [rows, cols] (cols contiguous, packed); writes out[c * ld_out + r]. Hands a GEMM that
+// contracts over W's rows (dX = dY @ W) a K-contiguous operand. 64 rows x 256 columns per block:
 //   * packed read: 32 consecutive lanes cover 128 B of one W row (4 B = 8 codes per lane), two rows per lane;
 //   * the lane packs (row r, row r+1) of each of its 8 columns into one 32-bit word and writes it to the
 //     transposed LDS tile [256 columns][32 row pairs] with the pair index XOR-ed by (column >> 3): the 32 lanes
@@ -291,8 +214,7 @@ nf4_dequant_t2_kernel(const uint8_t* __restrict__ packed, AbsmaxSrc am, const fl
     __shared__ float code2[256];
     __shared__ __attribute__((aligned(16))) uint32_t tile[256 * 32];        // 32 KiB
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < 16) lut[tid] = lut_g ? lut_g[tid] : kNF4[tid];
-    if (am.u8) code2[tid] = am.code2[tid];
+    nf4_stage_tables(lut, lut_g, code2, am.u8 ? am.code2 : nullptr);
     __syncthreads();
     // row_fastest: consecutive blocks take consecutive 64-row tiles of W = ADJACENT 128-byte segments of the same 256
     // output rows, so that within a short window whole DRAM pages of the transposed output get written (with the
@@ -408,41 +330,53 @@ inline unsigned grid_cap(int64_t work_items) {
     return (unsigned)(blocks < 256 * 8 ? blocks : 256 * 8);
 }
 
+inline bool trip_blocksize(int blocksize) { return blocksize >= 8 && (blocksize & (blocksize - 1)) == 0; }
+inline int block_shift(int blocksize) {     // log2(blocksize) - 3: 8-element group index -> absmax index
+    int shift = 0;
+    while ((8 << shift) < blocksize) ++shift;
+    return shift;
+}
+// whole trips spread EVENLY over at most 8 blocks per CU (7168 trips of a [14336, 4096] weight = 1792 blocks of 4 trips,
+// not 2048 blocks of which half run a fourth trip alone)
+inline unsigned trip_grid(int64_t trips) {
+    const int64_t per_block = (trips + 2047) / 2048;
+    return (unsigned)((trips + per_block - 1) / per_block);
+}
+// the trip kernel over m.seg[0 .. m.nseg) (every n >= 8192, blocksize a power of two >= 8); fills in m.trip_end
+template <typename T, int NSEG>
+int launch_trips(TripArgs<NSEG>& m, int blocksize, hipStream_t st) {
+    int64_t total = 0;
+    for (int i = 0; i < NSEG; ++i) {
+        if (i < m.nseg) total += m.seg[i].n / 8192;
+        m.trip_end[i] = total;
+    }
+    hipLaunchKernelGGL((nf4_dequant_trip_kernel<T, NSEG>), dim3(trip_grid(total)), dim3(256), 0, st, m, block_shift(blocksize));
+    return uamd_launch_status();
+}
+
 template <typename T>
 int launch_dequant(const uint8_t* packed, const AbsmaxSrc& am, const float* lut, void* out,
                    int64_t rows, int64_t cols, int blocksize, int transpose, int64_t ld_out,
                    hipStream_t st) {
     const int64_t n = rows * cols;
     if (!transpose) {
-        const bool pow2 = blocksize >= 8 && (blocksize & (blocksize - 1)) == 0;
-        if (sizeof(T) == 2 && pow2 && n >= 8192 && uamd_tuning_get(UAMD_TUNE_DEQUANT_X4) != 0) {
-            // whole trips spread EVENLY over at most 8 blocks per CU (7168 trips of a [14336, 4096] weight = 1792 blocks
-            // of 4 trips, not 2048 blocks of which half run a fourth trip alone)
-            const int64_t ntrips = n / 8192;
-            const int64_t per_block = (ntrips + 2047) / 2048;
-            const unsigned grid = (unsigned)((ntrips + per_block - 1) / per_block);
-            int shift = 0;
-            while ((8 << shift) < blocksize) ++shift;
-            hipLaunchKernelGGL((nf4_dequant_x4_kernel<T>), dim3(grid), dim3(256), 0, st, packed, am, lut, (T*)out, n,
-                               shift, blocksize);
-        } else {
-            hipLaunchKernelGGL((nf4_dequant_kernel<T>), dim3(grid_cap(n / 8)), dim3(256), 0, st, packed,
-                               am, lut, (T*)out, n, blocksize);
+        if constexpr (sizeof(T) == 2) {
+            if (trip_blocksize(blocksize) && n >= 8192 && uamd_tuning_get(UAMD_TUNE_DEQUANT_X4) != 0) {
+                TripArgs<1> m = {};
+                m.seg[0] = TripSeg{packed, am, lut, out, n};
+                m.nseg = 1;
+                return launch_trips<T>(m, blocksize, st);
+            }
         }
+        hipLaunchKernelGGL((nf4_dequant_kernel<T>), dim3(grid_cap(n / 8)), dim3(256), 0, st, packed,
+                           am, lut, (T*)out, n, blocksize);
     } else {
-        if (sizeof(T) != 2 || (cols & 7)) return UAMD_ERR_ARG;
-        const int tv = uamd_tuning_get(UAMD_TUNE_DEQUANT_T);
-        if ((blocksize & 7) == 0 && tv != 0) {
-            const int rf = tv == 2;
-            dim3 grid((unsigned)((cols + 255) / 256), (unsigned)((rows + 63) / 64));
-            if (rf) grid = dim3((unsigned)((rows + 63) / 64), (unsigned)((cols + 255) / 256));
-            hipLaunchKernelGGL((nf4_dequant_t2_kernel<T>), grid, dim3(256), 0, st, packed, am, lut,
-                               (T*)out, (int)rows, (int)cols, ld_out, blocksize, rf);
-        } else {
-            dim3 grid((unsigned)((cols + 63) / 64), (unsigned)((rows + 63) / 64));
-            hipLaunchKernelGGL((nf4_dequant_t_kernel<T>), grid, dim3(256), 0, st, packed, am, lut,
-                               (T*)out, (int)rows, (int)cols, ld_out, blocksize);
-        }
+        // the transposing kernel takes one absmax per 8-element group
+        if (sizeof(T) != 2 || (cols & 7) || (blocksize & 7)) return UAMD_ERR_ARG;
+        const int rf = uamd_tuning_get(UAMD_TUNE_DEQUANT_T) == 2;
+        const unsigned tr = (unsigned)((rows + 63) / 64), tc = (unsigned)((cols + 255) / 256);
+        hipLaunchKernelGGL((nf4_dequant_t2_kernel<T>), rf ? dim3(tr, tc) : dim3(tc, tr), dim3(256), 0, st, packed, am,
+                           lut, (T*)out, (int)rows, (int)cols, ld_out, blocksize, rf);
     }
     return uamd_launch_status();
 }
@@ -514,44 +448,28 @@ extern "C" int uamd_nf4_dequantize(const uint8_t* packed, const float* absmax_f3
                          ld_out, stream);
 }
 
-// Blockwise NF4 quantiser (first-level only; the 8-bit nested quantisation of absmax is host
-// logic, see unsloth_amd/nf4.py). blocksize: power of two in [8, 512].
-// Row-major NF4 decode of up to four weights in one launch (see nf4_dequant_x4_multi_kernel). Every weight: fp32 absmax
+// Row-major NF4 decode of up to four weights in one launch (see nf4_dequant_trip_kernel). Every weight: fp32 absmax
 // (first level, already dequantised), numel a multiple of 8192, 16-bit output, contiguous. Bit-identical to uamd_nf4_dequantize.
 extern "C" int uamd_nf4_dequantize_multi(int nseg, const uint8_t* const* packed, const float* const* absmax_f32,
                                          void* const* out, const int64_t* numel, const float* const* nf4_lut, int blocksize,
                                          int out_dtype, void* stream) {
     if (nseg < 1 || nseg > 4 || !packed || !absmax_f32 || !out || !numel) return UAMD_ERR_ARG;
-    if (blocksize < 8 || blocksize > 8192 || (blocksize & (blocksize - 1))) return UAMD_ERR_ARG;
+    if (!trip_blocksize(blocksize) || blocksize > 8192) return UAMD_ERR_ARG;
     if (out_dtype != UAMD_BF16 && out_dtype != UAMD_F16) return UAMD_ERR_DTYPE;
-    DqMulti m;
-    int64_t total = 0;
-    for (int i = 0; i < 4; ++i) {
-        if (i < nseg) {
-            if (!packed[i] || !absmax_f32[i] || !out[i] || numel[i] <= 0 || (numel[i] & 8191)) return UAMD_ERR_ARG;
-            if (!aligned16(packed[i]) || !aligned16(out[i])) return UAMD_ERR_ALIGN;
-            total += numel[i] / 8192;
-        }
-        m.packed[i] = i < nseg ? packed[i] : nullptr;
-        m.absmax[i] = i < nseg ? absmax_f32[i] : nullptr;
-        m.lut[i] = (i < nseg && nf4_lut) ? nf4_lut[i] : nullptr;
-        m.out[i] = i < nseg ? out[i] : nullptr;
-        m.trip_end[i] = total;
+    TripArgs<4> m = {};
+    for (int i = 0; i < nseg; ++i) {
+        if (!packed[i] || !absmax_f32[i] || !out[i] || numel[i] <= 0 || (numel[i] & 8191)) return UAMD_ERR_ARG;
+        if (!aligned16(packed[i]) || !aligned16(out[i])) return UAMD_ERR_ALIGN;
+        m.seg[i] = TripSeg{packed[i], AbsmaxSrc{absmax_f32[i], nullptr, nullptr, nullptr, 0.f, 1},
+                           nf4_lut ? nf4_lut[i] : nullptr, out[i], numel[i]};
     }
     m.nseg = nseg;
-    int shift = 0;
-    while ((8 << shift) < blocksize) ++shift;
-    // whole trips spread evenly over at most 8 blocks per CU, as the single launch does
-    const int64_t per_block = (total + 2047) / 2048;
-    const unsigned grid = (unsigned)((total + per_block - 1) / per_block);
-    hipStream_t st = (hipStream_t)stream;
-    if (out_dtype == UAMD_BF16)
-        hipLaunchKernelGGL((nf4_dequant_x4_multi_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, m, shift, per_block);
-    else
-        hipLaunchKernelGGL((nf4_dequant_x4_multi_kernel<f16_t>), dim3(grid), dim3(256), 0, st, m, shift, per_block);
-    return uamd_launch_status();
+    UAMD_DISPATCH_HALF(out_dtype, return launch_trips<T>(m, blocksize, (hipStream_t)stream))
+    return UAMD_ERR_DTYPE;
 }
 
+// Blockwise NF4 quantiser (first-level only; the 8-bit nested quantisation of absmax is host
+// logic, see unsloth_amd/nf4.py). blocksize: power of two in [8, 512].
 extern "C" int uamd_nf4_quantize(const void* in, uint8_t* packed, float* absmax, int64_t n,
                                  int blocksize, int in_dtype, void* stream) {
     if (n < 0 || blocksize < 8 || blocksize > 512 || (blocksize & (blocksize - 1))) return UAMD_ERR_ARG;
