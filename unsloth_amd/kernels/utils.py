@@ -39,6 +39,8 @@ GEMM256_MODE = "auto"
 GEMM256_MIN_TILES = 160
 # X @ A^T / dY @ B: streaming LDS-DMA kernel (csrc/lora_side.hip) for total rank <= 64, else the first version
 LORA_XA_V2 = True
+# rank columns of one uamd_lora_xa launch (csrc/gemm.hip: twelve 16-rank tiles); wider stacks go in chunks (lora_xa)
+LORA_XA_MAX_RANKS = 192
 
 
 def calculate_settings(n):
@@ -469,9 +471,9 @@ def rank_block_bk(members, rows, width, transposed, dtype, by_rows=False):
 
 
 def lora_xa(X2d, A_list, out=None, out_k=None, k_cols=0):
-    """XA_g = X @ A_g^T for every projection sharing X, ONE launch. fp32, each block of columns
-    padded to a multiple of 8. Returns (buffer, [(col_offset, R_padded)]). `out`: optional fp32 [M, sum Rp]
-    destination with unit column stride (e.g. a column slice of a wider buffer). `out_k` (activation dtype, unit
+    """XA_g = X @ A_g^T for every projection sharing X, ONE launch (one per LORA_XA_MAX_RANKS rank columns past
+    that width). fp32, each block of columns padded to a multiple of 8. Returns (buffer, [(col_offset, R_padded)]).
+    `out`: optional fp32 [M, sum Rp] destination with unit column stride (e.g. a column slice of a wider buffer). `out_k` (activation dtype, unit
     column stride) additionally receives the sums rounded to the activation dtype, zero-filled up to `k_cols`
     columns: the XK operand of the GEMM's rank-block K tiles."""
     dtype = X2d.dtype
@@ -497,14 +499,21 @@ def lora_xa(X2d, A_list, out=None, out_k=None, k_cols=0):
         else:
             Acat = _cat()
     Rt = Acat.shape[0]
-    if Rt > 192:
-        raise NotImplementedError(f"sum of LoRA ranks sharing one input = {Rt} > 192")
     if out is None:
         out = torch.empty((X2d.shape[0], Rt), dtype=torch.float32, device=X2d.device)
     else:
         assert out.dtype == torch.float32 and tuple(out.shape) == (X2d.shape[0], Rt) and out.stride(1) == 1 \
             and out.stride(0) % 4 == 0
-    if out_k is not None:
+    if Rt > LORA_XA_MAX_RANKS:
+        # r = 128 on gate|up (256 rank columns) or on q|k|v (384): one launch takes LORA_XA_MAX_RANKS rows of the stacked
+        # factors, so they go in row chunks (whole 8-rank blocks), each launch writing its own columns of `out`
+        assert out_k is None, "the rank-block output takes <= 64 ranks per launch (_xa_and_rank_block groups them)"
+        if not _aligned_rows(Acat):
+            Acat = _aligned_copy(Acat)
+        for c0 in range(0, Rt, LORA_XA_MAX_RANKS):
+            rc = min(LORA_XA_MAX_RANKS, Rt - c0)
+            lora_xa(X2d, [Acat[c0:c0 + rc]], out=out[:, c0:c0 + rc])
+    elif out_k is not None:
         assert Rt <= 64 and out_k.dtype == dtype and out_k.stride(1) == 1 and k_cols >= Rt
         _lib.call("uamd_lora_xa2k", X2d, _lib.ptr(X2d), X2d.stride(0), _lib.ptr(Acat), Acat.stride(0), _lib.ptr(out),
                   out.stride(0), _lib.ptr(out_k), out_k.stride(0), k_cols, X2d.shape[0], K, Rt, Rt,
