@@ -527,6 +527,34 @@ int uamd_attn_decode_fused(const void* qkv, int64_t ld_qkv, const void* cos_t, c
  * against 46 us for torch's reduction. Workspaces: ws_val rows * 64 floats, ws_idx rows * 64 int64. */
 int uamd_argmax_f32(const float* x, int rows, int64_t n, float* ws_val, int64_t* ws_idx, int64_t* out, void* stream);
 
+/* Sampled next token of a decode step, one launch, one 1024-thread workgroup per row (csrc/sampler.hip): HF's warpers in HF's
+ * order -- temperature, top-k, top-p, min-p -- and the draw that `torch.multinomial` makes in HF's generate.
+ * logits: fp32 [rows, V], row stride `ld` elements (ld >= V, or 0: every row reads the same logits); 1 <= V <= 2^18.
+ * params: DEVICE block, read by the launch (a captured launch follows a change of settings). ctr: DEVICE 64-bit draw counter,
+ *   read only; the caller advances it between launches. u_in: optional fp32 [rows]; when given it replaces the generator
+ *   (ctr may then be NULL).
+ * With z_i = x_i / T (IEEE fp32 division; -inf, +inf and NaN are never kept) the kept set is {i : z_i >= max of}
+ *   top-k  (0 < top_k < V): the top_k-th largest z; ties with it stay;
+ *   top-p  (top_p < 1): over the top-k survivors with p = softmax over them, a token goes iff the mass of all survivors with
+ *          z <= its own (itself and its ties included) is <= 1 - top_p; a tied group stays or goes whole, the largest z stays;
+ *   min-p  (min_p > 0): z_max + ln(min_p), i.e. p_i >= min_p * p_max.
+ * Weights w_i = exp(z_i - z_max), W = their sum over the kept set; the token is the smallest kept index j whose inclusive
+ * prefix sum over kept i <= j exceeds u W. u = (x0 >> 8) * 2^-24 with x0 the first word of Philox4x32-10 on counter
+ * (ctr low, ctr high, row, 0) and key (seed low, seed high): one draw per row per launch.
+ * Masses are summed as 64-bit fixed point (w * 2^45, at least 1) with integer adds only: the result is bit-reproducible from
+ * run to run. out: int64 [rows], always in [0, V); a row with nothing finite gives 0 (kept 0, threshold NaN). Optional (NULL):
+ * kept_out int32 [rows] = size of the kept set, thresh_out fp32 [rows] = its smallest z, u_out fp32 [rows] = the u used. */
+typedef struct {
+    float temperature;        /* > 0 (anything else is taken as 1) */
+    int top_k;
+    float top_p;
+    float min_p;
+    uint64_t seed;
+} uamd_sample_params;
+int uamd_sample_f32(const float* logits, int64_t ld, int rows, int V, const uamd_sample_params* params,
+                    const uint64_t* ctr, const float* u_in, int64_t* out, int* kept_out, float* thresh_out,
+                    float* u_out, void* stream);
+
 /* uamd_lora_xa2: same contract as uamd_lora_xa for R <= 64, streaming version (csrc/lora_side.hip): 32 rows per
  * block, K split over 4 waves, X and W through a per-wave LDS-DMA ring, fixed-order reduction. */
 int uamd_lora_xa2(const void* X, int64_t ldx, const void* A, int64_t lda, float* out,

@@ -3,6 +3,7 @@
 128) or tinyllama (TinyLlama-1.1B: hidden 2048, intermediate 5632, 22 layers, 32 / 4 heads, head_dim 64, vocab 32000).
 
     python tools/decode_bench.py [--shape llama3-8b] [--layers 32] [--context 2048] [--new 64] [--out decode.jsonl]
+    python tools/decode_bench.py --sampler [--out sampler.jsonl]     the device sampler: launch and sampled step
 """
 import argparse
 import json
@@ -62,6 +63,81 @@ def attn_head_dim_ab(context, emit, rounds=7):
                       frac_hbm=round(byts / (v[len(v) // 2] * 1e-6) / HBM, 3)))
 
 
+def _spread(us):
+    v = sorted(us)
+    return dict(median=round(v[len(v) // 2], 3), min=round(v[0], 3), max=round(v[-1], 3))
+
+
+def sampler_ab(V, emit, rounds=7, T=0.8, top_k=50, top_p=0.9, min_p=0.05):
+    """The sampler launch against the torch chain generate() ran per token before it (division, filter_logits with its topk and
+    full sort, softmax, multinomial -- that chain had no min-p; the launch has it on), [1, V] and [8, V], rounds interleaved in one
+    process."""
+    from unsloth_amd.kernels import decode as D
+    from unsloth_amd.models.decode import filter_logits
+    dev = "cuda"
+    for rows in (1, 8):
+        lg = 4.0 * torch.randn(rows, V, device=dev)
+        prm = D.sample_params(dev, T, top_k, top_p, min_p, seed=1)
+        ctr = torch.zeros(1, dtype=torch.int64, device=dev)
+        out = torch.empty(rows, dtype=torch.long, device=dev)
+        gen = torch.Generator(dev).manual_seed(1)
+        fns = dict(kernel=lambda: D.sample_f32(lg, prm, ctr, out=out),
+                   torch=lambda: torch.multinomial(torch.softmax(filter_logits(lg / max(T, 1e-6), top_k, top_p), dim=-1), 1,
+                                                   generator=gen).view(-1))
+        us = {k: [] for k in fns}
+        for _ in range(rounds):
+            for k, fn in fns.items():
+                us[k].append(timeit(fn, n=50))
+        emit(dict(kernel="sampler launch against the torch chain", rows=rows, V=V, temperature=T, top_k=top_k, top_p=top_p,
+                  min_p_kernel_only=min_p, rounds=rounds, kernel_us=_spread(us["kernel"]), torch_us=_spread(us["torch"]),
+                  kernel_is_faster_beyond_the_spread=max(us["kernel"]) < min(us["torch"])))
+
+
+def sampled_step_ab(eng, emit, steps, rounds=5, T=0.8, top_k=50, top_p=0.9, min_p=0.05):
+    """ms per token of the sampled step against the greedy step, both replayed hipGraphs of one engine, rounds interleaved; every
+    round starts at the same cache length."""
+    kv0 = eng.kv_len.clone()
+    tok = torch.zeros(1, dtype=torch.long, device=eng.dev)
+    ms = dict(greedy=[], sampled=[])
+    for r in range(rounds + 1):                          # round 0 captures and warms both graphs
+        for mode in ("greedy", "sampled"):
+            if mode == "greedy":
+                eng.sampling()
+            else:
+                eng.sampling(T, top_k, top_p, min_p, seed=r)
+            eng.kv_len.copy_(kv0)
+            eng.step(tok)
+            torch.cuda.synchronize()
+            t0 = time.time()
+            for _ in range(steps):
+                eng.step(eng.next_tok)
+            torch.cuda.synchronize()
+            if r:
+                ms[mode].append((time.time() - t0) / steps * 1e3)
+    eng.sampling()
+    g, s = _spread(ms["greedy"]), _spread(ms["sampled"])
+    emit(dict(metric="decode ms per token, sampled against greedy step, hipGraph, batch 1", layers=len(eng.core.layers),
+              context=int(kv0[0]), steps=steps, rounds=rounds, temperature=T, top_k=top_k, top_p=top_p, min_p=min_p,
+              greedy_ms=g, sampled_ms=s, sampled_minus_greedy_us=round((s["median"] - g["median"]) * 1e3, 1)))
+
+
+def whole_model(a, dev):
+    """The benchmark's synthetic Llama-shaped QLoRA model (NF4, r = 16 on every projection, random B factors)."""
+    import bench as B                                   # the benchmark's synthetic Llama-3-8B-shaped config
+    from unsloth_amd import FastLanguageModel
+    cfg = B.llama3_8b_config(a.layers) if a.shape == "llama3-8b" else B.tinyllama_1b_config(a.layers)
+    model, _ = FastLanguageModel.from_pretrained(config=cfg, max_seq_length=a.context, dtype=torch.bfloat16, load_in_4bit=True,
+                                                 device=torch.device(dev), random_state=3407, use_gradient_checkpointing=False)
+    model = FastLanguageModel.get_peft_model(model, r=16, lora_alpha=16, lora_dropout=0.0, bias="none",
+                                             use_gradient_checkpointing=False, random_state=3407)
+    gg = torch.Generator(device="cpu").manual_seed(3407)
+    for n, p in model.named_parameters():
+        if "lora_B" in n:
+            p.data.copy_((torch.randn(p.shape, generator=gg) * 0.02).to(p.device))
+    model.eval()
+    return model
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", choices=sorted(SHAPES), default="llama3-8b")
@@ -71,6 +147,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="whole model, hipGraph step only (for a rocprofv3 kernel trace)")
     ap.add_argument("--attn-ab", action="store_true", help="only the fused attention launch, head_dim 64 against 128")
+    ap.add_argument("--sampler", action="store_true",
+                    help="only the sampler: its launch against the torch chain, and the sampled against the greedy hipGraph step")
     a = ap.parse_args()
     H, I, L0, Hq, Hk, Dh, V = SHAPES[a.shape]
     if a.layers is None:
@@ -85,6 +163,12 @@ def main():
 
     if a.attn_ab:
         return attn_head_dim_ab(a.context, emit)
+    if a.sampler:
+        from unsloth_amd.models.decode import DecodeEngine
+        sampler_ab(V, emit)
+        eng = DecodeEngine(whole_model(a, "cuda"), max_seq_len=a.context, batch=1, use_graph=True)
+        eng.prefill(torch.randint(0, 32000, (1, a.context - a.new), device="cuda"))
+        return sampled_step_ab(eng, emit, steps=a.new - 4)
     from unsloth_amd.kernels import decode as D
     from unsloth_amd.nf4 import quantize_nf4
     dev, bf = "cuda", torch.bfloat16
@@ -163,20 +247,9 @@ def main():
     del W
 
     # ---- whole model
-    import bench as B                                   # the benchmark's synthetic Llama-3-8B-shaped config
-    from unsloth_amd import FastLanguageModel
     from unsloth_amd.models import decode as MD
     from unsloth_amd.models.decode import DecodeEngine
-    cfg = B.llama3_8b_config(a.layers) if a.shape == "llama3-8b" else B.tinyllama_1b_config(a.layers)
-    model, _ = FastLanguageModel.from_pretrained(config=cfg, max_seq_length=a.context, dtype=torch.bfloat16, load_in_4bit=True,
-                                                 device=torch.device(dev), random_state=3407, use_gradient_checkpointing=False)
-    model = FastLanguageModel.get_peft_model(model, r=16, lora_alpha=16, lora_dropout=0.0, bias="none",
-                                             use_gradient_checkpointing=False, random_state=3407)
-    gg = torch.Generator(device="cpu").manual_seed(3407)
-    for n, p in model.named_parameters():
-        if "lora_B" in n:
-            p.data.copy_((torch.randn(p.shape, generator=gg) * 0.02).to(p.device))
-    model.eval()
+    model = whole_model(a, dev)
     ids = torch.randint(0, 32000, (1, a.context - a.new), device=dev)
     for fused, graph in ((True, True),) if a.quick else ((True, True), (False, True), (True, False), (False, False)):
         MD.FUSED_STEP = fused

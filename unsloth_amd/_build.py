@@ -29,6 +29,7 @@ SOURCES = [
     "lora_side.hip",
     "attention.hip",
     "decode.hip",
+    "sampler.hip",
     "adamw.hip",
 ]
 

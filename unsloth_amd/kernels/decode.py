@@ -333,3 +333,52 @@ def argmax_f32(logits, out=None, ws=None):
     _lib.call("uamd_argmax_f32", logits, _lib.ptr(logits), rows, n, _lib.ptr(ws[0]), _lib.ptr(ws[1]), _lib.ptr(out),
               _lib.stream_of(logits))
     return out
+
+
+SAMPLE_MAX_V = 1 << 18                # uamd_sample_f32: 2^18 fixed-point masses cannot overflow 64 bits
+
+
+def sample_params(device=None, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, seed=None, out=None):
+    """The device parameter block of `sample_f32` (uamd_sample_params: fp32 temperature, int32 top_k, fp32 top_p, fp32 min_p,
+    uint64 seed) as an int32 [6] tensor; `out` updates an existing block in place, so a launch captured in a hipGraph follows
+    the new settings. `seed`: a python int (any 64 bits), an int64 tensor of one element on any device (copied without a
+    sync when it is on the block's device), or None = leave the seed as it is (0 in a new block)."""
+    import numpy as np
+    if not float(temperature) > 0.0:
+        raise ValueError(f"temperature must be positive (got {temperature})")
+    if out is None:
+        out = torch.zeros(6, dtype=torch.int32, device=device)
+    host = np.zeros(1, dtype=np.dtype([("t", "<f4"), ("k", "<i4"), ("p", "<f4"), ("m", "<f4")]))
+    host[0] = (float(temperature), int(top_k or 0), float(1.0 if top_p is None else top_p), float(min_p or 0.0))
+    out[:4].copy_(torch.from_numpy(host.view(np.int32)))
+    if seed is not None:
+        if not torch.is_tensor(seed):
+            s = int(seed) & ((1 << 64) - 1)
+            seed = torch.tensor([s - (1 << 64) if s >= (1 << 63) else s], dtype=torch.int64)
+        out.view(torch.int64)[2:3].copy_(seed.view(1))
+    return out
+
+
+def sample_f32(logits, params, ctr, out=None, ws=None, kept_out=None, thresh_out=None, u_out=None, u_in=None):
+    """Sampled next token (uamd_sample_f32): temperature -> top-k -> top-p -> min-p -> one draw per row, one launch.
+    logits fp32 [rows, V] with unit stride along V (row stride 0, an expanded row, is fine); `params` from `sample_params`;
+    `ctr` int64 [1] on the device, the draw counter (read only -- the caller advances it). Returns int64 [rows] (`out` is
+    reused when given). Optional outputs: kept_out int32 [rows] (size of the kept set), thresh_out fp32 [rows] (its smallest
+    scaled logit), u_out fp32 [rows] (the uniform number used); u_in fp32 [rows] replaces the generator. `ws` is accepted for
+    the calling convention of `argmax_f32` and unused: the launch needs no device workspace."""
+    _lib.require_gpu(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and (logits.shape[1] == 1 or logits.stride(1) == 1)
+    rows, V = logits.shape
+    ld = logits.stride(0) if rows > 1 else V
+    assert ld == 0 or ld >= V
+    dev = logits.device
+    assert params.dtype == torch.int32 and params.numel() >= 6 and params.device == dev and params.is_contiguous()
+    assert u_in is not None or (ctr is not None and ctr.dtype == torch.int64 and ctr.device == dev)
+    if out is None:
+        out = torch.empty(rows, dtype=torch.long, device=dev)
+    for t, dt in ((out, torch.long), (kept_out, torch.int32), (thresh_out, torch.float32), (u_out, torch.float32),
+                  (u_in, torch.float32)):
+        assert t is None or (t.dtype == dt and t.numel() >= rows and t.is_contiguous() and t.device == dev)
+    _lib.call("uamd_sample_f32", logits, _lib.ptr(logits), ld, rows, V, _lib.ptr(params), _lib.ptr(ctr), _lib.ptr(u_in),
+              _lib.ptr(out), _lib.ptr(kept_out), _lib.ptr(thresh_out), _lib.ptr(u_out), _lib.stream_of(logits))
+    return out

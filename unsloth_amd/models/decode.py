@@ -10,8 +10,9 @@ MI355X design: one `DecodeEngine` per (model, max_seq_len, batch):
   * a token step of one sequence is FIVE launches per layer -- q|k|v GEMV (residual add + RMSNorm inside), attention (RoPE,
     cache append, split-KV attention and its combine inside), o GEMV, gate|up GEMV (residual add + RMSNorm in, SwiGLU out),
     down GEMV; every LoRA `A x` is computed once inside the GEMV launch that needs it (uamd_gemv_fused) -- that read the
-    position from DEVICE memory, so the whole step -- all layers, final norm, lm_head GEMV, greedy argmax, position
-    increment -- is captured once as a hipGraph and replayed per token. (Rounds 2-3: 14 launches per layer, ~450 kernels
+    position from DEVICE memory, so the whole step -- all layers, final norm, lm_head GEMV, greedy argmax (or, when sampling,
+    the temperature / top-k / top-p / min-p draw of uamd_sample_f32 and its draw counter), position increment -- is captured
+    once as a hipGraph and replayed per token. (Rounds 2-3: 14 launches per layer, ~450 kernels
     of ~9 us for ~0.6 ms of HBM traffic; still the batch > 1 path and `UNSLOTH_AMD_DECODE_FUSED=0`.);
   * prefill runs the training-path kernels (flash attention over the prompt) and writes K (post-RoPE) / V into the cache.
 Batch > 1 decodes through the fused NF4 GEMM instead of the GEMV (as the reference does, utils.py:1095-1097).
@@ -97,7 +98,14 @@ class DecodeEngine:
         assert 5 * L + 1 < 1024, "hand-off tag sites: 5 per layer below UAMD_TAG_STRIDE"
         self._params = [self._layer_params(l) for l in self.core.layers]
         self._head = self.lm.lm_head.weight
+        # sampling: None = the steps pick next_tok greedily; otherwise (`sampling()`) they draw it with uamd_sample_f32 from the
+        # DEVICE parameter block and draw counter below -- settings, seed and counter change in place, so the captured sampled
+        # step (a capture of its own beside the greedy one) follows them. The counter is the engine's and starts at 0 in every
+        # generate(): the hand-off step counter never resets and would make equal seeds give different tokens
         self._sample = None
+        self._sparams = _dk.sample_params(self.dev)
+        self._draw_ctr = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self._graph_s = None
 
     # ---- per-layer parameter tuples, read once (adapters must not be switched under a live engine) -------------------
     @staticmethod
@@ -132,7 +140,7 @@ class DecodeEngine:
                     sig += [t.data_ptr() for pr in P[grp] for t in pr[:4] if torch.is_tensor(t)]
             sig = tuple(sig)
             if getattr(self, "_ptr_sig", None) != sig:
-                self._graph = None
+                self._graph = self._graph_s = None
                 self._ptr_sig = sig
         core = self.core
         h = core.embed_tokens(input_ids.to(self.dev)).to(self.dtype)
@@ -175,6 +183,29 @@ class DecodeEngine:
             _dk.argmax_f32(lg, out=self.next_tok, ws=self._amax_ws)
         else:
             self.next_tok.copy_(torch.argmax(lg, dim=-1))
+
+    def sampling(self, temperature=None, top_k=0, top_p=1.0, min_p=0.0, seed=None):
+        """`sampling()`: greedy steps. `sampling(temperature, top_k, top_p, min_p, seed)`: from now on `draw()` and every step
+        sample next_tok -- HF's warpers in HF's order, then one Philox draw per row at (seed, draw counter, row) -- and the
+        draw counter starts over at 0. `seed`: python int or int64 device tensor of one element (no sync); None keeps it."""
+        if temperature is None:
+            self._sample = None
+            return
+        V = self._head.shape[0]
+        if V > _dk.SAMPLE_MAX_V:
+            raise NotImplementedError(f"uamd_sample_f32 samples vocabularies up to {_dk.SAMPLE_MAX_V} entries (got {V})")
+        _dk.sample_params(temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed, out=self._sparams)
+        self._draw_ctr.zero_()
+        self._sample = True
+
+    def draw(self):
+        """next_tok ~ the current logits (of `prefill` or of the last step) at the current draw counter, which advances by one.
+        The step bodies call it where the greedy step calls `_greedy()`; generate() calls it once, eagerly, after prefill."""
+        lg = self.logits
+        assert lg.dtype == torch.float32 and lg.stride(-1) == 1
+        _dk.sample_f32(lg, self._sparams, self._draw_ctr, out=self.next_tok)
+        self._draw_ctr.add_(1)
+        return self.next_tok
 
     def _lm_head(self, x):                       # x [B, H] -> fp32 logits [B, V]
         W = self._head
@@ -250,6 +281,8 @@ class DecodeEngine:
         self._pos.add_(1)                                   # positions and the step counter
         if self._sample is None:
             self._greedy()
+        else:
+            self.draw()
         return self.logits
 
     @torch.no_grad()
@@ -284,6 +317,8 @@ class DecodeEngine:
         self._pos.add_(1)                                   # positions and the step counter
         if self._sample is None:
             self._greedy()
+        else:
+            self.draw()
         return self.logits
 
     def step(self, token_ids):
@@ -297,28 +332,43 @@ class DecodeEngine:
             self._steps = 1
         if not self.use_graph:
             return self._step_body()
-        if self._graph is None:
+        # the greedy step and the sampled step are two captures (argmax against the draw and its counter); which one replays
+        # follows `sampling()`, what the sampled one draws with follows the device parameter block
+        g, gl = ("_graph", "_graph_logits") if self._sample is None else ("_graph_s", "_graph_s_logits")
+        if getattr(self, g) is None:
             # eager warm-up (first-use attribute calls, allocator growth), with the position restored afterwards
-            kv0 = self.kv_len.clone()
+            kv0, ctr0 = self.kv_len.clone(), self._draw_ctr.clone()
             self._step_body()
             self.kv_len.copy_(kv0)
             torch.cuda.synchronize()
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
                 self._step_body()
-            self._graph_logits = self.logits     # the graph's static output buffer (prefill() rebinds self.logits)
+            setattr(self, g, graph)
+            setattr(self, gl, self.logits)       # the graph's static output buffer (prefill() rebinds self.logits)
             self.kv_len.copy_(kv0)               # the capture itself does not execute
-        self._graph.replay()
-        self.logits = self._graph_logits
+            self._draw_ctr.copy_(ctr0)
+        getattr(self, g).replay()
+        self.logits = getattr(self, gl)
         return self.logits
 
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens=32, eos_token_id=None, do_sample=False, temperature=1.0, top_k=0,
-                 generator=None, pad_token_id=None, top_p=1.0):
-        """Greedy (default) or temperature / top-k / nucleus sampling. Returns [B, T + new] token ids. Rows that have produced
-        an end-of-sequence token keep emitting `pad_token_id` (default: the first eos id), like HF's generate."""
+                 generator=None, pad_token_id=None, top_p=1.0, min_p=0.0):
+        """Greedy (default) or temperature / top-k / top-p / min-p sampling. Returns [B, T + new] token ids. Rows that have
+        produced an end-of-sequence token keep emitting `pad_token_id` (default: the first eos id), like HF's generate.
+        Sampling happens on the device (uamd_sample_f32): one 64-bit seed per call is drawn from `generator` (the default
+        generator of its device when None) without a sync, the first token is drawn from the prefill logits at draw 0 and every
+        later one inside the token step, so equally seeded generators give equal tokens."""
         input_ids = input_ids.to(self.dev)
         logits = self.prefill(input_ids)
+        if do_sample:
+            gdev = generator.device if generator is not None else self.dev
+            seed = torch.randint(-(1 << 63), (1 << 63) - 1, (1,), dtype=torch.int64, device=gdev, generator=generator)
+            self.sampling(max(temperature, 1e-6), top_k, top_p, min_p, seed=seed)
+            self.draw()
+        else:
+            self.sampling()
         out = [input_ids]
         eos = None if eos_token_id is None else sorted(set(eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id]))
         eos_t = None if eos is None else torch.tensor(eos, device=self.dev)
@@ -333,8 +383,7 @@ class DecodeEngine:
         for i in range(min(max_new_tokens, room)):
             poison += logits[:, 0].float() * 0.0
             if do_sample:
-                lg = filter_logits(logits / max(temperature, 1e-6), top_k, top_p)
-                nxt = torch.multinomial(torch.softmax(lg, dim=-1), 1, generator=generator).view(-1)
+                nxt = self.next_tok.clone()                  # drawn from `logits` already: after prefill, or inside the step
             else:
                 nxt = torch.argmax(logits, dim=-1)
             if eos_t is not None:
@@ -346,6 +395,7 @@ class DecodeEngine:
                     break
             if i + 1 < min(max_new_tokens, room):
                 logits = self.step(nxt)
+        self.sampling()
         if bool(torch.isnan(poison).any()):
             raise RuntimeError("unsloth_amd decode: non-finite logits -- an in-launch hand-off of the fused decode step timed out "
                                "(not every workgroup of a launch was resident: a CU-masked / shared GPU?) or the model produced "
@@ -353,11 +403,12 @@ class DecodeEngine:
         return torch.cat(out, dim=1)
 
 
-def filter_logits(logits, top_k=0, top_p=1.0):
-    """HF's warper order and rules (generation/logits_process.py TopKLogitsWarper, TopPLogitsWarper) on [B, V] logits: keep the
-    top_k largest (ties with the k-th stay), then the smallest set of most probable tokens whose mass reaches top_p -- a
-    token goes when the cumulative probability of it and everything LESS likely is <= 1 - top_p; the most likely token
-    always stays. Everything else becomes -inf."""
+def filter_logits(logits, top_k=0, top_p=1.0, min_p=0.0):
+    """HF's warper order and rules (generation/logits_process.py TopKLogitsWarper, TopPLogitsWarper, MinPLogitsWarper) on
+    [B, V] logits: keep the top_k largest (ties with the k-th stay), then the smallest set of most probable tokens whose mass
+    reaches top_p -- a token goes when the cumulative probability of it and everything LESS likely is <= 1 - top_p; the most
+    likely token always stays -- then the tokens whose probability is at least min_p times the largest one. Everything else
+    becomes -inf. The host statement of what uamd_sample_f32 keeps (the engine samples on the device and does not call this)."""
     if top_k and top_k < logits.shape[-1]:
         kth = torch.topk(logits, int(top_k), dim=-1).values[..., -1:]
         logits = logits.masked_fill(logits < kth, float("-inf"))
@@ -366,6 +417,11 @@ def filter_logits(logits, top_k=0, top_p=1.0):
         drop = ascending.softmax(dim=-1).cumsum(dim=-1) <= (1.0 - float(top_p))
         drop[..., -1:] = False
         logits = logits.masked_fill(drop.scatter(-1, order, drop), float("-inf"))
+    if min_p is not None and min_p > 0.0:
+        probs = logits.softmax(dim=-1)
+        drop = probs < float(min_p) * probs.max(dim=-1, keepdim=True).values
+        drop.scatter_(-1, logits.argmax(dim=-1, keepdim=True), False)
+        logits = logits.masked_fill(drop, float("-inf"))
     return logits
 
 
@@ -377,14 +433,14 @@ def _eps(norm):
 # return, so such calls go to the original `generate` (kept as `model._old_generate` by for_inference) instead of being
 # silently ignored
 _ENGINE_KWARGS = {"max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "do_sample", "temperature", "top_k", "top_p",
-                  "attention_mask", "use_cache", "generator", "max_seq_len", "return_dict_in_generate", "output_scores",
+                  "min_p", "attention_mask", "use_cache", "generator", "max_seq_len", "return_dict_in_generate", "output_scores",
                   "generation_config", "tokenizer"}
 
 
 def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_len=None, **kwargs):
     """llama.py:2167-2259 counterpart: `model.generate(...)` after `FastLanguageModel.for_inference(model)`.
-    The reference forwards every keyword to HF's generate; the engine covers greedy / temperature / top-k / top-p decoding of
-    unpadded batches. Calls outside that (repetition_penalty, beams, streamers, logits processors, a padded
+    The reference forwards every keyword to HF's generate; the engine covers greedy / temperature / top-k / top-p / min-p
+    decoding of unpadded batches. Calls outside that (repetition_penalty, beams, streamers, logits processors, a padded
     attention_mask, ...) are handed to HF's own generate (`model._old_generate`) -- or raise when it is unavailable."""
     input_ids = kwargs.pop("inputs", input_ids)
     attention_mask = kwargs.get("attention_mask", None)
@@ -416,7 +472,7 @@ def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_le
     if pad is None and gen_cfg is not None:
         pad = getattr(gen_cfg, "pad_token_id", None)
     # Sampling defaults come from the model's generation_config like in HF's generate (a checkpoint that ships
-    # do_sample=True / temperature / top_k / top_p -- Llama-3-Instruct's does -- samples without the caller saying so);
+    # do_sample=True / temperature / top_k / top_p / min_p -- Llama-3-Instruct's does -- samples without the caller saying so);
     # explicit keywords win.
     def gen_default(name, fallback):
         if name in kwargs and kwargs[name] is not None:
@@ -427,13 +483,14 @@ def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_le
     temperature = float(gen_default("temperature", 1.0))
     top_k = int(gen_default("top_k", 0) or 0) if do_sample else 0
     top_p = float(gen_default("top_p", 1.0)) if do_sample else 1.0
+    min_p = float(gen_default("min_p", 0.0) or 0.0) if do_sample else 0.0
     need = input_ids.shape[1] + max_new_tokens
     eng = getattr(model, "_uamd_decode_engine", None)
     if eng is None or eng.B != input_ids.shape[0] or eng.S < need:
         eng = DecodeEngine(model, max_seq_len=max(need, max_seq_len or 0), batch=input_ids.shape[0])
         model._uamd_decode_engine = eng
     return eng.generate(input_ids, max_new_tokens=max_new_tokens, eos_token_id=eos,
-                        do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                        do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p,
                         generator=kwargs.get("generator", None), pad_token_id=pad)
 
 
