@@ -198,9 +198,10 @@ int uamd_glu_bwd_tn_ws(const void* DW, void* e, void* g, int M, int K, int64_t l
 /* ---------------------------------------------------------------------------------------------
  * Cross entropy.  Replaces cross_entropy_loss.py:35-111 / :114-199 (+ host logsumexp :366-370) and
  * :202-285, as launched by Fast_CrossEntropyLoss (:288-418).  No vocabulary-size limit.
- *   forward : logsumexp[row], loss[row] = logsumexp - x[label]  (0 when label == -100)
+ *   forward : logsumexp[row], loss[row] = logsumexp - x[label]  (0 when label == -100 or outside [0, vocab_size))
  *   backward: logits <- dloss[row] * (softmax - onehot) (x scale, x (1 - tanh^2) for softcap),
- *             IN PLACE over logits (:276, :413-418); rows with label == -100 become zeros.
+ *             IN PLACE over logits (:276, :413-418); rows with label == -100 or outside [0, vocab_size) -- the rows
+ *             whose loss the forward reports as 0 -- become zeros.
  *   logprob_entropy_forward (the RL log-prob path): the forward's one pass, writing
  *             logprob[row] = x[index] - logsumexp (0 when index == -100 or out of range), logsumexp[row]
  *             exactly as forward writes it (backward consumes it unchanged), and

@@ -18,7 +18,8 @@
 // is the same expressions in both instantiations: lse and the selected logit are the same bits with or without it.
 //
 // Integer semantics that must stay exact: label == -100 -> loss 0 and zero gradient row;
-// the "- 1" lands exactly on column == label.
+// the "- 1" lands exactly on column == label. A label outside [0, vocab) is treated like -100 in BOTH directions:
+// loss (log-prob) 0 and a zero gradient row -- the backward never returns the gradient of a loss the forward did not report.
 #include "common.h"
 
 namespace {
@@ -172,7 +173,8 @@ ce_bwd_kernel(T* logits, int64_t row_stride, const float* __restrict__ dloss, in
     const int64_t row = blockIdx.x;
     T* x = logits + row * row_stride;
     const int64_t label = labels[row];
-    const float dl = (label != -100) ? dloss[row * dloss_stride] : 0.0f;  // :238-241
+    // the forward's own condition (:238-241 knows -100 only): a row whose loss was reported as 0 has no gradient
+    const float dl = (label >= 0 && label < vocab) ? dloss[row * dloss_stride] : 0.0f;
     const float l = lse[row];
     const int c0 = blockIdx.y * chunk;
     const int c1 = min(c0 + chunk, vocab);
@@ -280,7 +282,8 @@ extern "C" int uamd_logprob_entropy_forward(const void* logits, int64_t logits_r
     return UAMD_ERR_DTYPE;
 }
 
-// logits <- dloss[row] * d(loss)/d(logits), in place (same dtype as logits).
+// logits <- dloss[row] * d(loss)/d(logits), in place (same dtype as logits); a zero row where the label is -100 or
+// outside [0, vocab_size).
 extern "C" int uamd_cross_entropy_backward(void* logits, int64_t logits_row_stride,
                                            const float* dloss, int64_t dloss_stride,
                                            const float* logsumexp, const int64_t* labels,

@@ -9,6 +9,8 @@ the fused linear + cross-entropy entry point the reference imports from unsloth_
   fast_cross_entropy_loss   (:421-449)  sum / n_items
   patch_loss_functions      (:459-473)  installs the fast loss into transformers' LOSS_MAPPING
 
+A label (index) outside [0, vocab) is treated like -100 in both directions: loss / log-prob 0 and a zero gradient row.
+
 Vocabulary size is unlimited here (one streaming launch), so the reference's split into a
 <=65536 kernel and a chunked kernel + host torch.logsumexp (:303-370) disappears; results are
 the same quantity (logsumexp over the whole row).
