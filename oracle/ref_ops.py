@@ -129,8 +129,10 @@ def _act(e, kind):
         b = a * 0.044715 * e * e
         T = 1.0 + torch.tanh(a + b)
         T2 = 0.5 * T
-        Q2 = -T2 * (T - 2.0) * (a + 3.0 * b)                               # geglu.py:221-225
-        return T2 * e, T2 + Q2
+        P = -T2 * (T - 2.0)
+        Q2 = P * (a + 3.0 * b)                                             # geglu.py:221-225
+        # saturated tanh: P = 0 exactly, and a + 3 b = inf from |e| ~ 7e12 on -- 0 * inf = NaN for a finite e (csrc/glu.hip)
+        return T2 * e, torch.where(P == 0, T2, T2 + Q2)
     raise ValueError(kind)
 
 
@@ -158,6 +160,21 @@ def glu_backward(DW, e, g, kind="swiglu"):
     else:
         de = dg * dfde
     return h.to(dt), df.to(dt), de.to(dt)
+
+
+def quick_gelu_forward(x):
+    """transformers' QuickGELUActivation, y = x * sigmoid(1.702 x): fp32 arithmetic, one rounding (csrc/glu.hip)."""
+    v = x.to(F32)
+    return (v * torch.sigmoid(1.702 * v)).to(x.dtype)
+
+
+def quick_gelu_backward(dy, x):
+    """dx = dy * (s + 1.702 x s (1 - s)), s = sigmoid(1.702 x): fp32, one rounding. Where s is exactly 0 or 1 the second term
+    is 0 -- and 0 * inf = NaN once 1.702 x overflows -- so the factor is s there (the kernel's select)."""
+    v = x.to(F32)
+    s = torch.sigmoid(1.702 * v)
+    d = torch.where((s == 0) | (s == 1), s, s + 1.702 * v * s * (1.0 - s))
+    return (dy.to(F32) * d).to(x.dtype)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -650,8 +650,16 @@ __global__ void __launch_bounds__(GEMV_THREADS, NIT <= 16 ? 4 : 2) gemv_kernel(G
                     if (p.g[1].bias) gg += to_f32(((const T*)p.g[1].bias)[n_s[r]]);
                     e = round_to<T>(e);
                     gg = round_to<T>(gg);
-                    const float f = e * uamd_sigmoid(e);
-                    ((T*)p.g[0].y)[n_s[r]] = from_f32<T>(round_to<T>(f) * gg);
+                    // fp16: each of the two scalar products stays an fp32 value of its own on its way to the conversion (an empty
+                    // asm, no instruction). hipcc otherwise folds product and conversion into v_fma_mixlo_f16 -- one rounding, and
+                    // -0 + 0 = +0 inside the fma: h came out as +0 where uamd_swiglu_fg returns -0 (every e <= -17 or so). The note
+                    // in front of fwd_one in glu.hip; tests/test_gpu_glu_sweep.py holds both SwiGLU sites of this file to that
+                    // kernel's bits on every 16-bit e.
+                    float f = e * uamd_sigmoid(e);
+                    if constexpr (std::is_same<T, f16_t>::value) asm("" : "+v"(f));
+                    float hv = round_to<T>(f) * gg;
+                    if constexpr (std::is_same<T, f16_t>::value) asm("" : "+v"(hv));
+                    ((T*)p.g[0].y)[n_s[r]] = from_f32<T>(hv);
                 }
             } else {
                 const void* gb = p.g[cgi].bias;

@@ -59,12 +59,21 @@ __device__ __forceinline__ void act_bwd(float e, float& f, float& dfde) {
         const float b = a * 0.044715f * e * e;
         const float T = 1.0f + tanhf(a + b);
         const float T2 = 0.5f * T;
-        const float Q2 = -T2 * (T - 2.0f) * (a + 3.0f * b);     // geglu.py:221-225
-        dfde = T2 + Q2;
+        const float P = -T2 * (T - 2.0f);
+        const float Q2 = P * (a + 3.0f * b);                    // geglu.py:221-225
+        // saturated tanh: P is exactly 0, and from |e| ~ 7e12 on b = inf, so Q2 would be 0 * inf = NaN for a finite e whose
+        // derivative is 1 or 0. Where P is 0 and a + 3 b finite, T2 + Q2 was T2 already: no finite result changes.
+        dfde = P == 0.0f ? T2 : T2 + Q2;
         f = T2 * e;
     }
 }
 
+// fp16: "f rounded to the dtype" means TWO roundings, fp32 then fp16, as the reference's `.to(dtype)` of an fp32 value. hipcc
+// would fold the last fp32 multiply of an element into the conversion -- v_fma_mixlo_f16, ONE rounding, and -0 + 0 = +0 inside
+// the fma -- wherever its SLP vectoriser did not pair the element with a neighbour: the scalar tail loops, six of the 80
+// elements of a fused-kernel tile, some GeGLU lanes. Such elements disagreed with the same value at another position on the
+// near-ties (about 1 in 10^4) and on the sign of a zero. This file is therefore built WITHOUT the mixed-precision fma
+// instructions (_build.FILE_FLAGS); every site then rounds twice. bf16 and fp32 code never used them.
 // one element of the forward: f is rounded to the activation dtype before the product, which is a product IN that dtype
 template <typename T, int ACT>
 __device__ __forceinline__ T fwd_one(T e, T g) {
@@ -97,12 +106,10 @@ __device__ __forceinline__ void bwd_one(T dw, T e, T g, T& h, T& df, T& de) {
 // grid-stride loop (one trip per block under an uncapped grid: the hardware dispatcher streams 256-thread blocks, which is
 // how the reference's Triton kernel reaches 6.0 TB/s on this shape). The elements past the last whole vector go to block 0.
 //
-// The forward writes its NV = 2 trip out as ONE PASS with a whole-trip and a one-vector branch instead of the loop, because
-// the last bit of fp16 GeGLU depends on it: where hipcc's SLP vectoriser pairs two elements, f = 0.5 e (1 + ..) is a
-// v_mul_f32 and a v_cvt_pk_f16_f32 (two roundings); where it does not, one v_fma_mixlo_f16 (one rounding) -- 1 element in
-// ~10^4 differs by an ulp, and which elements are paired follows the shape of the source. The loop form of NV = 2 pairs
-// none (it agrees with NV = 1 bit for bit); this form pairs what the two-vector kernel always paired, so every variant
-// returns what it returned before. SwiGLU and bf16 round the same way in every form.
+// The forward writes its NV = 2 trip out as ONE PASS with a whole-trip and a one-vector branch instead of the loop. (The form
+// dates from when the last bit of fp16 GeGLU depended on which elements hipcc's SLP vectoriser paired -- v_mul_f32 +
+// v_cvt_pk_f16_f32 against one v_fma_mixlo_f16; without those instructions, the note in front of fwd_one, every form and every
+// position returns the same bits, tests/test_gpu_glu_sweep.py.)
 template <typename T, int ACT, int NV>
 __global__ void __launch_bounds__(256)
 glu_fwd_kernel(const T* __restrict__ E, const T* __restrict__ G, T* __restrict__ H, int64_t n, int mode) {
@@ -1054,6 +1061,11 @@ extern "C" int uamd_glu_bwd_tn_ws(const void* DW, void* e, void* g, int M, int K
 // fp32 arithmetic, one rounding: forward y from x; backward dx = dy * (s + 1.702 x s (1 - s)), s = sigmoid(1.702 x), written IN
 // PLACE over dy (x is kept: fc1's output is what autograd saved anyway).
 namespace {
+// s + 1.702 x s (1 - s). Where the sigmoid is saturated (s = 0 or 1 exactly) the second term is 0 and the sum was s already --
+// unless 1.702 x overflowed (|x| >= 2.0e38, finite in bf16 and fp32): inf * 0 = NaN. The select returns s in both cases.
+__device__ __forceinline__ float quick_gelu_dydx(float v, float sg) {
+    return (sg == 0.0f || sg == 1.0f) ? sg : sg + 1.702f * v * sg * (1.0f - sg);
+}
 template <typename T, bool BWD>
 __global__ void __launch_bounds__(256) quick_gelu_kernel(const T* __restrict__ X, T* __restrict__ Y, int64_t n) {
     constexpr int VEC = Vec16<T>::N;
@@ -1065,7 +1077,7 @@ __global__ void __launch_bounds__(256) quick_gelu_kernel(const T* __restrict__ X
         for (int j = 0; j < VEC; ++j) {
             const float v = to_f32(x.e[j]);
             const float sg = uamd_sigmoid(1.702f * v);
-            if (BWD) y.e[j] = from_f32<T>(to_f32(y.e[j]) * (sg + 1.702f * v * sg * (1.0f - sg)));
+            if (BWD) y.e[j] = from_f32<T>(to_f32(y.e[j]) * quick_gelu_dydx(v, sg));
             else y.e[j] = from_f32<T>(v * sg);
         }
         st16_m(Y + i * VEC, y, 0);
@@ -1074,7 +1086,7 @@ __global__ void __launch_bounds__(256) quick_gelu_kernel(const T* __restrict__ X
         for (int64_t k = nvec * VEC + threadIdx.x; k < n; k += 256) {
             const float v = to_f32(X[k]);
             const float sg = uamd_sigmoid(1.702f * v);
-            Y[k] = from_f32<T>(BWD ? to_f32(Y[k]) * (sg + 1.702f * v * sg * (1.0f - sg)) : v * sg);
+            Y[k] = from_f32<T>(BWD ? to_f32(Y[k]) * quick_gelu_dydx(v, sg) : v * sg);
         }
     }
 }
