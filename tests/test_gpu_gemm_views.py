@@ -532,7 +532,9 @@ def test_xa_and_rank_block_on_a_padded_activation(calls, M, K, Rs):
     want = torch.cat([X.double() @ a.double().t() for a in As], dim=1)
     xpool, Xv = place(X, K + 64, 0, NAN)
     calls.clear()
-    xa, offs, xk = U._xa_and_rank_block(Xv, [a.to(DEV) for a in As], True)
+    terms = U._xa_and_rank_block(Xv, [a.to(DEV) for a in As], True)
+    xa, xk = torch.cat([t.P for t in terms], dim=1), terms[0].xk
+    assert all(t.xk is xk for t in terms) and [t.col for t in terms] == [sum(Rs[:i]) for i in range(len(Rs))]
     side = [c for c in calls if c[0] in SIDE_ENTRIES]
     assert [c[0] for c in side] == ["uamd_lora_xa2k"] and _addr(side[0][1][0]) == Xv.data_ptr() and side[0][1][1] == K + 64
     torch.testing.assert_close(xa.cpu(), want.float(), rtol=1e-4, atol=1e-4 * float(want.abs().mean()) + 1e-5)

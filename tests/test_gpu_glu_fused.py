@@ -48,11 +48,13 @@ def _fused_case(M, K, r, act, dtype, geglu, swiglu, U):
         assert out is None and U.glu_bwd_terms(act, DW.clone(), e.clone(), g.clone(), up, gate) is None
         return
     assert out is not None
-    h, (xa, offs, xk) = out
+    h, (term,) = out
+    xa, xk = term.P, term.xk
     h_ref = fwd(e.clone(), g.clone())
     assert torch.equal(h, h_ref)
-    xa_ref, offs_ref, xk_ref = U._xa_and_rank_block(h_ref, [down[2]], xk is not None)
-    assert offs == offs_ref
+    (ref,) = U._xa_and_rank_block(h_ref, [down[2]], xk is not None)
+    xa_ref, xk_ref = ref.P, ref.xk
+    assert xa.shape == xa_ref.shape and term.col == ref.col == 0
     truth = h_ref.float() @ down[2].to(dtype).float().t()
     assert rel_fro(xa, truth) <= 2 * rel_fro(xa_ref, truth) + 1e-6
     assert rel_fro(xa, xa_ref) < 1e-5
@@ -67,14 +69,12 @@ def _fused_case(M, K, r, act, dtype, geglu, swiglu, U):
     DW2, e2, g2 = bwd(DW.clone(), e.clone(), g.clone())
     assert torch.equal(h2, DW2) and torch.equal(df, e2) and torch.equal(de, g2)
     tu, tg = U.lora_dx_terms([e2, g2], [up, gate])
-    assert rel_fro(pu, tu) < 1e-5 and rel_fro(pg, tg) < 1e-5
-    ku, kg = getattr(pu, "_uamd_xk", None), getattr(pg, "_uamd_xk", None)
-    ru_, rg_ = getattr(tu, "_uamd_xk", None), getattr(tg, "_uamd_xk", None)
-    assert (ku is None) == (ru_ is None)
-    if ku is not None:
-        assert ku[0] is kg[0] and ku[1] == ru_[1] and kg[1] == rg_[1] and ku[0].shape == ru_[0].shape
-        assert torch.all(ku[0][:, 2 * r:] == 0)
-        assert rel_fro(ku[0].float(), ru_[0].float()) < 2e-3
+    assert rel_fro(pu.P, tu.P) < 1e-5 and rel_fro(pg.P, tg.P) < 1e-5
+    assert (pu.xk is None) == (tu.xk is None)
+    if pu.xk is not None:
+        assert pu.xk is pg.xk and pu.col == tu.col and pg.col == tg.col and pu.xk.shape == tu.xk.shape
+        assert torch.all(pu.xk[:, 2 * r:] == 0)
+        assert rel_fro(pu.xk.float(), tu.xk.float()) < 2e-3
 
 
 def test_lora_mlp_block_with_and_without_the_fusion():
@@ -130,9 +130,9 @@ def test_fused_activation_schedules_agree(M, K, r):
             out = U.glu_fwd_xa("swiglu", e, g, down)
             if out is None:
                 pytest.skip("shape not fusable")
-            h, (xa, _, xk) = out
+            h, (term,) = out
             h2, df, de, (pu, pg) = U.glu_bwd_terms("swiglu", DW.clone(), e.clone(), g.clone(), up, gate)
-            res[v] = (h, h2, df, de, xa, pu, pg)
+            res[v] = (h, h2, df, de, term.P, pu.P, pg.P)
     finally:
         L.uamd_set_tuning(10, 3)
         U.GLU_FUSED = keep
@@ -161,9 +161,9 @@ def test_column_split_is_run_to_run_deterministic_and_leaves_its_counters_zero()
     try:
         runs = []
         for _ in range(4):
-            h, (xa, _, xk) = U.glu_fwd_xa("swiglu", e, g, down)
+            h, (term,) = U.glu_fwd_xa("swiglu", e, g, down)
             _, _, _, (pu, pg) = U.glu_bwd_terms("swiglu", DW.clone(), e.clone(), g.clone(), up, gate)
-            runs.append((xa.clone(), pu.clone(), pg.clone()))
+            runs.append((term.P.clone(), pu.P.clone(), pg.P.clone()))
         torch.cuda.synchronize()
         for other in runs[1:]:
             assert all(torch.equal(a, b) for a, b in zip(runs[0], other))

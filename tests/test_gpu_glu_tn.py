@@ -86,19 +86,17 @@ def test_activation_row_products_and_gradients(M, K, r, halves, dtype):
     if halves:                                   # nothing outside the [M, K] views was written
         assert e.stride(0) == 2 * K + 64 and torch.equal(DW._whole, dwb0) and torch.all(e._whole[:, 2 * K:] == 3.0)
     # row products
-    assert rel_fro(pu, tu) < 1e-5 and rel_fro(pg, tg) < 1e-5
-    for p_new, p_ref, Z, B in ((pu, tu, df, up[3]), (pg, tg, de, gate[3])):
+    assert rel_fro(pu.P, tu.P) < 1e-5 and rel_fro(pg.P, tg.P) < 1e-5
+    for p_new, p_ref, Z, B in ((pu.P, tu.P, df, up[3]), (pg.P, tg.P, de, gate[3])):
         truth = Z.double() @ B.to(dtype).double()
         e_new, e_ref = rel_fro(p_new.double(), truth), rel_fro(p_ref.double(), truth)
         print(f"row product: new {e_new:.3e} existing {e_ref:.3e}")
         assert e_new <= 2 * e_ref + 1e-6
-    ku, kg = getattr(pu, "_uamd_xk", None), getattr(pg, "_uamd_xk", None)
-    ru_, rg_ = getattr(tu, "_uamd_xk", None), getattr(tg, "_uamd_xk", None)
-    assert (ku is None) == (ru_ is None)
-    if ku is not None:
-        assert ku[0] is kg[0] and ku[1] == ru_[1] and kg[1] == rg_[1] and ku[0].shape == ru_[0].shape
-        assert torch.all(ku[0][:, 2 * r:] == 0)
-        assert rel_fro(ku[0].float(), ru_[0].float()) < 2e-3
+    assert (pu.xk is None) == (tu.xk is None)
+    if pu.xk is not None:
+        assert pu.xk is pg.xk and pu.col == tu.col and pg.col == tg.col and pu.xk.shape == tu.xk.shape
+        assert torch.all(pu.xk[:, 2 * r:] == 0)
+        assert rel_fro(pu.xk.float(), tu.xk.float()) < 2e-3
     # the three gradients
     for name, got, want, P, Z, nr in (("dA_down", grads[0], ref[0], p_d, h, False), ("dB_up", grads[1], ref[1], xa_u, df, True),
                                       ("dB_gate", grads[2], ref[2], xa_g, de, True)):
@@ -135,8 +133,8 @@ def test_accumulate_is_a_plain_add_and_runs_are_bitwise_equal():
     runs = []
     for _ in range(4):
         df, de, (pu, pg), grads = U.glu_bwd_tn("swiglu", DW, e.clone(), g.clone(), up, gate, down, p_d, xa_u, xa_g)
-        xk = getattr(pu, "_uamd_xk", (pu,))[0]
-        runs.append([df.clone(), de.clone(), pu.clone(), pg.clone(), xk.clone()] + [x.clone() for x in grads])
+        xk = pu.xk if pu.xk is not None else pu.P
+        runs.append([df.clone(), de.clone(), pu.P.clone(), pg.P.clone(), xk.clone()] + [x.clone() for x in grads])
     for other in runs[1:]:
         assert all(torch.equal(a, b) for a, b in zip(runs[0], other))
     g_ = torch.Generator().manual_seed(1)

@@ -40,14 +40,15 @@ Routes and a case that reaches each (the table in tests/_lora_blocks.py has them
                          qkv-r64-256-merged, w-r16-fp16-256-decode | dense, prologue: mlp-r16-tn-dense, qkv-r16-merged-dense |
                          dense, rank block: mlp-r16-256-tn-dense, qkv-r64-256-dense | X A^T handed over by glu_fwd_xa:
                          mlp-r16-tn, with its rank block mlp-r16-256-tn-dense | bias in the epilogue: qkv-r16-bias-frozen
-  _xa_and_rank_block     <= 64 ranks: every r <= 16 case | 65 .. 192 in groups of 64: mlp-r64-256-dense, qkv-r64-256-dense,
+  _rank_plan, forward    (_xa_and_rank_block; tests/test_rank_plan_host.py pins the launch lists) rank block, <= 64 ranks: every
+                         r <= 16 case | 65 .. 192 in groups of 64: mlp-r64-256-dense, qkv-r64-256-dense,
                          qkv-r32-m129-256-dense | first-version kernel + padded cast: mlp-r128-256-dense, qkv-r128-256-dense,
                          mlp-r16-xa1-256-dense | no rank block, one launch of 65 .. 192 ranks: mlp-r64-terms, qkv-r64 | past
                          192 in chunks: mlp-r128, qkv-r128-merged
-  lora_dx_terms          shared P and shared rank block: qkv-r16-merged-scales-256, qkv-r64-256-merged | one adapter's rank
-                         block: w-r4-m129-256-dense, qkv-q-only-256-dense | padded cast per term (odd ranks, a missing adapter,
-                         r > 64): mlp-r4-256-dense, qkv-r16-8-4-m257-256-dense, qkv-r128-256-dense | no rank block: every
-                         128-tile case | no adapter: mlp-none, qkv-none-merged, w-none
+  _rank_plan, backward   (lora_dx_terms) shared P and shared rank block: qkv-r16-merged-scales-256, qkv-r64-256-merged | one
+                         adapter's rank block: w-r4-m129-256-dense, qkv-q-only-256-dense | padded cast per term (odd ranks, a
+                         missing adapter, r > 64): mlp-r4-256-dense, qkv-r16-8-4-m257-256-dense, qkv-r128-256-dense | no rank
+                         block: every 128-tile case | no adapter: mlp-none, qkv-none-merged, w-none
   _dx_gemm               NT, 128-tile prologue: every 128-tile case, odd ranks through the padded LB: mlp-r4, qkv-r4 | NN, rank
                          block: every 256-tile case | 256-tile wanted but no shared rank block, prologue: mlp-r16-xa1-256-dense,
                          qkv-r128-m129-256-merged | NN without an adapter: mlp-none-256-dense

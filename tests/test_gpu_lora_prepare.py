@@ -25,7 +25,7 @@ def test_prepare_matches_torch_cast(dtype):
     torch.cuda.synchronize()
     for P in params:
         g = U._PREPARED[(P.device, dtype)].params[id(P)]
-        assert torch.equal(g[1], P.detach().to(dtype)) and torch.equal(g[2], P.detach().to(dtype).t())
+        assert torch.equal(g.rm, P.detach().to(dtype)) and torch.equal(g.tr, P.detach().to(dtype).t())
     assert first.data_ptr() == U._cached_cast(params[0], "rowmajor", dtype, None).data_ptr()
     with torch.no_grad():                              # in-place edit inside an epoch is picked up via _version
         params[3].add_(1.0)

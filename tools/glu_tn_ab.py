@@ -42,12 +42,12 @@ for M in (8192, 4096, 2048):
 
     def old():
         h, df, de, (pu, pg) = U.glu_bwd_terms("swiglu", DW, e, g, up, gate)
-        U.lora_tn([(p_d, h, r, False, 2.0), (xa_d, dY, r, True, 2.0), (pu, X, r, False, 2.0), (xa_u, df, r, True, 2.0),
-                   (pg, X, r, False, 2.0), (xa_g, de, r, True, 2.0)])
+        U.lora_tn([(p_d, h, r, False, 2.0), (xa_d, dY, r, True, 2.0), (pu.P, X, r, False, 2.0), (xa_u, df, r, True, 2.0),
+                   (pg.P, X, r, False, 2.0), (xa_g, de, r, True, 2.0)])
 
     def new():
         df, de, (pu, pg), _ = U.glu_bwd_tn("swiglu", DW, e, g, up, gate, down, p_d, xa_u, xa_g)
-        U.lora_tn([(xa_d, dY, r, True, 2.0), (pu, X, r, False, 2.0), (pg, X, r, False, 2.0)])
+        U.lora_tn([(xa_d, dY, r, True, 2.0), (pu.P, X, r, False, 2.0), (pg.P, X, r, False, 2.0)])
 
     def once(fn, burst):
         eg.copy_(eg0)                                       # both variants work in place: the same inputs every time

@@ -79,30 +79,29 @@ def _nf4_fields(qs):
 def lora_a_rows(A_list, dtype):
     """[sum R_i, K] activation-dtype copy of the LoRA A factors that share an input, cached on the first Parameter
     (the reference caches `lora_A._fast_lora = lora_A.to(dtype)`, utils.py:1104-1106; weights are frozen at inference)."""
-    from .utils import _CAST_EPOCH
+    from .utils import _stamp
     key = A_list[0]
     ent = getattr(key, "_uamd_fast_lora_rows", None)
-    # validity = the rule kernels/utils._cached_cast uses: _version alone is not enough -- the fused optimizers
+    # validity = kernels/utils._stamp, the rule of every factor cache: _version alone is not enough -- the fused optimizers
     # (optim.FlatAdamW's raw HIP kernel, torch's fused AdamW) update parameters WITHOUT bumping it, so the global
     # optimizer-step / model-forward epoch and the storage address are part of the key (generate -> train -> generate
     # must not multiply the trained B by the pre-training A)
-    vers = (_CAST_EPOCH[0],) + tuple((a._version, a.data_ptr()) for a in A_list)
-    if ent is None or ent[0] != vers or ent[1].dtype != dtype or len(ent[2]) != len(A_list):
-        shapes = [a.shape[0] for a in A_list]
-        if (ent is not None and ent[1].dtype == dtype and ent[2] == shapes and ent[1].shape[1] == A_list[0].shape[1]
-                and ent[1].device == A_list[0].device):
+    vers = tuple(_stamp(a) for a in A_list)
+    stamps, rows, shapes = ent if ent is not None else (None, None, None)
+    if stamps != vers or rows.dtype != dtype:
+        was, shapes = shapes, [a.shape[0] for a in A_list]
+        if (rows is not None and rows.dtype == dtype and was == shapes and rows.shape[1] == A_list[0].shape[1]
+                and rows.device == A_list[0].device):
             # refresh IN PLACE: a captured hipGraph of the token step holds this buffer's address
             r0 = 0
             with torch.no_grad():
                 for a in A_list:
-                    ent[1][r0:r0 + a.shape[0]].copy_(a.detach())
+                    rows[r0:r0 + a.shape[0]].copy_(a.detach())
                     r0 += a.shape[0]
-            ent = (vers, ent[1], shapes)
         else:
             rows = torch.cat([a.detach().to(dtype) for a in A_list], dim=0).contiguous()
-            ent = (vers, rows, shapes)
-        key._uamd_fast_lora_rows = ent
-    return ent[1]
+        key._uamd_fast_lora_rows = (vers, rows, shapes)
+    return rows
 
 
 def gemv(x, groups, nf4, blocksize=64, pro=None):

@@ -22,7 +22,7 @@ import os
 
 import torch
 
-from .utils import _same_rows, alloc_rows, glu_bwd_terms, glu_bwd_tn, glu_fwd_xa, glu_tn_takes
+from .utils import _features, _same_rows, alloc_rows, glu_bwd_terms, glu_bwd_tn, glu_fwd_xa, glu_tn_takes
 from .utils import (
     GRAD_SINKS,
     grad_sink,
@@ -66,17 +66,17 @@ def _lora_grads(X2d, dY2d, A, B, s, dtype):
 
 
 def _lora_grads_fused(items):
-    """items: [(X2d, dY2d, A, B, s, XA, P)] with XA = X @ A^T (fp32, saved by the forward) and P = dY @ B (fp32,
-    shared with the dX GEMM). Returns [(dA, dB)] in fp32, all products of the block in ONE launch per 8:
+    """items: [(X2d, dY2d, A, B, s, XA, term)] with XA = X @ A^T (fp32, saved by the forward) and the RankTerm of
+    P = dY @ B (fp32, shared with the dX GEMM). Returns [(dA, dB)] in fp32, all products of the block in ONE launch per 8:
         dA = s * P^T @ X   [r, in]          dB = s * dY^T @ XA   [out, r]          (fast_lora.py:172-189)"""
     probs, slots, targets, sinks = [], [], [], []
-    for (X2d, dY2d, A, B, s, XA, P) in items:
+    for (X2d, dY2d, A, B, s, XA, term) in items:
         if A is None:
             slots.append(None)
             continue
         r = A.shape[0]
         slots.append(len(probs))
-        probs.append((P, X2d, r, False, s))
+        probs.append((term.P, X2d, r, False, s))
         probs.append((XA, dY2d, r, True, s))
         for prm in (A, B):
             sink = grad_sink(prm)
@@ -98,12 +98,12 @@ def _mlp_grads_tn(act, DW, e, g, dY, X2, xas, p_d, gate, up, down):
     narrow = [down[3], up[2], gate[2]]               # dB_down, dA_up, dA_gate: one lora_tn launch
     sinks = [(grad_sink(prm), prm) for prm in wide + narrow]
     targets = [sk.grad_view(prm) if sk is not None else None for sk, prm in sinks]
-    res = glu_bwd_tn(act, DW, e, g, up, gate, down, p_d, xa_u, xa_g, targets[:3])
+    res = glu_bwd_tn(act, DW, e, g, up, gate, down, p_d.P, xa_u, xa_g, targets[:3])
     if res is None:
         return None
     df, de, (p_u, p_g), outs = res
-    outs = outs + lora_tn([(xa_d, dY, down[2].shape[0], True, down[4]), (p_u, X2, up[2].shape[0], False, up[4]),
-                           (p_g, X2, gate[2].shape[0], False, gate[4])],
+    outs = outs + lora_tn([(xa_d, dY, down[2].shape[0], True, down[4]), (p_u.P, X2, up[2].shape[0], False, up[4]),
+                           (p_g.P, X2, gate[2].shape[0], False, gate[4])],
                           targets[3:] if any(t is not None for t in targets[3:]) else None)
     for sk, prm in sinks:
         if sk is not None:
@@ -127,7 +127,7 @@ def _gate_up(X, gate, up, return_xa=False):
     reads an intermediate as its A operand (down_proj forward: h; that dX: df | de) sees rows that are not a whole number of
     4 KiB pages."""
     outs = None
-    widths = [(q.shape[0] if q is not None else W.shape[0]) for (W, q, *_rest) in (gate, up)]
+    widths = [_features(p[0], p[1])[0] for p in (gate, up)]
     if (X.is_cuda and X.dtype in (torch.bfloat16, torch.float16) and widths[0] == widths[1]
             and widths[0] % 64 == 0 and all(len(p) <= 5 or p[5] is None for p in (gate, up))):
         M = X.numel() // X.shape[-1]

@@ -13,6 +13,7 @@ that share their input (q/k/v, gate/up) are ONE uamd_lora_xa launch and ONE grou
 launch, with NF4 decode and the LoRA term fused into the GEMM (csrc/gemm.hip).
 """
 import ctypes
+import functools
 import os
 
 import torch
@@ -37,10 +38,12 @@ GEMM256_MODE = "auto"
 # (160 since round 4: Qwen2-VL's ViT linears with N = 1280 at 4096 patches are 160 half-height tiles -- on the 128 x 128 kernel
 # they ran at 0.18 PFLOP/s, the config-4 step is 2.7 % faster with them on the 256 family: profiles/r04p_config4_min_tiles_ab.txt)
 GEMM256_MIN_TILES = 160
-# X @ A^T / dY @ B: streaming LDS-DMA kernel (csrc/lora_side.hip) for total rank <= 64, else the first version
+# X @ A^T / dY @ B: streaming LDS-DMA kernel (csrc/lora_side.hip) for total rank <= LORA_XA2_MAX_RANKS, else the first version
 LORA_XA_V2 = True
-# rank columns of one uamd_lora_xa launch (csrc/gemm.hip: twelve 16-rank tiles); wider stacks go in chunks (lora_xa)
+# rank columns of one uamd_lora_xa launch (csrc/gemm.hip: twelve 16-rank tiles); wider stacks go in chunks (_rank_plan)
 LORA_XA_MAX_RANKS = 192
+# rank columns of one uamd_lora_xa2 / uamd_lora_xa2k launch
+LORA_XA2_MAX_RANKS = 64
 
 
 def calculate_settings(n):
@@ -291,7 +294,8 @@ def _out2d(C, M, N, dtype, name):
 # (b) no optimizer has stepped since (fused optimizers update in place WITHOUT bumping _version, so a global
 # optimizer post-step hook and every top-level model forward advance an epoch that invalidates everything).
 import weakref
-_CAST_CACHE = {}     # id(param) -> (weakref, version, data_ptr, epoch, {(tag, dtype): tensor})
+from collections import namedtuple
+_CAST_CACHE = {}     # id(param) -> _CastCopies
 _CAST_EPOCH = [0]
 
 
@@ -306,16 +310,53 @@ except Exception:  # pragma: no cover
     pass
 
 
+def _stamp(P):
+    """What a copy of the factor P was made from -- the object, its _version, its storage and the epoch. The copy is current
+    while this is unchanged: the one validity rule of every cache of factor copies (here and kernels/decode.py lora_a_rows)."""
+    return (id(P), P._version, P.data_ptr(), _CAST_EPOCH[0])
+
+
+def _stack_tag(kind, others):
+    """Tag of a copy stacked from several factors and cached on the first of them: the stamps of the others."""
+    return (kind,) + tuple(_stamp(A) for A in others)
+
+
+# The copies of one factor in _CAST_CACHE, which is keyed on id(P): `ref` (a weakref) guards against a recycled id, `stamp` is
+# the `_stamp` they were made at, `copies` = {(tag, dtype): tensor}.
+class _CastCopies:
+    __slots__ = ("ref", "stamp", "copies")
+
+    def __init__(self, P, pid):
+        self.ref, self.stamp, self.copies = weakref.ref(P, lambda _: _CAST_CACHE.pop(pid, None)), _stamp(P), {}
+
+
+# The copies of one factor in _PreparedFactors.params (keyed on id(P) too): row-major `rm`, transposed `tr` and, with
+# `pad` = (buffer, offset, scale, transposed), a scaled one inside a rank-block BK buffer. `stamp`: the `_stamp` of the last
+# uamd_lora_prepare launch that wrote them (None: to be written).
+class _Prepared:
+    __slots__ = ("ref", "stamp", "rm", "tr", "pad")
+
+    def __init__(self, P, ref, dtype):
+        self.ref, self.stamp, self.pad = ref, None, None
+        self.rm = torch.empty(P.shape, dtype=dtype, device=P.device)
+        self.tr = torch.empty((P.shape[1], P.shape[0]), dtype=dtype, device=P.device)
+
+
+# The descriptor table of the last multi-factor uamd_lora_prepare launch: the descriptor bytes, the two device tensors the
+# kernel reads, its tile count, and the identity key of the entries it was built from.
+_PrepTable = namedtuple("_PrepTable", "sig descs prefix tiles key")
+
+
 class _PreparedFactors:
     """Per (device, dtype): activation-dtype row-major + transposed copies of every LoRA factor seen so far,
     refreshed by ONE `uamd_lora_prepare` launch per optimizer step (epoch)."""
 
     def __init__(self, device, dtype):
         self.device, self.dtype = device, dtype
-        self.params = {}        # id -> [weakref, rm, tr, version, epoch, padspec]
+        self.params = {}        # id -> _Prepared
         self.pad_bufs = {}      # key -> zero-initialised [rows, width] buffer (rank-block BK operands of the GEMM)
         self.epoch = -1
-        self.table = None       # (descriptor bytes, descs tensor, prefix tensor, total tiles, identity key)
+        self.table = None       # _PrepTable
 
     @staticmethod
     def _tiles(P):
@@ -325,39 +366,38 @@ class _PreparedFactors:
              ("pad_ld", "<i8"), ("pad_scale", "<f4"), ("pad_t", "<i4")]          # uamd_lora_prep_desc
 
     def _launch(self, ents):
-        import numpy as np
+        import numpy as np                  # ents: [(P, its _Prepared)]
         # the table only changes when a factor / copy / pad buffer moves: a cheap identity key first, the numpy
         # descriptor build (1.2 ms of host time for 448 factors -- visible at 2048 tokens per step, where the host is
         # barely ahead of the GPU) only on a miss
-        key = tuple((P.data_ptr(), P.shape[0], P.shape[1], rm.data_ptr(), tr.data_ptr(),
-                     None if pad is None else (pad[0].data_ptr(), pad[0].stride(0)) + tuple(pad[1:]))
-                    for (P, rm, tr, pad) in ents) if len(ents) > 1 else None
+        key = tuple((P.data_ptr(), P.shape[0], P.shape[1], e.rm.data_ptr(), e.tr.data_ptr(),
+                     None if e.pad is None else (e.pad[0].data_ptr(), e.pad[0].stride(0)) + tuple(e.pad[1:]))
+                    for (P, e) in ents) if len(ents) > 1 else None
         tab = self.table
-        if key is None or tab is None or tab[4] != key:
+        if key is None or tab is None or tab.key != key:
             descs = np.zeros(len(ents), dtype=np.dtype(self._DESC))
             assert descs.dtype.itemsize == 56
             prefix, tot = np.zeros(len(ents), dtype=np.int32), 0
-            for i, (P, rm, tr, pad) in enumerate(ents):
-                if pad is None:
-                    descs[i] = (P.data_ptr(), rm.data_ptr(), tr.data_ptr(), P.shape[0], P.shape[1], 0, 0, 0.0, 0)
-                else:
-                    buf, col, scale, transposed = pad
-                    descs[i] = (P.data_ptr(), rm.data_ptr(), tr.data_ptr(), P.shape[0], P.shape[1],
-                                buf.data_ptr() + col * buf.element_size(), buf.stride(0), scale, int(transposed))
+            for i, (P, e) in enumerate(ents):
+                pad = (0, 0, 0.0, 0)
+                if e.pad is not None:
+                    buf, col, scale, transposed = e.pad
+                    pad = (buf.data_ptr() + col * buf.element_size(), buf.stride(0), scale, int(transposed))
+                descs[i] = (P.data_ptr(), e.rm.data_ptr(), e.tr.data_ptr(), P.shape[0], P.shape[1]) + pad
                 prefix[i] = tot
                 tot += self._tiles(P)
             sig = descs.tobytes()
-            if tab is None or tab[0] != sig:
+            if tab is None or tab.sig != sig:
                 d = torch.from_numpy(descs.view(np.uint8).copy()).to(self.device)
                 pf = torch.from_numpy(prefix).to(self.device)
-                tab = (sig, d, pf, tot, key)
+                tab = _PrepTable(sig, d, pf, tot, key)
             else:                                   # same descriptors under a new identity key
-                tab = tab[:4] + (key,)
+                tab = tab._replace(key=key)
             if len(ents) > 1:                       # (a single-entry launch never matches the stored table's bytes)
                 self.table = tab
         any_p = ents[0][0]
         # the table tensors must outlive the launch: stream-ordered free is fine for torch's caching allocator
-        _lib.call("uamd_lora_prepare", any_p, _lib.ptr(tab[1]), _lib.ptr(tab[2]), len(ents), tab[3],
+        _lib.call("uamd_lora_prepare", any_p, _lib.ptr(tab.descs), _lib.ptr(tab.prefix), len(ents), tab.tiles,
                   _lib.dtype_code(self.dtype), _lib.stream_of(any_p))
 
     def _forget(self, pid):
@@ -369,35 +409,30 @@ class _PreparedFactors:
         """Registers P (and, optionally, its padded/scaled third copy) and makes every copy current."""
         pid = id(P)
         ent = self.params.get(pid)
-        epoch = _CAST_EPOCH[0]
         with torch.no_grad():
-            if ent is None or ent[0]() is not P or ent[1].shape != P.shape:
-                rm = torch.empty(P.shape, dtype=self.dtype, device=self.device)
-                tr = torch.empty((P.shape[1], P.shape[0]), dtype=self.dtype, device=self.device)
-                ent = [weakref.ref(P, lambda _, pid=pid: self._forget(pid)), rm, tr, -1, -1, None]
-                self.params[pid] = ent
+            if ent is None or ent.ref() is not P or ent.rm.shape != P.shape:
+                ent = self.params[pid] = _Prepared(P, weakref.ref(P, lambda _, pid=pid: self._forget(pid)), self.dtype)
             if padspec is not None:
-                old = ent[5]
+                old = ent.pad
                 if old is None or old[0] is not padspec[0] or old[1:] != padspec[1:]:
-                    ent[5] = padspec
-                    ent[4] = -1                                # this entry must be (re)written
-            if self.epoch != epoch:
+                    ent.pad, ent.stamp = padspec, None         # this entry must be (re)written
+            if self.epoch != _CAST_EPOCH[0]:
                 live = []
                 for e in list(self.params.values()):
-                    Q = e[0]()
+                    Q = e.ref()
                     if Q is not None:
-                        live.append((Q, e[1], e[2], e[5]))
-                        e[3], e[4] = Q._version, epoch
+                        live.append((Q, e))
+                        e.stamp = _stamp(Q)
                 self._launch(live)
-                self.epoch = epoch
-            elif ent[4] != epoch or ent[3] != P._version:       # registered (or modified in place) mid-epoch
-                self._launch([(P, ent[1], ent[2], ent[5])])
-                ent[3], ent[4] = P._version, epoch
+                self.epoch = _CAST_EPOCH[0]
+            elif ent.stamp != _stamp(P):                        # registered (or modified in place) mid-epoch
+                self._launch([(P, ent)])
+                ent.stamp = _stamp(P)
         return ent
 
     def get(self, P, tag):
         ent = self._entry(P)
-        return ent[1] if tag == "rowmajor" else ent[2]
+        return ent.rm if tag == "rowmajor" else ent.tr
 
     def get_pad(self, members, rows, width, transposed, by_rows=False):
         """members: [(P, off, scale)] written into ONE zero-initialised [rows, width] buffer: scale * P
@@ -436,17 +471,14 @@ def _cached_cast(P, tag, dtype, build):
         return _prepared_for(P.device, dtype).get(P, tag)
     pid = id(P)
     ent = _CAST_CACHE.get(pid)
-    if (ent is None or ent[0]() is not P or ent[1] != P._version or ent[2] != P.data_ptr()
-            or ent[3] != _CAST_EPOCH[0]):
-        ent = (weakref.ref(P, lambda _, pid=pid: _CAST_CACHE.pop(pid, None)), P._version, P.data_ptr(),
-               _CAST_EPOCH[0], {})
-        _CAST_CACHE[pid] = ent
+    if ent is None or ent.ref() is not P or ent.stamp != _stamp(P):
+        ent = _CAST_CACHE[pid] = _CastCopies(P, pid)
     key = (tag, dtype)
-    out = ent[4].get(key)
+    out = ent.copies.get(key)
     if out is None:
         with torch.no_grad():
             out = build()
-        ent[4][key] = out
+        ent.copies[key] = out
     return out
 
 
@@ -470,65 +502,6 @@ def rank_block_bk(members, rows, width, transposed, dtype, by_rows=False):
     return _prepared_for(members[0][0].device, dtype).get_pad(members, rows, width, transposed, by_rows)
 
 
-def lora_xa(X2d, A_list, out=None, out_k=None, k_cols=0):
-    """XA_g = X @ A_g^T for every projection sharing X, ONE launch (one per LORA_XA_MAX_RANKS rank columns past
-    that width). fp32, each block of columns padded to a multiple of 8. Returns (buffer, [(col_offset, R_padded)]).
-    `out`: optional fp32 [M, sum Rp] destination with unit column stride (e.g. a column slice of a wider buffer). `out_k` (activation dtype, unit
-    column stride) additionally receives the sums rounded to the activation dtype, zero-filled up to `k_cols`
-    columns: the XK operand of the GEMM's rank-block K tiles."""
-    dtype = X2d.dtype
-    Rs = [A.shape[0] for A in A_list]
-    Rp = [(r + 7) // 8 * 8 for r in Rs]
-    K = X2d.shape[1]
-    if len(A_list) == 1 and Rs[0] == Rp[0]:
-        Acat = cast_lora(A_list[0], dtype)                                              # A.to(dtype), utils.py:1166
-    else:
-        def _cat():
-            if Rs == Rp:
-                return torch.cat([cast_lora(A, dtype) for A in A_list], dim=0)
-            buf = torch.zeros((sum(Rp), K), dtype=dtype, device=X2d.device)
-            o = 0
-            for A, r, rp in zip(A_list, Rs, Rp):
-                buf[o:o + r] = A
-                o += rp
-            return buf
-        if all(isinstance(A, torch.nn.Parameter) for A in A_list):
-            # keyed on the first factor, tagged with the identity + version of the others
-            tag = ("cat",) + tuple((id(A), A._version, A.data_ptr()) for A in A_list[1:])
-            Acat = _cached_cast(A_list[0], tag, dtype, _cat)
-        else:
-            Acat = _cat()
-    Rt = Acat.shape[0]
-    if out is None:
-        out = torch.empty((X2d.shape[0], Rt), dtype=torch.float32, device=X2d.device)
-    else:
-        assert out.dtype == torch.float32 and tuple(out.shape) == (X2d.shape[0], Rt) and out.stride(1) == 1 \
-            and out.stride(0) % 4 == 0
-    if Rt > LORA_XA_MAX_RANKS:
-        # r = 128 on gate|up (256 rank columns) or on q|k|v (384): one launch takes LORA_XA_MAX_RANKS rows of the stacked
-        # factors, so they go in row chunks (whole 8-rank blocks), each launch writing its own columns of `out`
-        assert out_k is None, "the rank-block output takes <= 64 ranks per launch (_xa_and_rank_block groups them)"
-        if not _aligned_rows(Acat):
-            Acat = _aligned_copy(Acat)
-        for c0 in range(0, Rt, LORA_XA_MAX_RANKS):
-            rc = min(LORA_XA_MAX_RANKS, Rt - c0)
-            lora_xa(X2d, [Acat[c0:c0 + rc]], out=out[:, c0:c0 + rc])
-    elif out_k is not None:
-        assert Rt <= 64 and out_k.dtype == dtype and out_k.stride(1) == 1 and k_cols >= Rt
-        _lib.call("uamd_lora_xa2k", X2d, _lib.ptr(X2d), X2d.stride(0), _lib.ptr(Acat), Acat.stride(0), _lib.ptr(out),
-                  out.stride(0), _lib.ptr(out_k), out_k.stride(0), k_cols, X2d.shape[0], K, Rt, Rt,
-                  _lib.dtype_code(dtype), _lib.stream_of(X2d))
-    else:
-        _lib.call("uamd_lora_xa2" if (LORA_XA_V2 and Rt <= 64 and K >= 8) else "uamd_lora_xa", X2d,
-                  _lib.ptr(X2d), X2d.stride(0), _lib.ptr(Acat), Acat.stride(0), _lib.ptr(out), out.stride(0),
-                  X2d.shape[0], K, Rt, Rt, _lib.dtype_code(dtype), _lib.stream_of(X2d))
-    offs, o = [], 0
-    for rp in Rp:
-        offs.append((o, rp))
-        o += rp
-    return out, offs
-
-
 def cast_lora(P, dtype):
     """P.to(dtype) (row-major, contiguous), converted once per parameter version."""
     return _cached_cast(P, "rowmajor", dtype, lambda: P.to(dtype).contiguous())
@@ -549,54 +522,209 @@ def _pad_rank(B, Rp, dtype):
     return out
 
 
-def _rank_width(r):
+def _features(W, q):
+    """(N, K) = (out, in) features of a projection: off the quant state when the weight is packed NF4."""
+    shape = q.shape if q is not None else W.shape
+    return shape[0], shape[1]
+
+
+# The rank term of one projection, forward (P = X A^T) or backward (P = dY B). `P`: fp32 [M, Rp] view, unit column stride;
+# `xk`: the 16-bit zero-padded rank block P was also written to (the XK operand the 256-tile GEMMs contract as extra K tiles)
+# or None; `col`: P's first column in it.
+RankTerm = namedtuple("RankTerm", "P xk col", defaults=(None, 0))
+
+
+# ------------------------------------------------------------------------------------------------
+# rank columns: which launches form the P of the factors of one block, and where they land
+def _pad8(r):                           # every factor's P takes whole 8-rank blocks of columns
+    return (r + 7) // 8 * 8
+
+
+def _rank_width(r):                     # columns of a rank block: whole K tiles of the GEMM
     return (r + 63) // 64 * 64
 
 
-def _xa_and_rank_block(X2d, A_list, want_k, out=None):
-    """(xa fp32 [M, sum Rp], offsets, xk): X @ A_g^T for the projections sharing X and, when `want_k`, the same sums
-    in the activation dtype zero-padded to a multiple of 64 columns (XK, the GEMM's rank-block operand)."""
-    Rt = sum((A.shape[0] + 7) // 8 * 8 for A in A_list)
-    if not want_k:
-        xa, offs = lora_xa(X2d, A_list, out=out)
-        return xa, offs, None
-    M = X2d.shape[0]
-    width = _rank_width(Rt)
-    if Rt <= 64 and LORA_XA_V2 and X2d.shape[1] >= 8:
-        xk = torch.empty((M, width), dtype=X2d.dtype, device=X2d.device)
-        xa, offs = lora_xa(X2d, A_list, out=out, out_k=xk, k_cols=width)
-    elif (LORA_XA_V2 and X2d.shape[1] >= 8 and Rt <= 192
-          and all(A.shape[0] % 8 == 0 and A.shape[0] <= 64 for A in A_list)):
-        # total rank 65 .. 192 (r = 32 on q|k|v, r = 64 on gate|up): the streaming kernel takes <= 64 rank columns per
-        # launch, so the factors go in groups, each launch writing its own columns of the shared XA / rank-block buffers
-        # (the last one zero-fills the padding)
-        xk = torch.empty((M, width), dtype=X2d.dtype, device=X2d.device)
-        xa = out if out is not None else torch.empty((M, Rt), dtype=torch.float32, device=X2d.device)
-        groups, cur, cur_r = [], [], 0
-        for A in A_list:
-            if cur and cur_r + A.shape[0] > 64:
-                groups.append((cur, cur_r))
-                cur, cur_r = [], 0
-            cur.append(A)
-            cur_r += A.shape[0]
-        groups.append((cur, cur_r))
-        offs, col = [], 0
-        for gi, (As, r) in enumerate(groups):
-            last = gi == len(groups) - 1
-            _, o = lora_xa(X2d, As, out=xa[:, col:col + r], out_k=xk[:, col:], k_cols=(width - col) if last else r)
-            offs += [(col + a, b) for a, b in o]
-            col += r
-    else:                                   # odd ranks / very wide: first-version kernel, then a padded cast
-        xa, offs = lora_xa(X2d, A_list, out=out)
-        xk = torch.zeros((M, width), dtype=X2d.dtype, device=X2d.device)
-        xk[:, :Rt] = xa
-    return xa, offs, xk
+def _streams(r):
+    """A rank the streaming kernels (uamd_lora_xa2 / xa2k, the fused gated activations) take: unpadded, one launch."""
+    return 0 < r <= LORA_XA2_MAX_RANKS and r == _pad8(r)
+
+
+def _share_block(ranks):
+    """Ranks whose P the streaming kernel can write side by side into ONE rank block: one launch's worth of padded columns, or
+    up to three launches' worth of whole unpadded factors."""
+    Rt = sum(_pad8(r) for r in ranks)
+    return Rt <= LORA_XA2_MAX_RANKS or (Rt <= LORA_XA_MAX_RANKS and all(_streams(r) for r in ranks))
+
+
+# One launch of a plan. entry: uamd_lora_xa | uamd_lora_xa2 | uamd_lora_xa2k; members: the factors whose stacked rows it reads
+# (indices into the plan's ranks); col: the first rank column it writes, of P and of the rank block; cols: rank columns;
+# k_cols: (uamd_lora_xa2k, else None) rank-block columns written from `col` on -- `cols`, then zeros.
+XaLaunch = namedtuple("XaLaunch", "entry members col cols k_cols")
+# ranks: as given (None: a projection without an adapter); widths: padded columns of each P (None likewise); starts: first rank
+# column of each; total: rank columns of all; shared: the Ps are column blocks of ONE fp32 buffer; launches: XaLaunch in launch
+# order; block: columns of the ONE rank block the launches write (0: none); casts: [(members, width)] -- a padded cast of their
+# P columns into a rank block of their own follows.
+RankPlan = namedtuple("RankPlan", "ranks widths starts total shared launches block casts")
+
+
+@functools.lru_cache(maxsize=None)
+def _rank_plan(ranks, K, want_k, one_input=True, v2=True):
+    """The X @ A^T (forward) or dY @ B (backward) launches of one block. Pure -- tuples in, no tensors, no launches, no module
+    switches (`v2` is LORA_XA_V2) -- so every distinct block of a model is planned once.
+    `one_input` (forward): the factors share an input of K columns, their Ps sit side by side and one launch may take
+    several of them. Else (backward) factor i has an input of K[i] columns and a launch of its own; rank None = no adapter.
+    `want_k`: the GEMM will take a rank block. The streaming kernel writes it when the ranks can share one (_share_block) -- in
+    the backward only when the Ps share a buffer too, or there is just one; else a padded cast per unit follows."""
+    n = len(ranks)
+    Ks = (K,) * n if one_input else K
+    widths = [None if r is None else _pad8(r) for r in ranks]
+    idx = [i for i in range(n) if ranks[i] is not None]
+    starts = [sum(w or 0 for w in widths[:i]) for i in range(n)]
+    Rt = sum(w or 0 for w in widths)
+    span = lambda g: sum(widths[i] for i in g)
+    shared = one_input or (n > 1 and len(idx) == n and all(r == _pad8(r) for r in ranks))
+    units = [idx] if one_input else [[i] for i in idx]          # the factors a launch may take together
+    block = (want_k and bool(idx) and _share_block([ranks[i] for i in idx])
+             and ((v2 and K >= 8) if one_input else (shared or len(idx) == 1)))
+    launches, width = [], _rank_width(Rt) if block else 0
+    if block:
+        # <= LORA_XA2_MAX_RANKS rank columns per launch: whole factors in greedy groups, each launch writing its own columns
+        # of the shared buffers, the last one zero-filling the block's padding
+        groups = []
+        for i in idx:
+            if one_input and groups and span(groups[-1]) + widths[i] <= LORA_XA2_MAX_RANKS:
+                groups[-1].append(i)
+            else:
+                groups.append([i])
+        for g in groups:
+            col, cols = starts[g[0]], span(g)
+            launches.append(XaLaunch("uamd_lora_xa2k", tuple(g), col, cols, width - col if g is groups[-1] else cols))
+    else:
+        # one launch per unit; past LORA_XA_MAX_RANKS (r = 128 on gate|up or q|k|v) in chunks of its stacked rows
+        for u in units:
+            for o in range(0, span(u), LORA_XA_MAX_RANKS):
+                cols = min(LORA_XA_MAX_RANKS, span(u) - o)
+                name = "uamd_lora_xa2" if (v2 and cols <= LORA_XA2_MAX_RANKS and Ks[u[0]] >= 8) else "uamd_lora_xa"
+                launches.append(XaLaunch(name, tuple(u), starts[u[0]] + o, cols, None))
+    casts = [(tuple(u), _rank_width(span(u))) for u in units] if (want_k and not block) else []
+    return RankPlan(ranks, tuple(widths), tuple(starts), Rt, shared, tuple(launches), width, tuple(casts))
+
+
+def _padded_cast(P, width, dtype):
+    """P (fp32 [M, R]) as a rank block of its own, with torch ops: where the streaming kernel writes none (_rank_plan)."""
+    xk = torch.zeros((P.shape[0], width), dtype=dtype, device=P.device)
+    xk[:, :P.shape[1]] = P
+    return xk
+
+
+def _stacked_rows(plan, members, rows, params, X2d):
+    """[sum widths, K] in the activation dtype: the rows of the factors `members`, each zero-padded to its width."""
+    exact = all(plan.ranks[i] == plan.widths[i] for i in members)
+    if len(members) == 1 and exact:
+        return rows(members[0], False)
+
+    def build():
+        if exact:
+            return torch.cat([rows(i, False) for i in members], dim=0)
+        buf = torch.zeros((sum(plan.widths[i] for i in members), X2d.shape[1]), dtype=X2d.dtype, device=X2d.device)
+        for i in members:
+            o = plan.starts[i] - plan.starts[members[0]]
+            buf[o:o + plan.ranks[i]] = rows(i, True)
+        return buf
+    if params is not None and all(isinstance(params[i], torch.nn.Parameter) for i in members):
+        return _cached_cast(params[members[0]], _stack_tag("cat", [params[i] for i in members[1:]]), X2d.dtype, build)
+    return build()
+
+
+def _rank_terms(plan, Xs, rows, params=None, out=None, xk=None):
+    """Executes `plan`: [RankTerm | None] per factor. Xs[i]: the 2-D input of factor i; rows(i, padded): its [r, K] rows in the
+    activation dtype (A.to(dtype), utils.py:1166) or, when `padded`, in any, to be copied into a zero-padded stack; `params`:
+    the factors when a stack of Parameters may be cached on the first; `out` / `xk`: the caller's shared P buffer / rank block."""
+    if not plan.total:
+        return [None] * len(plan.widths)
+    X0 = Xs[plan.launches[0].members[0]]
+    M, dtype, dev = X0.shape[0], X0.dtype, X0.device
+    if plan.block and xk is None:
+        xk = torch.empty((M, plan.block), dtype=dtype, device=dev)
+    if not plan.shared:
+        Ps = [None if w is None else torch.empty((M, w), dtype=torch.float32, device=dev) for w in plan.widths]
+    else:
+        if out is None:
+            out = torch.empty((M, plan.total), dtype=torch.float32, device=dev)
+        else:
+            assert out.dtype == torch.float32 and tuple(out.shape) == (M, plan.total) and out.stride(1) == 1 and out.stride(0) % 4 == 0
+        Ps = [None if w is None else out[:, c:c + w] for c, w in zip(plan.starts, plan.widths)]
+    of = None
+    for entry, members, col, cols, k_cols in plan.launches:
+        X2d, P = Xs[members[0]], Ps[members[0]]
+        if members != of:
+            S, of = _stacked_rows(plan, members, rows, params, X2d), members
+            if S.shape[0] > LORA_XA_MAX_RANKS and not _aligned_rows(S):         # read in row chunks: each from an aligned start
+                S = _aligned_copy(S)
+        o = col - plan.starts[members[0]]
+        args = [_lib.ptr(X2d), X2d.stride(0), ctypes.c_void_p(S.data_ptr() + o * S.stride(0) * S.element_size()), S.stride(0),
+                ctypes.c_void_p(P.data_ptr() + 4 * o), P.stride(0)]
+        if k_cols is not None:
+            args += [ctypes.c_void_p(xk.data_ptr() + col * xk.element_size()), xk.stride(0), k_cols]
+        _lib.call(entry, X2d, *args, M, X2d.shape[1], cols, cols, _lib.dtype_code(dtype), _lib.stream_of(X2d))
+    if not plan.casts:
+        return [None if P is None else RankTerm(P, xk, c) for P, c in zip(Ps, plan.starts)]
+    terms = list(Ps)
+    for members, width in plan.casts:
+        c0, last = plan.starts[members[0]], members[-1]
+        own = _padded_cast(out[:, c0:plan.starts[last] + plan.widths[last]] if plan.shared else Ps[last], width, dtype)
+        for i in members:
+            terms[i] = RankTerm(Ps[i], own, plan.starts[i] - c0)
+    return terms
+
+
+def _factor_rows(A_list, dtype):
+    return lambda i, padded: A_list[i] if padded else cast_lora(A_list[i], dtype)
+
+
+def lora_xa(X2d, A_list, out=None, out_k=None, k_cols=0):
+    """XA_g = X @ A_g^T for every projection sharing X, ONE launch (one per LORA_XA_MAX_RANKS rank columns past
+    that width). fp32, each block of columns padded to a multiple of 8. Returns (buffer, [(col_offset, R_padded)]).
+    `out`: optional fp32 [M, sum Rp] destination with unit column stride (e.g. a column slice of a wider buffer). `out_k`
+    (activation dtype, unit column stride) additionally receives the sums rounded to the activation dtype, zero-filled up to
+    `k_cols` columns: the XK operand of the GEMM's rank-block K tiles."""
+    plan = _rank_plan(tuple(A.shape[0] for A in A_list), X2d.shape[1], False, v2=LORA_XA_V2)
+    if out_k is not None:
+        assert plan.total <= LORA_XA2_MAX_RANKS and out_k.dtype == X2d.dtype and out_k.stride(1) == 1 and k_cols >= plan.total
+        plan = plan._replace(launches=(XaLaunch("uamd_lora_xa2k", tuple(range(len(A_list))), 0, plan.total, k_cols),))
+    if out is None:
+        out = torch.empty((X2d.shape[0], plan.total), dtype=torch.float32, device=X2d.device)
+    _rank_terms(plan, [X2d] * len(A_list), _factor_rows(A_list, X2d.dtype), A_list, out=out, xk=out_k)
+    return out, list(zip(plan.starts, plan.widths))
+
+
+def _xa_and_rank_block(X2d, A_list, want_k):
+    """[RankTerm] of X @ A_g^T for the projections sharing X: column blocks of one fp32 [M, sum Rp] buffer and, when `want_k`,
+    of one rank block (the same sums in the activation dtype, zero-padded to a multiple of 64 columns)."""
+    plan = _rank_plan(tuple(A.shape[0] for A in A_list), X2d.shape[1], bool(want_k), v2=LORA_XA_V2)
+    return _rank_terms(plan, [X2d] * len(A_list), _factor_rows(A_list, X2d.dtype), A_list)
 
 
 def _fused_nf4(q, M, K):
-    """Does a forward launch of M rows decode this weight inside the GEMM (uamd_gemm_nt_nf4)? lora_linear_forward and the
-    kernel that prepares its rank block (glu_fwd_xa) must agree."""
+    """Does a forward launch of M rows decode this weight inside the GEMM (uamd_gemm_nt_nf4)? Part of
+    _forward_wants_rank_block, where lora_linear_forward and the kernel that prepares its rank block (glu_fwd_xa) agree."""
     return q is not None and FUSED_NF4 and M < FUSED_NF4_MAX_M and q.blocksize == 64 and K % 64 == 0
+
+
+def _forward_wants_rank_block(M, K, projs):
+    """Does the forward launch of `projs` on an [M, K] input take its LoRA terms as a rank block? Its dense groups (NF4 not
+    decoded in the GEMM) go to the 256x256 kernel when the launch is large enough: there the LoRA term rides along as extra K
+    tiles. lora_linear_forward launches by this answer; glu_fwd_xa, which hands it X A^T, writes the rank block by the same."""
+    dense = [_features(p[0], p[1])[0] for p in projs if not _fused_nf4(p[1], M, K)]
+    return bool(dense) and _use_gemm256(M, K, dense)
+
+
+def _dx_wants_rank_block(M, projs):
+    """Should the producers of the dX rank terms (lora_dx_terms, glu_bwd_terms, glu_bwd_tn) also write a rank block? When the
+    dX GEMM of every projection could run on the 256-tile family, asked at a nominal 64 output features. _dx_gemm, which has
+    the real dY in hand, takes the block when `_use_gemm256(M, N, [Kin])` holds for it: with a dY whose width N is no multiple
+    of 64 the block is written here and not used there (the 128-tile prologue runs)."""
+    return all(_use_gemm256(M, 64, [_features(p[0], p[1])[1]]) for p in projs)
 
 
 def _decoded_as(Wd, dtype):
@@ -606,10 +734,44 @@ def _decoded_as(Wd, dtype):
     return Wd
 
 
+def _forward_weight_operands(projs, M, K, dtype, device):
+    """Per projection of ONE forward launch, the twin of _dx_weight: None -- NF4 decoded inside the GEMM (_fused_nf4) -- or the
+    dense [N, K] operand: the member of the mirror group when every projection keeps a mirror, else its scratch slot (8 + its
+    index) filled by ONE grouped decode launch or a launch of its own, or the dense weight as is or as an aligned copy."""
+    Ws, qs = [p[0] for p in projs], [p[1] for p in projs]
+    fused = [_fused_nf4(q, M, K) for q in qs]
+    if len(projs) > 1 and not any(fused) and all(q is not None and _nf4.mirror_wanted(q) for q in qs):
+        return list(_nf4.resident_group(Ws, qs)[1])
+    decoded = {}
+    todo = [gi for gi, q in enumerate(qs) if q is not None and not fused[gi]]
+    if len(todo) > 1 and all(qs[gi].dtype == dtype and qs[gi].quant_type == "nf4" for gi in todo):
+        slots = [_nf4.scratch(device, qs[gi].shape[0] * qs[gi].shape[1], dtype, slot=8 + gi).view(tuple(qs[gi].shape))
+                 for gi in todo]
+        _nf4.dequantize_nf4_group([Ws[gi] for gi in todo], [qs[gi] for gi in todo], slots)
+        decoded = dict(zip(todo, slots))
+
+    def own(gi, W, q):
+        if q is not None:
+            return _decoded_as(_nf4.dequantize_nf4(W, q, use_global_buffer=True, slot=8 + gi), dtype)
+        return W if (W.dtype == dtype and _aligned_rows(W)) else _aligned_copy(W, dtype)
+    return [None if fused[gi] else decoded[gi] if gi in decoded else own(gi, Ws[gi], qs[gi]) for gi in range(len(projs))]
+
+
+def _forward_rank_term(term, B, s, N, fused, dtype):
+    """`_group` keywords of the rank term s (X A^T) B^T of one forward group, the twin of _dx_rank_term: BK = T(s B) at the
+    term's columns of its rank block, or -- no block, or NF4 decoded in the GEMM (`fused`) -- LB = T(B) for the prologue."""
+    P, xk = term.P, term.xk
+    if xk is not None and not fused:
+        return dict(xa=P, ld_xa=P.stride(0), R=P.shape[1], scale=s, xk=xk,
+                    bk=rank_block_bk([(B, term.col, s)], N, xk.shape[1], False, dtype))
+    return dict(xa=P, ld_xa=P.stride(0), R=P.shape[1], scale=s, lb=_pad_rank(B, P.shape[1], dtype))
+
+
 def lora_linear_forward(X, projs, outs=None, return_xa=False, pre_xa=None):
     """Y_g = X @ W_g^T + s_g * (X @ A_g^T) @ B_g^T for projections `projs` = [(W, W_quant, A, B, s)]
     that share X. Returns a list of [.., N_g] tensors. This is matmul_lora (utils.py:1128-1170)
-    for q/k/v or gate/up at once."""
+    for q/k/v or gate/up at once. `pre_xa`: the [RankTerm] of the adapters when the kernel that produced X formed them
+    (glu_fwd_xa). `return_xa`: also the fp32 [M, Rp] views of X @ A_g^T (None without adapter), kept for d_B = s dY^T (X A^T)."""
     _refuse_fp8(projs)
     _lib.require_gpu(X)
     dtype = X.dtype
@@ -617,153 +779,55 @@ def lora_linear_forward(X, projs, outs=None, return_xa=False, pre_xa=None):
         raise NotImplementedError("the MFMA GEMM path takes bf16/fp16 activations")
     X2d = _rows2d(X)
     M, K = X2d.shape
-    lead = X.shape[:-1]
-    # a projection may carry the base layer's bias as a 6th element (get_lora_parameters_bias order): it is added in the
-    # GEMM epilogue, in fp32, before the single rounding (Qwen2's q/k/v; the reference leaves such layers un-fused)
-    biases = [(p[5] if len(p) > 5 else None) for p in projs]
-    projs = [tuple(p[:5]) for p in projs]
-    with_lora = [p for p in projs if p[2] is not None]
-    Ns = [(q.shape[0] if q is not None else W.shape[0]) for (W, q, _, _, _) in projs]
-    fused_nf4 = [_fused_nf4(q, M, K) for (_, q, _, _, _) in projs]
-    # the dense groups go to the 256x256 kernel when the launch is large enough: there the LoRA term rides along as
-    # extra K tiles (XK = T(X A^T) zero-padded to 64 columns, BK_g = T(s_g B_g) at its rank columns)
-    dense_Ns = [n for n, f in zip(Ns, fused_nf4) if not f]
-    use256 = bool(dense_Ns) and _use_gemm256(M, K, dense_Ns)
-    xa, offs, xk = None, [], None
-    if with_lora and pre_xa is not None:
-        # X @ A^T already produced by the kernel that produced X (glu_fwd_xa: the gated activation computes h @ A_down^T
-        # while h is in its registers); the rank block must be there iff this launch wants it
-        xa, offs, xk = pre_xa
-        if (xk is not None) != use256:
-            xa, offs, xk = _xa_and_rank_block(X2d, [p[2] for p in with_lora], use256)
-    elif with_lora:
-        xa, offs, xk = _xa_and_rank_block(X2d, [p[2] for p in with_lora], use256)
-    results, dense_groups, nf4_groups, keep = [], [], [], []
-    resident = None
-    if len(projs) > 1 and all(q is not None and _nf4.mirror_wanted(q) for (_, q, _, _, _) in projs) and not any(fused_nf4):
-        _, resident = _nf4.resident_group([p_[0] for p_ in projs], [p_[1] for p_ in projs])
-    # the members that are decoded for this launch: ONE decode launch for all of them (nf4.dequantize_nf4_group), each into the
-    # scratch slot of its own that the grouped GEMM reads
-    decoded = {}
-    if resident is None:
-        todo = [gi for gi, (W, q, _, _, _) in enumerate(projs) if q is not None and not fused_nf4[gi]]
-        if len(todo) > 1 and all(projs[gi][1].dtype == dtype and projs[gi][1].quant_type == "nf4" for gi in todo):
-            slots = [_nf4.scratch(X.device, projs[gi][1].shape[0] * projs[gi][1].shape[1], dtype, slot=8 + gi).view(
-                tuple(projs[gi][1].shape)) for gi in todo]
-            _nf4.dequantize_nf4_group([projs[gi][0] for gi in todo], [projs[gi][1] for gi in todo], slots)
-            decoded = dict(zip(todo, slots))
-    li = 0
-    for gi, (W, W_quant, A, B, s) in enumerate(projs):
-        if W_quant is not None:
-            assert W_quant.shape[1] == K, "weight/in_features mismatch"
-        N = Ns[gi]
+    factors = [p[2] for p in projs if p[2] is not None]
+    want_k = _forward_wants_rank_block(M, K, projs)
+    if factors and (pre_xa is None or (pre_xa[0].xk is not None) != want_k):
+        # (a handed-over X A^T must come with its rank block iff this launch wants it)
+        pre_xa = _xa_and_rank_block(X2d, factors, want_k)
+    terms = iter(pre_xa or ())
+    operands = _forward_weight_operands(projs, M, K, dtype, X.device)
+    results, views, dense_groups, nf4_groups, keep = [], [], [], [], []
+    for gi, (p, Wd) in enumerate(zip(projs, operands)):
+        W, W_quant, A, B, s = p[:5]
+        N = _features(W, W_quant)[0]
+        assert W_quant is None or W_quant.shape[1] == K, "weight/in_features mismatch"
         C = _out2d(outs[gi], M, N, dtype, f"outs[{gi}]") if outs is not None else torch.empty((M, N), dtype=dtype, device=X.device)
         kw = {}
-        if biases[gi] is not None:
-            bias = biases[gi].detach()
+        # a projection may carry the base layer's bias as a 6th element (get_lora_parameters_bias order): it is added in the
+        # GEMM epilogue, in fp32, before the single rounding (Qwen2's q/k/v; the reference leaves such layers un-fused)
+        if len(p) > 5 and p[5] is not None:
+            bias = p[5].detach()
             if bias.dtype != dtype or not bias.is_contiguous():
                 bias = bias.to(dtype).contiguous()
             assert bias.numel() == N
-            keep.append(bias)
             kw["bias"] = bias
-        if A is not None:
-            o, rp = offs[li]
-            li += 1
-            if xk is not None and not fused_nf4[gi]:
-                bk = rank_block_bk([(B, o, s)], N, xk.shape[1], False, dtype)
-                keep.append(bk)
-                kw.update(xa=xa[:, o:], ld_xa=xa.stride(0), R=rp, scale=s, xk=xk, bk=bk)
-            else:
-                lb = _pad_rank(B, rp, dtype)
-                keep.append(lb)
-                kw.update(xa=xa[:, o:], ld_xa=xa.stride(0), lb=lb, R=rp, scale=s)
-        if fused_nf4[gi]:
+        term = next(terms) if A is not None else None
+        views.append(term.P if term is not None else None)
+        if term is not None:
+            kw.update(_forward_rank_term(term, B, s, N, Wd is None, dtype))
+        keep += [kw, Wd]                # (the groups hold addresses only)
+        if Wd is None:
             nf4_groups.append(_group(W, C, N, 0, absmax=_nf4.absmax_f32(W_quant), **kw))
         else:
-            Wd = W
-            if resident is not None:
-                Wd = resident[gi]
-            elif gi in decoded:
-                Wd = decoded[gi]
-            elif W_quant is not None:
-                # one scratch slot per group member: the grouped launch reads all of them
-                Wd = _decoded_as(_nf4.dequantize_nf4(W, W_quant, use_global_buffer=True, slot=8 + gi), dtype)
-            elif Wd.dtype != dtype or not _aligned_rows(Wd):
-                Wd = _aligned_copy(Wd, dtype)
-            keep.append(Wd)
             dense_groups.append(_group(Wd, C, N, Wd.stride(0), **kw))
-        results.append(C)
+        results.append(C.view(*X.shape[:-1], N))
     if nf4_groups:
         _launch_gemm(X2d, nf4_groups, nf4=True)
     if dense_groups:
         _launch_gemm(X2d, dense_groups, nf4=False)
-    results = [r.view(*lead, r.shape[-1]) for r in results]
-    if return_xa:
-        # per projection: fp32 [M, Rp] view of X @ A^T (None without adapter), kept for d_B = s * dY^T (X A^T)
-        views, li = [], 0
-        for (W, W_quant, A, B, s) in projs:
-            if A is None:
-                views.append(None)
-            else:
-                o, rp = offs[li]
-                li += 1
-                views.append(xa[:, o:o + rp])
-        return results, views
-    return results
+    return (results, views) if return_xa else results
 
 
 def lora_dx_terms(dYs, projs):
-    """P_g = dY_g @ B_g (fp32 [M, Rp]) for every projection with an adapter (None otherwise): the rank-r factor
-    shared by dX += s (dY B) A and by d_A = s (dY B)^T X (fast_lora.py:172-189).
-    When the dX GEMM will run on the 256x256 kernel, each launch also writes T(P_g) into a shared zero-padded
-    [M, 64k] rank block (attached to the returned tensor as `_uamd_xk = (xk, col_off)`): the XK operand of that
-    GEMM's extra K tiles."""
-    terms = []
-    projs = [tuple(p[:5]) for p in projs]              # (a 6th element, the bias, plays no part in any gradient but its own)
-    ranks = [None if A is None else A.shape[0] for (_, _, A, _, _) in projs]
+    """The RankTerm of P_g = dY_g @ B_g for every projection with an adapter (None otherwise): the rank-r factor shared by
+    dX += s (dY B) A and by d_A = s (dY B)^T X (fast_lora.py:172-189). All P_g sit side by side in ONE buffer when possible:
+    lora_linear_dx can then hand them to a single K-concatenated GEMM. With their rank block by _dx_wants_rank_block."""
     dY2 = [_rows2d(dY) for dY in dYs]
-    M = dY2[0].shape[0]
-    dev, dtype = dY2[0].device, dY2[0].dtype
-    Kin = [(q.shape[1] if q is not None else W.shape[1]) for (W, q, _, _, _) in projs]
-    want_k = (dtype in (torch.bfloat16, torch.float16) and LORA_XA_V2
-              and all(_use_gemm256(M, 64, [k]) for k in Kin))
-    # all P_g side by side in ONE [M, sum r] buffer when possible: lora_linear_dx can then hand the whole rank
-    # block to a single K-concatenated GEMM
-    shared, col = None, 0
-    with_lora = [r for r in ranks if r is not None]
-    if len(projs) > 1 and len(with_lora) == len(projs) and all(r % 8 == 0 for r in ranks):
-        shared = torch.empty((M, sum(ranks)), dtype=torch.float32, device=dev)
-    Rt = sum((r + 7) // 8 * 8 for r in with_lora)
-    xk = None
-    if want_k and with_lora and Rt <= 192 and max(with_lora) <= 64 and (shared is not None or len(with_lora) == 1):
-        xk = torch.empty((M, _rank_width(Rt)), dtype=dtype, device=dev)
-    n_left = len(with_lora)
-    for dY2d, (W, W_quant, A, B, s) in zip(dY2, projs):
-        if A is None:
-            terms.append(None)
-            continue
-        n_left -= 1
-        Bt = cast_lora_t(B, dtype)              # [r, N]
-        r = A.shape[0]
-        rp = (r + 7) // 8 * 8
-        kw = {}
-        if xk is not None:
-            # the last launch also zero-fills the padding columns up to the 64-multiple
-            kw = dict(out_k=xk[:, col:], k_cols=(xk.shape[1] - col) if n_left == 0 else rp)
-        if shared is not None:
-            xa, offs = lora_xa(dY2d, [Bt], out=shared[:, col:col + r], **kw)
-        else:
-            xa, offs = lora_xa(dY2d, [Bt], **kw)                    # dY @ B
-        t = xa[:, :offs[0][1]]
-        if xk is not None:
-            t._uamd_xk = (xk, col)
-        elif want_k:                            # odd ranks / total rank > 64: padded cast with torch ops
-            own = torch.zeros((M, _rank_width(t.shape[1])), dtype=dtype, device=dev)
-            own[:, :t.shape[1]] = t
-            t._uamd_xk = (own, 0)
-        col += rp
-        terms.append(t)
-    return terms
+    M, dtype = dY2[0].shape[0], dY2[0].dtype
+    want_k = dtype in (torch.bfloat16, torch.float16) and LORA_XA_V2 and _dx_wants_rank_block(M, projs)
+    plan = _rank_plan(tuple(None if p[2] is None else p[2].shape[0] for p in projs), tuple(dY.shape[1] for dY in dY2), want_k,
+                      one_input=False, v2=LORA_XA_V2)
+    return _rank_terms(plan, dY2, lambda i, padded: cast_lora_t(projs[i][3], dtype))         # rows of B^T [r, N]
 
 
 def _adjacent_columns(ts):
@@ -832,8 +896,7 @@ def _dx_rank_term(members, xa, xk, nn, Kin, dtype):
         return None
     A_list = [A for A, _, _ in members]
     if len(A_list) > 1:
-        tag = ("catT",) + tuple((id(A), A._version, A.data_ptr()) for A in A_list[1:])
-        lb = _cached_cast(A_list[0], tag, dtype,
+        lb = _cached_cast(A_list[0], _stack_tag("catT", A_list[1:]), dtype,
                           lambda: torch.cat([cast_lora_t(A, dtype) for A in A_list], dim=1).contiguous())
     elif A_list[0].shape[0] == xa.shape[1]:
         lb = cast_lora_t(A_list[0], dtype)                                                 # A^T [Kin, r]
@@ -844,19 +907,18 @@ def _dx_rank_term(members, xa, xk, nn, Kin, dtype):
 
 def _dx_gemm(dY2d, projs, terms, xa, out, accumulate):
     """out (+)= dY2d @ [W_1; W_2; ...] + xa @ [s_1 A_1; s_2 A_2; ...]: one GEMM over the (concatenated) output features
-    of `projs`. `terms` = per projection its P = dY B or None, `xa` = the [M, sum r] view of all of them (None without an
-    adapter). The NN form of the 256-tile family (no transposed copy of any weight) when the launch is large enough for
-    it and every rank term has its rank block, else a transposed decode and the NT form. Returns `out`, or None when the
-    rank term cannot go in one launch."""
+    of `projs`. `terms` = per projection its RankTerm (P = dY B) or None, `xa` = the [M, sum r] view of all the Ps (None
+    without an adapter). The NN form of the 256-tile family (no transposed copy of any weight) when the launch is large enough
+    for it and every rank term has its rank block, else a transposed decode and the NT form. The producers of the terms wrote
+    the blocks by _dx_wants_rank_block's guess of the answer given here. Returns `out`, or None when the rank term cannot go in
+    one launch."""
     M, N = dY2d.shape
     dtype = dY2d.dtype
-    W0, q0 = projs[0][:2]
-    Kin = q0.shape[1] if q0 is not None else W0.shape[1]
+    Kin = _features(*projs[0][:2])[1]
     if out is not None:
         out = _out2d(out, M, Kin, dtype, "out")
-    # per adapter (A, s, (rank block its P was also written to, at column)) -- lora_dx_terms / glu_bwd_terms attach the latter
-    lora = [(A, s, getattr(t, "_uamd_xk", None)) for (_, _, A, _, s), t in zip(projs, terms) if A is not None]
-    have_xk = all(x is not None and x[0] is lora[0][2][0] for _, _, x in lora)         # ONE block shared by all of them
+    lora = [(p[2], p[4], t) for p, t in zip(projs, terms) if p[2] is not None]
+    have_xk = all(t.xk is not None and t.xk is lora[0][2].xk for _, _, t in lora)      # ONE block shared by all of them
     use256 = _use_gemm256(M, N, [Kin])
     nn = use256 and Kin % 8 == 0 and have_xk
     Wd = _dx_weight(projs, nn, dtype)
@@ -864,8 +926,8 @@ def _dx_gemm(dY2d, projs, terms, xa, out, accumulate):
         out = torch.empty((M, Kin), dtype=dtype, device=dY2d.device)
     kw = {}
     if lora:
-        block = lora[0][2][0] if (have_xk and use256) else None
-        members = [(A, x[1] if block is not None else 0, s) for A, s, x in lora]
+        block = lora[0][2].xk if (have_xk and use256) else None
+        members = [(A, t.col if block is not None else 0, s) for A, s, t in lora]
         kw = _dx_rank_term(members, xa, block, nn, Kin, dtype)
         if kw is None:
             return None
@@ -878,12 +940,10 @@ def _lora_linear_dx_merged(dYs, projs, out, terms):
     incoming gradients are column blocks of one buffer (the attention backward writes dQ, dK, dV that way): the
     contraction simply runs over the concatenated output features. Saves the read-modify-write of dX per extra
     projection and the short-K launches (k_proj / v_proj: K = 1024). Returns None when the shapes do not allow it."""
-    if len(dYs) < 2 or any(q is None for (_, q, _, _, _) in projs):
-        return None
-    if any(A is None for (_, _, A, _, _) in projs) or any(t is None for t in terms):
+    if len(dYs) < 2 or any(p[1] is None or p[2] is None for p in projs) or any(t is None for t in terms):
         return None
     dYcat = _adjacent_columns([_rows2d(dY) for dY in dYs])
-    Pcat = _adjacent_columns(list(terms))
+    Pcat = _adjacent_columns([t.P for t in terms])
     if dYcat is None or Pcat is None or dYcat.shape[1] % 64 or dYcat.stride(0) % 8:
         return None
     Kin = projs[0][1].shape[1]
@@ -904,8 +964,8 @@ def lora_linear_dx(dYs, projs, out=None, terms=None):
     merged = _lora_linear_dx_merged(dYs, projs, out, terms)
     if merged is not None:
         return merged
-    for gi, (dY, proj, xa) in enumerate(zip(dYs, projs, terms)):
-        out = _dx_gemm(_rows2d(dY), [proj], [xa], xa, out, accumulate=gi > 0)
+    for gi, (dY, proj, t) in enumerate(zip(dYs, projs, terms)):
+        out = _dx_gemm(_rows2d(dY), [proj], [t], t.P if t is not None else None, out, accumulate=gi > 0)
     return out
 
 
@@ -1033,7 +1093,7 @@ def _glu_fusable(dtype, tensors, ranks, backward):
         return False
     return (LORA_XA_V2 and dtype in (torch.bfloat16, torch.float16) and K % 8 == 0
             and all(t.is_cuda and t.dtype == dtype for t in tensors) and _same_rows(tensors)
-            and all(r is not None and r % 8 == 0 and 0 < r <= 64 for r in ranks))
+            and all(r is not None and _streams(r) for r in ranks))
 
 
 _GLU_WS = {}        # (device index, stream) -> (fp32 partials, int32 arrival counters): the column-split kernels' workspace
@@ -1056,9 +1116,9 @@ def _glu_workspace(t, n_products, max_rank):
 
 def glu_fwd_xa(act, e, g, down, n_out_cols_hint=None):
     """h = act(e) * g AND the down projection's X A^T (fp32 [M, r]) + rank block, in ONE pass over e and g
-    (uamd_glu_fwd_xa). `down` = (W, W_quant, A, B, s[, bias]). Returns (h, pre_xa) with pre_xa = (xa, offs, xk) as
-    lora_linear_forward(pre_xa=) takes it, or None when the shapes do not allow the fusion (the caller then runs the plain
-    activation kernel and lets lora_linear_forward compute X A^T itself)."""
+    (uamd_glu_fwd_xa). `down` = (W, W_quant, A, B, s[, bias]). Returns (h, [RankTerm]) as lora_linear_forward(pre_xa=) takes
+    it -- the rank block by _forward_wants_rank_block, which that launch asks too -- or None when the shapes do not allow the
+    fusion (the caller then runs the plain activation kernel and lets lora_linear_forward compute X A^T itself)."""
     A = down[2]
     # SwiGLU only (the hot path's activation): its fused arithmetic is bit-identical to the plain kernel, which is pinned
     # bit for bit to the reference's Triton kernel; the GeGLU instantiations differ from theirs in the last place in fp16
@@ -1067,9 +1127,7 @@ def glu_fwd_xa(act, e, g, down, n_out_cols_hint=None):
     M, K = e.shape
     dtype = e.dtype
     r = A.shape[0]
-    W, q = down[0], down[1]
-    N = q.shape[0] if q is not None else W.shape[0]
-    want_k = (not _fused_nf4(q, M, K)) and _use_gemm256(M, K, [N])
+    want_k = _forward_wants_rank_block(M, K, [down])
     Ac = cast_lora(A, dtype)
     h = alloc_rows(M, K, dtype, e.device, ld=e.stride(0))          # (one `ld` for e, g and h)
     xa = torch.empty((M, r), dtype=torch.float32, device=e.device)
@@ -1084,42 +1142,37 @@ def glu_fwd_xa(act, e, g, down, n_out_cols_hint=None):
     if rc != 0:
         counters.zero_()                 # a launch that did not complete may leave arrival counts behind (include/unsloth_amd.h)
     _lib.check(rc, "uamd_glu_fwd_xa_ws")
-    return h, (xa, [(0, r)], xk)
+    return h, [RankTerm(xa, xk, 0)]
 
 
 def glu_bwd_terms(act, DW, e, g, up, gate):
     """The in-place activation backward (DW <- h, e <- df, g <- de) AND P_up = df @ B_up, P_gate = de @ B_gate -- the
     lora_dx_terms([df, de], [up, gate]) of fast_lora.mlp_backward -- in ONE pass (uamd_glu_bwd_xa). Returns
-    (h, df, de, [p_up, p_gate]) or None when the shapes do not allow the fusion."""
+    (h, df, de, [p_up, p_gate] as RankTerms) or None when the shapes do not allow the fusion."""
     (Au, Bu), (Ag, Bg) = (up[2], up[3]), (gate[2], gate[3])
     if act != "swiglu" or Au is None or Ag is None or not _glu_fusable(e.dtype, [DW, e, g], [Au.shape[0], Ag.shape[0]], True):
         return None
     M, K = e.shape
     dtype = e.dtype
     ru, rg = Au.shape[0], Ag.shape[0]
-    Kin = [(p[1].shape[1] if p[1] is not None else p[0].shape[1]) for p in (up, gate)]
-    want_k = all(_use_gemm256(M, 64, [k]) for k in Kin)
+    want_k = _dx_wants_rank_block(M, (up, gate))
     But, Bgt = cast_lora_t(Bu, dtype), cast_lora_t(Bg, dtype)                        # [r, K]
     shared = torch.empty((M, ru + rg), dtype=torch.float32, device=e.device)
     xk = torch.empty((M, _rank_width(ru + rg)), dtype=dtype, device=e.device) if want_k else None
     pu, pg = shared[:, :ru], shared[:, ru:]
-    null = None
     with _lib.device_ctx(e):
         part, counters = _glu_workspace(e, 2, max(ru, rg))
         rc = _lib.lib().uamd_glu_bwd_xa_ws(
             _GLU_ACTS[act], _lib.ptr(DW), _lib.ptr(e), _lib.ptr(g), M, K, e.stride(0),
             _lib.ptr(But), But.stride(0), ru, _lib.ptr(pu), shared.stride(0), ru,
-            _lib.ptr(xk) if want_k else null, xk.stride(0) if want_k else 0, ru if want_k else 0,
+            _lib.ptr(xk), xk.stride(0) if want_k else 0, ru if want_k else 0,
             _lib.ptr(Bgt), Bgt.stride(0), rg, _lib.ptr(pg), shared.stride(0), rg,
-            _lib.ptr(xk[:, ru:]) if want_k else null, xk.stride(0) if want_k else 0, (xk.shape[1] - ru) if want_k else 0,
+            _lib.ptr(xk[:, ru:]) if want_k else None, xk.stride(0) if want_k else 0, (xk.shape[1] - ru) if want_k else 0,
             _lib.ptr(part), part.numel(), _lib.ptr(counters), _lib.dtype_code(dtype), _lib.stream_of(e))
     if rc != 0:
         counters.zero_()
     _lib.check(rc, "uamd_glu_bwd_xa_ws")
-    if want_k:
-        pu._uamd_xk = (xk, 0)
-        pg._uamd_xk = (xk, ru)
-    return DW, e, g, [pu, pg]
+    return DW, e, g, [RankTerm(pu, xk, 0), RankTerm(pg, xk, ru)]
 
 
 # The SwiGLU backward that also forms the MLP's three wide LoRA gradients (csrc/glu.hip glu_tn_kernel): glu_bwd_terms writes h
@@ -1151,7 +1204,7 @@ def glu_bwd_tn(act, DW, e, g, up, gate, down, p_d, xa_u, xa_g, targets=None):
         p_up = df @ B_up, p_gate = de @ B_gate                 (fp32 [M, r] + the dX GEMM's rank block, as glu_bwd_terms)
         dA_down = s (p_d^T h), dB_up = s (df^T xa_u), dB_gate = s (de^T xa_g)      (fp32, as lora_tn returns them)
     with p_d = dY @ B_down, xa_u = X @ A_up^T, xa_g = X @ A_gate^T (fp32 [M, >= r]). `targets`: three contiguous fp32 tensors
-    (or None each) to ACCUMULATE dA_down / dB_up / dB_gate into. Returns (df, de, [p_up, p_gate], [dA_down, dB_up, dB_gate]),
+    (or None each) to ACCUMULATE dA_down / dB_up / dB_gate into. Returns (df, de, [p_up, p_gate] as RankTerms, [dA_down, dB_up, dB_gate]),
     or None -- nothing launched, nothing touched -- when the shape is not taken (glu_tn_takes)."""
     if not glu_tn_takes(act, DW, e, g, up, gate, down):
         return None
@@ -1160,8 +1213,7 @@ def glu_bwd_tn(act, DW, e, g, up, gate, down, p_d, xa_u, xa_g, targets=None):
     ru, rg, rd = up[2].shape[0], gate[2].shape[0], down[2].shape[0]
     if any(P.dim() != 2 or P.shape[0] != M or P.shape[1] < r for P, r in ((p_d, rd), (xa_u, ru), (xa_g, rg))):
         raise ValueError("glu_bwd_tn: p_d / xa_u / xa_g must be fp32 [M, >= rank]")
-    Kin = [(p[1].shape[1] if p[1] is not None else p[0].shape[1]) for p in (up, gate)]
-    want_k = all(_use_gemm256(M, 64, [k]) for k in Kin)
+    want_k = _dx_wants_rank_block(M, (up, gate))
     But, Bgt = cast_lora_t(up[3], dtype), cast_lora_t(gate[3], dtype)                # [r, K]
     p_d, xa_u, xa_g = _tn_factor(p_d, rd), _tn_factor(xa_u, ru), _tn_factor(xa_g, rg)
     shapes = [(rd, K), (K, ru), (K, rg)]
@@ -1190,11 +1242,7 @@ def glu_bwd_tn(act, DW, e, g, up, gate, down, p_d, xa_u, xa_g, targets=None):
     if rc in _lib._ERR:         # one of the library's own codes: rejected before any launch -- "not supported", not "failed"
         return None
     _lib.check(rc, "uamd_glu_bwd_tn_ws")
-    pu, pg = shared[:, :ru], shared[:, ru:]
-    if want_k:
-        pu._uamd_xk = (xk, 0)
-        pg._uamd_xk = (xk, ru)
-    return e, g, [pu, pg], grads
+    return e, g, [RankTerm(shared[:, :ru], xk, 0), RankTerm(shared[:, ru:], xk, ru)], grads
 
 
 def dense_dw(dY, X, out=None, accumulate=False):
@@ -1266,7 +1314,7 @@ def fast_linear_forward(proj, X, temp_lora=None, out=None):
     W, W_quant, A, B, s, bias = get_lora_parameters_bias(proj)
     _refuse_fp8([(W,)])
     bsz, q_len, in_dim = X.shape
-    n_out = int(W_quant.shape[0]) if W_quant is not None else int(W.shape[0])
+    n_out = int(_features(W, W_quant)[0])
     if bsz == 1 and q_len == 1 and in_dim <= 16384 and X.dtype in (torch.bfloat16, torch.float16) \
             and (W_quant is not None or W.dtype == X.dtype):
         flat = out.view(-1) if out is not None else None
