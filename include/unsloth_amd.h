@@ -450,6 +450,19 @@ typedef struct {
 } uamd_gemv_group;
 int uamd_gemv(const void* x, int K, const uamd_gemv_group* groups, int n_groups, int nf4, int blocksize, int dtype,
               void* stream);
+/* uamd_gemv_rows: uamd_gemv for M = 1 .. 16 token rows that share ONE pass over the weights (the decode step of a batch):
+ *   Y_g[m, n] = W_g[n, :] . X[m, :] (+ lora_scale_g * LB_g[n, :] . T_g[m, :] + bias_g[n])   for m < M, up to 4 groups.
+ * x is [M, ldx] (ldx >= K, ldx % 8 == 0, 16-byte aligned); every group's y addresses rows of stride ldy elements (of dtype, or
+ * of float when y_f32), so the groups can write adjacent column ranges of one [M, ldy] buffer; every group's lora_t is fp32
+ * [M, ldt], produced by an earlier launch of this function over the stacked A rows with y_f32 = 1. The group struct and the
+ * limits are uamd_gemv's: K % 8 == 0 (nf4: K % 32 == 0, blocksize a power of two >= 32), K <= 16384, R <= 64, nested or
+ * single-level absmax, dense 16-bit weights with nf4 == 0, bf16 and fp16. Anything else: UAMD_ERR_ARG / UAMD_ERR_ALIGN, and
+ * nothing is launched.
+ * Row independence: the bits of Y[m, :] depend on X[m, :] and the weights alone -- not on M, not on m, not on the other rows
+ * (a non-finite row stays in its own outputs). Rows m >= M are neither read nor written, and no column outside the groups'
+ * [0, N) is written. */
+int uamd_gemv_rows(const void* x, int64_t ldx, int M, int K, const uamd_gemv_group* groups, int n_groups, int64_t ldy,
+                   int64_t ldt, int nf4, int blocksize, int dtype, void* stream);
 /* uamd_gemv_fused: the same launch with the token PRODUCED inside it and the LoRA `t = A x` computed INSIDE it, once, so that
  * one decoder layer of a decode step is 5 launches (q|k|v, attention, o, gate|up -> h, down) instead of 14
  * (LlamaModel_fast_forward_inference, llama.py:1249-1364: residual adds, fast_rms_layernorm_inference, fast_swiglu_inference

@@ -164,6 +164,8 @@ SIGNATURES = {
     "uamd_attn_bwd": (c_int, [c_void_p] * 10 + [ctypes.POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_int,
                                                c_float, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "uamd_gemv": (c_int, [c_void_p, c_int, ctypes.POINTER(GemvGroup), c_int, c_int, c_int, c_int, c_void_p]),
+    "uamd_gemv_rows": (c_int, [c_void_p, c_int64, c_int, c_int, ctypes.POINTER(GemvGroup), c_int, c_int64, c_int64, c_int, c_int,
+                               c_int, c_void_p]),
     "uamd_gemv_fused": (c_int, [c_void_p, c_int, ctypes.POINTER(GemvGroup), c_int, c_int, c_int, c_int, c_void_p,
                                 ctypes.POINTER(GemvPrologue)]),
     "uamd_rope_kv_append": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -28,6 +28,7 @@
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+typedef __attribute__((ext_vector_type(4))) float rows_f32x4;
 
 namespace {
 
@@ -721,6 +722,248 @@ int launch_gemv(const GemvArgs& a, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// uamd_gemv_rows: the GEMV for M = 1 .. 16 token rows that share ONE pass over the weights (a decode step of a batch).
+//
+//   * v_mfma_f32_16x16x32: the A operand is 16 weight rows, the B operand the token rows (rows >= M are zero fragments), the
+//     accumulator D[n][m] fp32. Lane l feeds row l & 15 of both operands at the 8 k slots of quad l >> 4; the order in which
+//     columns meet the slots is free as long as both operands agree, so a lane's 16-byte weight load -- 32 consecutive NF4
+//     codes of one row inside one absmax block, or 8 dense elements -- goes straight from memory into fragments: no LDS
+//     round trip for the weights.
+//   * NF4: byte -> packed pair of levels through the GEMV's bank-replicated table, times the block's absmax in fp32, rounded
+//     once to T (an MFMA sums over the four quads, i.e. over two absmax blocks: the scale cannot wait for the accumulator).
+//   * One workgroup = 8 waves = RT adjacent 16-row tiles of one group. The waves split K: wave w takes the 128-column
+//     chunks w, w + 8, ..., so the eight of them read 512 contiguous bytes of a row side by side, and a wave's X fragments
+//     serve its RT tiles. Loads run one stage (a chunk of every tile) ahead of the MFMAs.
+//   * The eight partial tiles meet in LDS and are summed in wave order 0 .. 7: the value of Y[m][n] is a fixed sequence of
+//     operations on row m and weight row n alone -- it depends neither on M, nor on m, nor on the other token rows, nor on RT
+//     (the MFMA computes each D element from its own A row and B column). A NaN in one token row stays in its column of D.
+//   * The epilogue (all 512 threads, one output each per pass) adds the LoRA term s * B[n, :] . t[m, :] (t fp32, from an
+//     earlier launch over the stacked A rows) and the bias, and stores to y + m * ldy + n.
+constexpr int ROWS_THREADS = 512, ROWS_WAVES = ROWS_THREADS / 64, ROWS_CHUNK = 128;
+struct GemvRowsArgs {
+    const void* x;
+    int64_t ldx, ldy, ldt;
+    int M, K, n_groups, bs_shift;
+    int blk_start[UAMD_GEMV_MAX_GROUPS + 1];       // group g owns workgroups [blk_start[g], blk_start[g + 1])
+    uamd_gemv_group g[UAMD_GEMV_MAX_GROUPS];       // (blocksize2 as a shift)
+};
+
+template <typename T> struct RowsMfma;
+template <> struct RowsMfma<bf16_t> {
+    typedef __attribute__((ext_vector_type(8))) __bf16 frag;
+    static __device__ __forceinline__ rows_f32x4 run(frag a, frag b, rows_f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+};
+template <> struct RowsMfma<f16_t> {
+    typedef __attribute__((ext_vector_type(8))) _Float16 frag;
+    static __device__ __forceinline__ rows_f32x4 run(frag a, frag b, rows_f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+};
+
+template <typename T, bool NF4, int RT>
+__global__ void __launch_bounds__(ROWS_THREADS) gemv_rows_kernel(GemvRowsArgs p) {
+    typedef typename RowsMfma<T>::frag frag;
+    constexpr int WV = NF4 ? 1 : 4;                  // 16-byte weight loads per lane, tile and chunk
+    extern __shared__ __attribute__((aligned(16))) unsigned char rows_smem[];
+    // layout: code2 [256] float | lut2 [256][32] u32 (NF4); after the K loop the partial tiles [8][RT][64] x 16 bytes from 0
+    float* code2 = reinterpret_cast<float*>(rows_smem);
+    uint32_t* lut2 = reinterpret_cast<uint32_t*>(rows_smem + 1024);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, q = lane >> 4;
+    const int K = p.K, M = p.M;
+    int gi = 0;
+    if (1 < p.n_groups && (int)blockIdx.x >= p.blk_start[1]) gi = 1;
+    if (2 < p.n_groups && (int)blockIdx.x >= p.blk_start[2]) gi = 2;
+    if (3 < p.n_groups && (int)blockIdx.x >= p.blk_start[3]) gi = 3;
+    const uamd_gemv_group& g = p.g[gi];
+    const int N = g.N;
+    const int n0 = ((int)blockIdx.x - p.blk_start[gi]) * 16 * RT;
+    const bool dir = NF4 && g.absmax_f32 != nullptr;
+    if (NF4 && tid < 256) {
+        code2[tid] = (!dir && g.code2) ? g.code2[tid] : 0.f;
+        const uint32_t v = pack2<T>(kNF4[tid >> 4], kNF4[tid & 15]);       // high nibble = even element
+        uint4* dst = reinterpret_cast<uint4*>(lut2 + tid * 32);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) dst[c] = make_uint4(v, v, v, v);
+    }
+    // a lane's rows: weight row n0 + 16 t + r of tile t (past the group's end: its last row again, never stored) and token row
+    // r (rows >= M: row 0's address, the fragment zeroed -- such rows are not read)
+    const bool mok = r < M;
+    const T* const xrow = (const T*)p.x + (int64_t)(mok ? r : 0) * p.ldx;
+    int64_t wrow[RT];                                // NF4: first code of the row; dense: first element
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+        const int n = min(n0 + 16 * t + r, N - 1);
+        wrow[t] = (int64_t)n * (NF4 ? (int64_t)K : g.ldw);
+    }
+    // nested or single-level absmax without a branch in the loop: the byte load of the single-level case reads the weights
+    const uint8_t* const pa8 = dir ? (const uint8_t*)g.W : g.absmax_u8;
+    const float* const pa2 = dir ? g.absmax_f32 : g.absmax2;
+    const int sh2 = dir ? 0 : g.blocksize2;
+    const float offset = g.offset;
+    const int nch = (K + ROWS_CHUNK - 1) / ROWS_CHUNK;
+    auto col_of = [&](int c, int j) { return NF4 ? c * ROWS_CHUNK + q * 32 + j * 8 : c * ROWS_CHUNK + j * 32 + q * 8; };
+
+    struct Stage {
+        uint4 w[RT][WV];
+        uint32_t a8[RT];
+        float a2[RT];
+        uint4 x[4];
+    };
+    auto load = [&](Stage& s, int c) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int col = col_of(c, j);
+            s.x[j] = *reinterpret_cast<const uint4*>(xrow + (col < K ? col : 0));
+        }
+#pragma unroll
+        for (int t = 0; t < RT; ++t) {
+            if constexpr (NF4) {
+                const int col = col_of(c, 0);
+                const int64_t e = wrow[t] + (col < K ? col : 0);
+                const uamd_u32x4 v = __builtin_nontemporal_load(
+                    reinterpret_cast<const uamd_u32x4*>((const uint8_t*)g.W + (e >> 1)));
+                s.w[t][0] = make_uint4(v[0], v[1], v[2], v[3]);
+                const int64_t blk = e >> p.bs_shift;
+                s.a8[t] = pa8[blk];
+                s.a2[t] = pa2[blk >> sh2];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int col = col_of(c, j);
+                    const uamd_u32x4 v = __builtin_nontemporal_load(
+                        reinterpret_cast<const uamd_u32x4*>((const T*)g.W + wrow[t] + (col < K ? col : 0)));
+                    s.w[t][j] = make_uint4(v[0], v[1], v[2], v[3]);
+                }
+                s.a8[t] = 0;
+                s.a2[t] = 0.f;
+            }
+        }
+    };
+    rows_f32x4 acc[RT];
+#pragma unroll
+    for (int t = 0; t < RT; ++t) acc[t] = rows_f32x4{0.f, 0.f, 0.f, 0.f};
+    const uint32_t* const lut_lane = lut2 + (lane & 31);
+    union F { uint4 u; uint32_t w[4]; frag f; };
+    auto compute = [&](const Stage& s, int c) {
+        F xb[4];
+        bool in[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            in[j] = col_of(c, j) < K;
+            xb[j].u = (mok && in[j]) ? s.x[j] : make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int t = 0; t < RT; ++t) {
+            if constexpr (NF4) {
+                // columns past K: the weights are a real row's (finite values), the token fragment is zero
+                const float am = dir ? s.a2[t] : code2[s.a8[t]] * s.a2[t] + offset;
+                const uint32_t ww[4] = {s.w[t][0].x, s.w[t][0].y, s.w[t][0].z, s.w[t][0].w};
+                uint32_t dec[16];                            // all 16 table reads first: one LDS latency, not 16
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) dec[4 * j + b] = lut_lane[((ww[j] >> (8 * b)) & 0xffu) * 32];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    F a;
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        const uint32_t pr = dec[4 * j + b];
+                        a.w[b] = pack2<T>(bits16_to_f32<T>(pr & 0xffffu) * am, bits16_to_f32<T>(pr >> 16) * am);
+                    }
+                    acc[t] = RowsMfma<T>::run(a.f, xb[j].f, acc[t]);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    F a;                                     // columns past K: zero (the bits read there may be a NaN's)
+                    a.u = in[j] ? s.w[t][j] : make_uint4(0, 0, 0, 0);
+                    acc[t] = RowsMfma<T>::run(a.f, xb[j].f, acc[t]);
+                }
+            }
+        }
+    };
+    Stage s0, s1;
+    int c = wave;
+    if (c < nch) load(s0, c);
+    if (NF4) __syncthreads();                        // the tables
+    for (; c < nch; c += 2 * ROWS_WAVES) {
+        const bool more = c + ROWS_WAVES < nch;
+        if (more) load(s1, c + ROWS_WAVES);
+        compute(s0, c);
+        if (more) {
+            if (c + 2 * ROWS_WAVES < nch) load(s0, c + 2 * ROWS_WAVES);
+            compute(s1, c + ROWS_WAVES);
+        }
+    }
+    // ---- the eight partial tiles -> LDS -> summed in wave order
+    __syncthreads();                                 // (the tables are dead)
+    rows_f32x4* red = reinterpret_cast<rows_f32x4*>(rows_smem);
+#pragma unroll
+    for (int t = 0; t < RT; ++t) red[(wave * RT + t) * 64 + lane] = acc[t];
+    __syncthreads();
+    const float* redf = reinterpret_cast<const float*>(rows_smem);
+    const int R = g.lora_b ? g.R : 0;
+    for (int o = tid; o < RT * 256; o += ROWS_THREADS) {
+        const int nl = o & 15, m = (o >> 4) & 15, t = o >> 8;
+        const int n = n0 + 16 * t + nl;
+        if (m >= M || n >= N) continue;
+        const int src = ((nl >> 2) * 16 + m) * 4 + (nl & 3);        // D[row nl][col m]: lane (nl / 4) * 16 + m, register nl % 4
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < ROWS_WAVES; ++w) v += redf[(w * RT + t) * 256 + src];
+        if (R > 0) {
+            const float* tv = g.lora_t + (int64_t)m * p.ldt;
+            float l = 0.f;
+            if (g.lora_b_f32) {
+                const float* bv = (const float*)g.lora_b + (int64_t)n * g.ld_lb;
+                for (int j = 0; j < R; ++j) l += bv[j] * tv[j];
+            } else {
+                const T* bv = (const T*)g.lora_b + (int64_t)n * g.ld_lb;
+                for (int j = 0; j < R; ++j) l += to_f32(bv[j]) * tv[j];
+            }
+            v += g.lora_scale * l;
+        }
+        if (g.bias) v += to_f32(((const T*)g.bias)[n]);
+        if (g.y_f32) ((float*)g.y)[(int64_t)m * p.ldy + n] = v;
+        else ((T*)g.y)[(int64_t)m * p.ldy + n] = from_f32<T>(v);
+    }
+}
+
+template <typename T, bool NF4, int RT>
+int launch_gemv_rows_rt(GemvRowsArgs a, hipStream_t st) {
+    int blocks = 0;
+    for (int i = 0; i < UAMD_GEMV_MAX_GROUPS; ++i) {
+        a.blk_start[i] = blocks;
+        if (i < a.n_groups) blocks += (a.g[i].N + 16 * RT - 1) / (16 * RT);
+    }
+    a.blk_start[UAMD_GEMV_MAX_GROUPS] = blocks;
+    const int tables = NF4 ? 1024 + 256 * 32 * 4 : 0, red = ROWS_WAVES * RT * 64 * 16;
+    const int lds = tables > red ? tables : red;
+    if (lds > 48 * 1024)
+        if (int rc = uamd_lds_optin<&gemv_rows_kernel<T, NF4, RT>>(lds)) return rc;
+    hipLaunchKernelGGL((gemv_rows_kernel<T, NF4, RT>), dim3(blocks), dim3(ROWS_THREADS), lds, st, a);
+    return uamd_launch_status();
+}
+
+// RT: as many tiles per workgroup (token fragments shared) as still leave two workgroups for every CU
+template <typename T, bool NF4>
+int launch_gemv_rows(const GemvRowsArgs& a, hipStream_t st) {
+    int tiles = 0;
+    for (int i = 0; i < a.n_groups; ++i) tiles += (a.g[i].N + 15) / 16;
+    const int want = 2 * uamd_cu_count_or_256();
+    if constexpr (NF4) {
+        if (tiles >= 4 * want) return launch_gemv_rows_rt<T, true, 4>(a, st);
+    }
+    if (tiles >= 2 * want) return launch_gemv_rows_rt<T, NF4, 2>(a, st);
+    return launch_gemv_rows_rt<T, NF4, 1>(a, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // RoPE (rotate-half, the training kernel's arithmetic and rounding points) on the new token's q and k, and the
 // append of k, v to the cache at position kv_len[b]. qkv: [B, (Hq + 2 Hk) D] as the fused q|k|v GEMV wrote it.
 //
@@ -1295,6 +1538,43 @@ extern "C" int uamd_gemv(const void* x, int K, const uamd_gemv_group* groups, in
 extern "C" int uamd_gemv_fused(const void* x, int K, const uamd_gemv_group* groups, int n_groups, int nf4, int blocksize,
                                int dtype, void* stream, const uamd_gemv_prologue* pro) {
     return gemv_entry(x, K, groups, n_groups, nf4, blocksize, dtype, stream, pro);
+}
+
+// Y_g[m, n] = W_g[n, :] . X[m, :] (+ s_g * B_g[n, :] . T_g[m, :] + bias_g[n]) for M = 1 .. 16 token rows in ONE pass over the
+// weights: the decode step of a batch (gemv_rows_kernel). The groups are uamd_gemv's; every group's y and lora_t address
+// rows of stride ldy / ldt.
+extern "C" int uamd_gemv_rows(const void* x, int64_t ldx, int M, int K, const uamd_gemv_group* groups, int n_groups,
+                              int64_t ldy, int64_t ldt, int nf4, int blocksize, int dtype, void* stream) {
+    if (!x || !groups || n_groups < 1 || n_groups > UAMD_GEMV_MAX_GROUPS || M < 1 || M > 16 || K <= 0 || K > 16384 || ldx < K ||
+        ldy < 1 || ldt < 0)
+        return UAMD_ERR_ARG;
+    if (nf4 && (blocksize < 32 || (blocksize & 31) || (K & 31))) return UAMD_ERR_ARG;
+    if ((K & 7) || (ldx & 7) || !aligned16(x)) return UAMD_ERR_ALIGN;
+    auto log2_exact = [](int v) { int sft = 0; while ((1 << sft) < v) ++sft; return (1 << sft) == v ? sft : -1; };
+    GemvRowsArgs a;
+    a.x = x; a.ldx = ldx; a.ldy = ldy; a.ldt = ldt; a.M = M; a.K = K; a.n_groups = n_groups;
+    a.bs_shift = nf4 ? log2_exact(blocksize) : 0;
+    if (a.bs_shift < 0) return UAMD_ERR_ARG;
+    for (int i = 0; i < UAMD_GEMV_MAX_GROUPS; ++i) {
+        a.g[i] = groups[i < n_groups ? i : 0];
+        if (i >= n_groups) continue;
+        uamd_gemv_group& g = a.g[i];
+        if (!g.W || !g.y || g.N <= 0) return UAMD_ERR_ARG;
+        if (!aligned16(g.W)) return UAMD_ERR_ALIGN;
+        if (nf4) {
+            if (!g.absmax_f32 && !(g.absmax_u8 && g.code2 && g.absmax2 && g.blocksize2 > 0)) return UAMD_ERR_ARG;
+            if (!g.absmax_f32 && (g.blocksize2 = log2_exact(g.blocksize2)) < 0) return UAMD_ERR_ARG;
+        } else if (g.ldw < K) {
+            return UAMD_ERR_ARG;
+        } else if (g.ldw & 7) {
+            return UAMD_ERR_ALIGN;
+        }
+        if (g.lora_t && (!g.lora_b || g.R <= 0 || g.R > 64 || g.ld_lb < g.R || ldt < g.R)) return UAMD_ERR_ARG;
+        if (!g.lora_t) g.lora_b = nullptr;            // (a B without a t: no LoRA term)
+    }
+    hipStream_t st = (hipStream_t)stream;
+    UAMD_DISPATCH_HALF(dtype, return nf4 ? launch_gemv_rows<T, true>(a, st) : launch_gemv_rows<T, false>(a, st))
+    return UAMD_ERR_DTYPE;
 }
 
 // RoPE on the new token's q, k (in place in the fused qkv row) + append of k, v at cache position kv_len[b]

@@ -3,7 +3,8 @@
 `fast_gemv` / the bsz == 1 branch of `fast_linear_forward` (utils.py:872-977, :1082-1125) become ONE `uamd_gemv`
 launch per group of projections that share the token (q|k|v, gate|up), plus one small `uamd_gemv` over the LoRA A rows
 that share it. NF4 weights are read in bitsandbytes' format straight from the `Params4bit` storage: nothing is
-dequantised to memory.
+dequantised to memory. The token rows of a batch of 2 .. 16 sequences share one pass over the weights: `uamd_gemv_rows`
+(`gemv_rows`, `linear_group_rows`), where utils.py:1095-1097 dequantises and calls matmul.
 """
 import ctypes
 
@@ -225,6 +226,103 @@ def linear_group(x, projs, out=None, fused=None):
     ys = []
     for i in range(0, len(groups), MAX_GROUPS):
         ys += gemv(x, groups[i:i + MAX_GROUPS], nf4=nf4, blocksize=blocksize)
+    return ys
+
+
+MAX_ROWS = 16                         # token rows of one uamd_gemv_rows launch
+
+
+def gemv_rows(x, groups, nf4, blocksize=64, M=None):
+    """One uamd_gemv_rows launch: x [M, K] (unit stride along K, any row stride that is a multiple of 8; M <= 16) against the
+    groups of `gemv`. A group's `y` is an [M, N] view whose rows may be strided (all groups of a launch share the row stride:
+    adjacent column ranges of one buffer) and is allocated when absent; `lora_t` is fp32 [M, R] (a column range of the t
+    buffer, one row stride for all groups). `M` < x.shape[0] launches the first M rows only. Returns the outputs."""
+    _lib.require_gpu(x)
+    assert x.dim() == 2 and x.stride(1) == 1
+    M = x.shape[0] if M is None else int(M)
+    K = x.shape[1]
+    dtype, dev = x.dtype, x.device
+    assert 1 <= len(groups) <= MAX_GROUPS
+    arr = (GemvGroup * len(groups))()
+    outs, keep, ldy, ldt, f32 = [], [], None, 0, None
+    for i, g in enumerate(groups):
+        N = g["N"]
+        y_f32 = bool(g.get("y_f32", False))
+        y = g.get("y")
+        if y is None:
+            y = torch.empty(x.shape[0], N, dtype=torch.float32 if y_f32 else dtype, device=dev)
+        assert y.dim() == 2 and y.shape[1] == N and y.stride(1) == 1 and y.dtype == (torch.float32 if y_f32 else dtype)
+        assert y.shape[0] >= M and (M == 1 or ldy in (None, y.stride(0))), "the groups of a launch share the row stride of y"
+        assert f32 in (None, y_f32), "a launch stores 16-bit or fp32 rows, not both"
+        ldy, f32 = (y.stride(0) if M > 1 else N), y_f32         # (one row: the stride is never used)
+        outs.append(y)
+        W = g["W"]
+        e = arr[i]
+        e.W = W.data_ptr()
+        if nf4:
+            a_u8, a_f32, code2, absmax2, off, bs2 = _nf4_fields(g["qs"])
+            e.absmax_u8 = a_u8.data_ptr() if a_u8 is not None else None
+            e.absmax_f32 = a_f32.data_ptr() if a_f32 is not None else None
+            e.code2 = code2.data_ptr() if code2 is not None else None
+            e.absmax2 = absmax2.data_ptr() if absmax2 is not None else None
+            e.offset, e.blocksize2, e.ldw = off, bs2, 0
+        else:
+            assert W.dim() == 2 and W.stride(1) == 1 and W.dtype == dtype and W.shape[1] == K
+            e.ldw = W.stride(0)
+        e.y = y.data_ptr()
+        t = g.get("lora_t")
+        if t is not None:
+            B = g["lora_b"]
+            assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and B.stride(1) == 1
+            assert B.dtype in (torch.float32, dtype)
+            assert t.shape[0] >= M and (M == 1 or ldt in (0, t.stride(0)))
+            ldt = t.stride(0) if M > 1 else t.shape[1]
+            e.lora_t, e.lora_b, e.ld_lb = t.data_ptr(), B.data_ptr(), B.stride(0)
+            e.lora_scale, e.R, e.lora_b_f32 = float(g["lora_scale"]), int(g["R"]), int(B.dtype == torch.float32)
+            keep += [t, B]
+        bias = g.get("bias")
+        e.bias = bias.data_ptr() if bias is not None else None
+        e.N, e.y_f32 = N, int(y_f32)
+    _lib.call("uamd_gemv_rows", x, _lib.ptr(x), x.stride(0) if M > 1 else K, M, K, arr, len(groups),
+              int(ldy), int(ldt), int(bool(nf4)), int(blocksize), _lib.dtype_code(dtype), _lib.stream_of(x))
+    return outs
+
+
+def linear_group_rows(x2d, projs, out=None, y_f32=False, t_buf=None):
+    """`linear_group` for M = 1 .. 16 token rows x2d [M, K] that share one pass over the weights (uamd_gemv_rows): at most two
+    launches per four projections (the stacked A rows of all members -> t fp32 [M, sum R], then the weights). `out`: an
+    [M, sum N_i] buffer (rows may be strided) the outputs are written into side by side -- q|k|v land in the fused row with no
+    concatenation; `t_buf`: an fp32 [M, >= sum R] buffer to reuse under a hipGraph. Returns the [M, N_i] views. The value of a
+    row depends on that row and the weights alone (the kernel's row-independence contract)."""
+    assert x2d.dim() == 2 and 1 <= x2d.shape[0] <= MAX_ROWS
+    M, dtype = x2d.shape[0], x2d.dtype
+    nf4 = projs[0][1] is not None
+    assert all((p[1] is not None) == nf4 for p in projs), "a launch is all-NF4 or all-16-bit"
+    Ns = [int(p[1].shape[0]) if p[1] is not None else int(p[0].shape[0]) for p in projs]
+    if out is None:
+        out = torch.empty(M, sum(Ns), dtype=torch.float32 if y_f32 else dtype, device=x2d.device)
+    assert out.shape == (M, sum(Ns))
+    with_lora = [p for p in projs if p[2] is not None]
+    t_all = None
+    if with_lora:
+        A_rows = lora_a_rows([p[2] for p in with_lora], dtype)
+        Rt = A_rows.shape[0]
+        t_all = t_buf[:M, :Rt] if t_buf is not None else torch.empty(M, Rt, dtype=torch.float32, device=x2d.device)
+        gemv_rows(x2d, [dict(W=A_rows, N=Rt, y=t_all, y_f32=True)], nf4=False)
+    groups, col, r0 = [], 0, 0
+    for p, N in zip(projs, Ns):
+        W, qs, A, B, s = p[:5]
+        g = dict(W=W, N=N, qs=qs, y=out[:, col:col + N], y_f32=y_f32, bias=p[5] if len(p) > 5 else None)
+        if A is not None:
+            R = A.shape[0]
+            g.update(lora_t=t_all[:, r0:r0 + R], lora_b=B.detach(), lora_scale=s, R=R)
+            r0 += R
+        groups.append(g)
+        col += N
+    blocksize = int(projs[0][1].blocksize) if nf4 else 64
+    ys = []
+    for i in range(0, len(groups), MAX_GROUPS):
+        ys += gemv_rows(x2d, groups[i:i + MAX_GROUPS], nf4=nf4, blocksize=blocksize)
     return ys
 
 

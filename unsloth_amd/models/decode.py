@@ -15,7 +15,12 @@ MI355X design: one `DecodeEngine` per (model, max_seq_len, batch):
     once as a hipGraph and replayed per token. (Rounds 2-3: 14 launches per layer, ~450 kernels
     of ~9 us for ~0.6 ms of HBM traffic; still the batch > 1 path and `UNSLOTH_AMD_DECODE_FUSED=0`.);
   * prefill runs the training-path kernels (flash attention over the prompt) and writes K (post-RoPE) / V into the cache.
-Batch > 1 decodes through the fused NF4 GEMM instead of the GEMV (as the reference does, utils.py:1095-1097).
+Batches of 2 .. 16 sequences run the 14-launch step with every linear on uamd_gemv_rows -- ONE pass over the weights for all
+token rows, LoRA term and bias inside the launch, q|k|v written straight into the fused row -- captured and replayed as a
+hipGraph like the single-sequence step (`BATCH_ROWS`); a row's logits do not depend on its companions. Larger batches decode
+through the fused NF4 GEMM (as the reference does, utils.py:1095-1097), eager. Prompts of different lengths arrive LEFT-padded
+with their attention_mask: prefill treats the padding as documents, counts RoPE positions from each row's first real token
+and stores row b's keys at cache positions [0, L_b); the step works per row from kv_len[b] and needs nothing else.
 """
 import math
 import os
@@ -42,6 +47,26 @@ def _base(model):
 # launch and handed over through a device workspace, RoPE / append / combine ride in the attention launch and SwiGLU in the
 # gate|up epilogue.)
 FUSED_STEP = True
+# Batches of 2 .. 16 sequences: every linear of the token step through uamd_gemv_rows (one pass over the weights for all rows,
+# LoRA term and bias inside the launch) and the step captured as a hipGraph, against the 128 x 128-tile NF4 GEMM + separate
+# LoRA / bias launches, eager (False: the route of every larger batch). Read when an engine is built; only tests and
+# tools/decode_batch_bench.py flip it (profiles/decode_batch_bench.jsonl is the A/B).
+BATCH_ROWS = True
+
+
+def left_pad_lengths(attention_mask):
+    """Lengths [B] (int64, on the mask's device) of a LEFT-padded key mask [B, T] -- every row `[zeros | ones]` with at least
+    one real token (a row of all ones included) -- or None for anything else: right padding, holes, an empty row. One host
+    sync."""
+    m = attention_mask != 0
+    if m.dim() != 2 or m.shape[1] == 0:
+        return None
+    n = m.sum(1)
+    T = m.shape[1]
+    tail = torch.arange(T, device=m.device)[None, :] >= (T - n)[:, None]
+    if not bool(((n > 0).all()) & ((m == tail).all())):
+        return None
+    return n
 
 
 class DecodeEngine:
@@ -66,7 +91,8 @@ class DecodeEngine:
             raise NotImplementedError("decode path: SwiGLU MLP only")
         self.window = int(getattr(cfg, "sliding_window", None) or 0)
         self.scale = 1.0 / math.sqrt(self.D)
-        self.use_graph = bool(use_graph) and batch == 1
+        self.rows = bool(BATCH_ROWS) and 2 <= batch <= _dk.MAX_ROWS      # the batched step on uamd_gemv_rows
+        self.use_graph = bool(use_graph) and (batch == 1 or self.rows)
         L = len(self.core.layers)
         kw = dict(dtype=self.dtype, device=self.dev)
         self.k_cache = [torch.zeros(batch, self.Hk, self.S, self.D, **kw) for _ in range(L)]
@@ -119,10 +145,28 @@ class DecodeEngine:
 
     # ---- prefill: prompt through the training-path kernels, K / V into the cache -----------------------------------------
     @torch.no_grad()
-    def prefill(self, input_ids):
+    def prefill(self, input_ids, attention_mask=None, repeat=1):
+        """The prompt(s) [B, T] through the training-path kernels; K / V into the cache, next-token logits out.
+        `attention_mask`: a LEFT-padded key mask (`left_pad_lengths`); row b's L_b real tokens get RoPE positions 0 .. L_b - 1
+        and cache positions [0, L_b), pad positions never enter the cache, kv_len[b] = L_b. `repeat` = n: the engine's batch is
+        B * n and every prompt's cache rows and logits are replicated to n adjacent rows (num_return_sequences)."""
         from . import llama as _ll
+        from ..kernels import attention as _flash
         B, T = input_ids.shape
-        assert B == self.B and T <= self.S
+        assert B * repeat == self.B and T <= self.S
+        lens = pad = seq_info = rope_pos = None
+        if attention_mask is not None and not bool((attention_mask != 0).all()):
+            attention_mask = attention_mask.to(self.dev)
+            lens = left_pad_lengths(attention_mask)
+            if lens is None or attention_mask.shape != (B, T):
+                raise ValueError("DecodeEngine.prefill: the attention_mask must be left-padded ([zeros | ones] rows, none empty)")
+            pad = (T - lens)
+            seq_info = (_flash.padding_mask_documents(attention_mask), None, None)
+            ar = torch.arange(T, device=self.dev)
+            rope_pos = (ar[None, :] - pad[:, None]).clamp_min(0).to(torch.int32).reshape(-1)
+            src = (ar[None, :] + pad[:, None]).clamp_max(T - 1)                         # cache position j <- column pad_b + j
+            src = src[:, None, :, None].expand(B, self.Hk, T, self.D)
+            live = (ar[None, :] < lens[:, None])[:, None, :, None]
         # parameters were updated since the token step was captured (an optimizer stepped, a training forward ran): the
         # graph holds pointers to activation-dtype copies of the LoRA factors that are stale now -- capture again
         from ..kernels.utils import _CAST_EPOCH
@@ -158,10 +202,16 @@ class DecodeEngine:
             Q = Q.view(B, T, self.Hq, self.D).transpose(1, 2)
             K = K.view(B, T, self.Hk, self.D).transpose(1, 2)
             V = V.view(B, T, self.Hk, self.D).transpose(1, 2)
-            Q, K = fast_rope_embedding(Q, K, cos, sin, None)
-            self.k_cache[li][:, :, :T].copy_(K)
-            self.v_cache[li][:, :, :T].copy_(V)
-            A = _ll._attention(Q, K, V, None, None, self.window or None)
+            Q, K = fast_rope_embedding(Q, K, cos, sin, rope_pos)
+            Kc, Vc = K, V
+            if lens is not None:
+                zero = torch.zeros((), dtype=self.dtype, device=self.dev)
+                Kc, Vc = torch.where(live, K.gather(2, src), zero), torch.where(live, V.gather(2, src), zero)
+            if repeat > 1:
+                Kc, Vc = Kc.repeat_interleave(repeat, 0), Vc.repeat_interleave(repeat, 0)
+            self.k_cache[li][:, :, :T].copy_(Kc)
+            self.v_cache[li][:, :, :T].copy_(Vc)
+            A = _ll._attention(Q, K, V, seq_info, None, self.window or None)
             o = attn.apply_o(attn, A)
             w2, e2 = self._params[li]["ln2"]
             resid, x, _ = add_rms_fwd(o, resid, w2, e2)
@@ -169,8 +219,12 @@ class DecodeEngine:
             delta = layer.mlp(x)
         wn, en = core.norm.weight, _eps(core.norm)
         _, xn, _ = add_rms_fwd(delta[:, -1:], resid[:, -1:], wn, en)
-        self.kv_len.fill_(T)
-        self.logits = self._lm_head(xn.view(B, -1))
+        if lens is None:
+            self.kv_len.fill_(T)
+        else:
+            self.kv_len.copy_(lens.repeat_interleave(repeat, 0))
+        xn = xn.view(B, -1)
+        self.logits = self._lm_head(xn if repeat == 1 else xn.repeat_interleave(repeat, 0))
         return self.logits
 
     def _greedy(self):
@@ -212,6 +266,9 @@ class DecodeEngine:
         if self.B == 1 and W.dtype == x.dtype and W.shape[1] <= 16384:
             (y,) = _dk.gemv(x.reshape(-1), [dict(W=W, N=W.shape[0], y_f32=True)], nf4=False)
             return y.view(1, -1)
+        if self.rows and W.dtype == x.dtype and W.shape[1] <= 16384:
+            (y,) = _dk.gemv_rows(x, [dict(W=W, N=W.shape[0], y_f32=True)], nf4=False)
+            return y
         return (x @ W.t().to(x.dtype)).float()
 
     # ---- one token ----------------------------------------------------------------------------------------------------------
@@ -219,6 +276,8 @@ class DecodeEngine:
         """x [B, K] -> list of [B, N_i]."""
         if self.B == 1:
             return [y.view(1, -1) for y in _dk.linear_group(x, projs)]
+        if self.rows:
+            return _dk.linear_group_rows(x, projs)
         outs = []
         for p in projs:                           # batch > 1: the fused small-M NF4 GEMM (utils.py:1095-1097 does dequant + matmul)
             y = matmul_lora(x, p[0], p[1], p[2], p[3], p[4])
@@ -300,6 +359,9 @@ class DecodeEngine:
             if B == 1:
                 qkv = torch.empty(1, (self.Hq + 2 * self.Hk) * self.D, dtype=self.dtype, device=self.dev)
                 _dk.linear_group(x, P["qkv"], out=qkv.view(-1))
+            elif self.rows:                       # q | k | v straight into the fused row
+                qkv = torch.empty(B, (self.Hq + 2 * self.Hk) * self.D, dtype=self.dtype, device=self.dev)
+                _dk.linear_group_rows(x, P["qkv"], out=qkv)
             else:
                 qkv = torch.cat(self._linear(x, P["qkv"]), dim=1)
             _dk.rope_kv_append(qkv, self.cos, self.sin, self.kv_len, self.k_cache[li], self.v_cache[li],
@@ -354,14 +416,23 @@ class DecodeEngine:
 
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens=32, eos_token_id=None, do_sample=False, temperature=1.0, top_k=0,
-                 generator=None, pad_token_id=None, top_p=1.0, min_p=0.0):
+                 generator=None, pad_token_id=None, top_p=1.0, min_p=0.0, attention_mask=None, num_return_sequences=1):
         """Greedy (default) or temperature / top-k / top-p / min-p sampling. Returns [B, T + new] token ids. Rows that have
         produced an end-of-sequence token keep emitting `pad_token_id` (default: the first eos id), like HF's generate.
+        `attention_mask`: left-padded prompts (see `prefill`); the padded prompt is returned in front of the new tokens.
+        `num_return_sequences` = n > 1 (sampling only): the engine's batch is B * n, every prompt is prefilled once and decoded
+        as n adjacent rows that draw differently (the draw is keyed on the row) -- the tokens of the same call on
+        input_ids.repeat_interleave(n, 0).
         Sampling happens on the device (uamd_sample_f32): one 64-bit seed per call is drawn from `generator` (the default
         generator of its device when None) without a sync, the first token is drawn from the prefill logits at draw 0 and every
         later one inside the token step, so equally seeded generators give equal tokens."""
         input_ids = input_ids.to(self.dev)
-        logits = self.prefill(input_ids)
+        n = int(num_return_sequences or 1)
+        if n > 1 and not do_sample:
+            raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True")
+        logits = self.prefill(input_ids, attention_mask, repeat=n)
+        if n > 1:
+            input_ids = input_ids.repeat_interleave(n, 0)
         if do_sample:
             gdev = generator.device if generator is not None else self.dev
             seed = torch.randint(-(1 << 63), (1 << 63) - 1, (1,), dtype=torch.int64, device=gdev, generator=generator)
@@ -434,64 +505,121 @@ def _eps(norm):
 # silently ignored
 _ENGINE_KWARGS = {"max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "do_sample", "temperature", "top_k", "top_p",
                   "min_p", "attention_mask", "use_cache", "generator", "max_seq_len", "return_dict_in_generate", "output_scores",
-                  "generation_config", "tokenizer"}
+                  "generation_config", "tokenizer", "num_return_sequences"}
 
 
-def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_len=None, **kwargs):
-    """llama.py:2167-2259 counterpart: `model.generate(...)` after `FastLanguageModel.for_inference(model)`.
-    The reference forwards every keyword to HF's generate; the engine covers greedy / temperature / top-k / top-p / min-p
-    decoding of unpadded batches. Calls outside that (repetition_penalty, beams, streamers, logits processors, a padded
-    attention_mask, ...) are handed to HF's own generate (`model._old_generate`) -- or raise when it is unavailable."""
-    input_ids = kwargs.pop("inputs", input_ids)
+# generation_config fields the engine reads (below the explicit keywords, above the model's own generation config)
+_CONFIG_FIELDS = ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "do_sample", "temperature", "top_k", "top_p",
+                  "min_p", "num_return_sequences")
+_NEUTRAL = {"repetition_penalty": (None, 1.0), "num_beams": (None, 1), "streamer": (None,), "num_return_sequences": (None, 1),
+            "min_new_tokens": (None, 0), "return_dict_in_generate": (None, False), "output_scores": (None, False),
+            "generation_config": (None,)}
+
+
+def _config_fields(gc):
+    """(fields the engine reads, names of the other fields that are set to something else than the class default) of a
+    `generation_config=` object."""
+    def public(o):
+        d = o.to_dict() if hasattr(o, "to_dict") else dict(vars(o))
+        return {k: v for k, v in d.items() if not k.startswith("_") and k != "transformers_version"}
+    have = public(gc)
+    try:
+        base = public(type(gc)())
+    except Exception:
+        base = {}
+    other = [k for k, v in have.items() if k not in _CONFIG_FIELDS and k not in ("use_cache",) and v != base.get(k, None)
+             and not (k in _NEUTRAL and v in _NEUTRAL[k])]
+    return {k: have[k] for k in _CONFIG_FIELDS if have.get(k, None) is not None}, other
+
+
+def route_generate(model, input_ids, max_new_tokens, kwargs):
+    """Where a `generate` call goes: ("old", reasons) -- HF's own generate -- or ("engine", settings): the keyword arguments of
+    DecodeEngine.generate plus `batch` (rows the engine decodes: B x num_return_sequences) and `need` (padded prompt + new
+    tokens). A left-padded attention_mask is the engine's when its masked positions hold the pad token (or no pad token is
+    known). Explicit keywords win over `generation_config=`'s fields, those over the model's generation config. No GPU work:
+    one host sync when an attention_mask with zeros has to be classified."""
     attention_mask = kwargs.get("attention_mask", None)
-    padded = attention_mask is not None and not bool(torch.all(attention_mask != 0))
-    neutral = {"repetition_penalty": (None, 1.0), "num_beams": (None, 1), "streamer": (None,),
-               "num_return_sequences": (None, 1), "min_new_tokens": (None, 0), "return_dict_in_generate": (None, False),
-               "output_scores": (None, False), "generation_config": (None,)}
-    unsupported = [k for k, v in kwargs.items()
-                   if (k not in _ENGINE_KWARGS and not (k in neutral and v in neutral[k]))
-                   or (k in ("return_dict_in_generate", "output_scores", "generation_config") and v)]
-    if padded or unsupported:
-        old = getattr(model, "_old_generate", None)
-        if old is None:
-            raise NotImplementedError(f"unsloth_fast_generate: unsupported arguments {unsupported or ['padded attention_mask']}")
-        return old(input_ids, max_new_tokens=max_new_tokens, **kwargs) if max_new_tokens is not None else old(input_ids, **kwargs)
+    lens = None
+    reasons = []
+    call_cfg, cfg_other = {}, []
+    if kwargs.get("generation_config", None) is not None:
+        call_cfg, cfg_other = _config_fields(kwargs["generation_config"])
     gen_cfg = getattr(model, "generation_config", None)
     if gen_cfg is None:
         gen_cfg = getattr(_base(model), "generation_config", None)
+    eos, pad = kwargs.get("eos_token_id", None), kwargs.get("pad_token_id", None)
+    for cfg in (call_cfg, gen_cfg):
+        if eos is None and cfg is not None:
+            eos = cfg.get("eos_token_id") if isinstance(cfg, dict) else getattr(cfg, "eos_token_id", None)
+        if pad is None and cfg is not None:
+            pad = cfg.get("pad_token_id") if isinstance(cfg, dict) else getattr(cfg, "pad_token_id", None)
+    if attention_mask is not None and not bool(torch.all(attention_mask != 0)):
+        # The engine takes PADDING: rows `[zeros | ones]` whose masked positions hold the pad token, as a tokenizer with
+        # padding_side="left" writes them (no pad token known anywhere: the mask's word is taken). A mask that hides other
+        # tokens is not padding; such calls stay with HF's generate, as every mask with a zero did before the engine had a
+        # padded prefill.
+        lens = left_pad_lengths(attention_mask)
+        if lens is None or tuple(attention_mask.shape) != tuple(input_ids.shape):
+            reasons.append("attention_mask that is not left-padded")
+        elif isinstance(pad, int) and not bool((input_ids[(attention_mask == 0).to(input_ids.device)] == pad).all()):
+            reasons.append("attention_mask that hides tokens other than the pad token")
+            lens = None
+    reasons += [k for k, v in kwargs.items()
+                if (k not in _ENGINE_KWARGS and not (k in _NEUTRAL and v in _NEUTRAL[k]))
+                or (k in ("return_dict_in_generate", "output_scores") and v)]
+    reasons += [f"generation_config.{k}" for k in cfg_other]
+    if reasons:
+        return "old", reasons
+
+    # Sampling defaults come from the model's generation_config like in HF's generate (a checkpoint that ships
+    # do_sample=True / temperature / top_k / top_p / min_p -- Llama-3-Instruct's does -- samples without the caller saying so);
+    # a generation_config= of the call stands above it, explicit keywords win.
+    def gen_default(name, fallback):
+        if name in kwargs and kwargs[name] is not None:
+            return kwargs[name]
+        if name in call_cfg:
+            return call_cfg[name]
+        v = getattr(gen_cfg, name, None) if (gen_cfg is not None and not call_cfg) else None
+        return fallback if v is None else v
     if max_new_tokens is None:
         max_length = kwargs.get("max_length", None)
         if max_length is not None:
             max_new_tokens = max(int(max_length) - input_ids.shape[1], 0)
         else:
-            max_new_tokens = getattr(gen_cfg, "max_new_tokens", None) or 32
-    eos = kwargs.get("eos_token_id", None)
-    if eos is None and gen_cfg is not None:
-        eos = getattr(gen_cfg, "eos_token_id", None)
-    pad = kwargs.get("pad_token_id", None)
-    if pad is None and gen_cfg is not None:
-        pad = getattr(gen_cfg, "pad_token_id", None)
-    # Sampling defaults come from the model's generation_config like in HF's generate (a checkpoint that ships
-    # do_sample=True / temperature / top_k / top_p / min_p -- Llama-3-Instruct's does -- samples without the caller saying so);
-    # explicit keywords win.
-    def gen_default(name, fallback):
-        if name in kwargs and kwargs[name] is not None:
-            return kwargs[name]
-        v = getattr(gen_cfg, name, None) if gen_cfg is not None else None
-        return fallback if v is None else v
+            max_new_tokens = call_cfg.get("max_new_tokens") or getattr(gen_cfg, "max_new_tokens", None) or 32
     do_sample = bool(gen_default("do_sample", False))
-    temperature = float(gen_default("temperature", 1.0))
-    top_k = int(gen_default("top_k", 0) or 0) if do_sample else 0
-    top_p = float(gen_default("top_p", 1.0)) if do_sample else 1.0
-    min_p = float(gen_default("min_p", 0.0) or 0.0) if do_sample else 0.0
-    need = input_ids.shape[1] + max_new_tokens
+    n = int(kwargs.get("num_return_sequences", None) or call_cfg.get("num_return_sequences", None) or 1)
+    if n > 1 and not do_sample:
+        raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True")
+    return "engine", dict(max_new_tokens=int(max_new_tokens), eos_token_id=eos, pad_token_id=pad, do_sample=do_sample,
+                          temperature=float(gen_default("temperature", 1.0)),
+                          top_k=int(gen_default("top_k", 0) or 0) if do_sample else 0,
+                          top_p=float(gen_default("top_p", 1.0)) if do_sample else 1.0,
+                          min_p=float(gen_default("min_p", 0.0) or 0.0) if do_sample else 0.0,
+                          generator=kwargs.get("generator", None), attention_mask=attention_mask if lens is not None else None,
+                          num_return_sequences=n, batch=input_ids.shape[0] * n, need=input_ids.shape[1] + int(max_new_tokens))
+
+
+def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_len=None, **kwargs):
+    """llama.py:2167-2259 counterpart: `model.generate(...)` after `FastLanguageModel.for_inference(model)`.
+    The reference forwards every keyword to HF's generate; the engine covers greedy / temperature / top-k / top-p / min-p
+    decoding of unpadded and LEFT-padded batches (pad tokens under the mask's zeros), `num_return_sequences` when sampling and a `generation_config=` object
+    whose other fields are at their defaults. Calls outside that (repetition_penalty, beams, streamers, logits processors, a
+    right-padded or holey attention_mask, ...) are handed to HF's own generate (`model._old_generate`) -- or raise when it is
+    unavailable."""
+    input_ids = kwargs.pop("inputs", input_ids)
+    where, what = route_generate(model, input_ids, max_new_tokens, kwargs)
+    if where == "old":
+        old = getattr(model, "_old_generate", None)
+        if old is None:
+            raise NotImplementedError(f"unsloth_fast_generate: unsupported arguments {what}")
+        return old(input_ids, max_new_tokens=max_new_tokens, **kwargs) if max_new_tokens is not None else old(input_ids, **kwargs)
+    batch, need = what.pop("batch"), what.pop("need")
     eng = getattr(model, "_uamd_decode_engine", None)
-    if eng is None or eng.B != input_ids.shape[0] or eng.S < need:
-        eng = DecodeEngine(model, max_seq_len=max(need, max_seq_len or 0), batch=input_ids.shape[0])
+    if eng is None or eng.B != batch or eng.S < need:
+        eng = DecodeEngine(model, max_seq_len=max(need, max_seq_len or 0), batch=batch)
         model._uamd_decode_engine = eng
-    return eng.generate(input_ids, max_new_tokens=max_new_tokens, eos_token_id=eos,
-                        do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p,
-                        generator=kwargs.get("generator", None), pad_token_id=pad)
+    return eng.generate(input_ids, **what)
 
 
 # ---- the reference's function names, for code written against unsloth/models/llama.py ----------------------------------------
