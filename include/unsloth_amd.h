@@ -520,7 +520,37 @@ int uamd_attn_decode(const void* q, int64_t q_sb, const void* k_cache, const voi
                      int64_t cache_sh, const int* kv_len, int len_add, float* partials, void* out, int64_t out_sb,
                      int B, int Hq, int Hk, int D, int nsplit, int split_keys, int window, float scale, int dtype,
                      void* stream);
-/* The three launches above (RoPE + append, split attention, combine) as ONE: every workgroup (split, kv head, batch) rotates
+/* ---- FP8 KV cache (opt-in: DecodeEngine(kv_cache_dtype="fp8")) -- THE definition of the stored format --------------------
+ * A cache row is one (sequence, KV head, position) vector of D elements, D = 64 or 128. It is stored as D bytes of OCP e4m3fn
+ * codes in `codes` [B, Hk, s_max, D] (uint8; strides cache_sb, cache_sh, D, 1) and ONE fp32 scale in `scales` [B, Hk, s_max]
+ * (strides cache_sb / D, cache_sh / D, 1: both strides are multiples of D). K and V have their own codes and scales.
+ * The quantiser of a row x, already rounded to the activation type and taken as fp32:
+ *     amax  = max_j |x_j|
+ *     scale = amax / 448 when amax > 0 (IEEE fp32 division), 1 when amax == 0
+ *     code_j = e4m3fn_rne(clamp(x_j / scale, -448, 448))   (IEEE fp32 division, round to nearest even, the sign of zero kept)
+ * -- in torch: (x.float() / scale).clamp(-448, 448).to(torch.float8_e4m3fn). A row with a non-finite element stores scale = NaN
+ * and unspecified codes: every score against that key is NaN. The dequantised value is float(code_j) * scale.
+ *
+ * uamd_kv_store_fp8: rows (b, h, t), t < T, of a strided 16-bit [B, Hk, T, D] tensor (element strides src_sb, src_sh, src_st,
+ * 1, multiples of 8; the transpose(1, 2) view a prefill holds, no contiguous copy) -> cache positions [0, T), T <= s_max. */
+int uamd_kv_store_fp8(const void* src, int64_t src_sb, int64_t src_sh, int64_t src_st, void* codes, float* scales,
+                      int64_t cache_sb, int64_t cache_sh, int B, int Hk, int T, int D, int s_max, int dtype, void* stream);
+/* uamd_rope_kv_append with an FP8 cache: q and k of the fused row are rotated in place exactly as there (same rounding points,
+ * same kv_len / rope_pos / s_max behaviour); k and v are stored at position kv_len[b] as codes + scale. What is quantised is
+ * what uamd_rope_kv_append would have written: the rotated k rounded to the activation type, the raw v -- through the same
+ * device function as uamd_kv_store_fp8, so a key appended by a step and the same key stored by prefill are the same bytes. */
+int uamd_rope_kv_append_fp8(void* qkv, int64_t ld_qkv, const void* cos_t, const void* sin_t, int64_t ld_cs, const int* kv_len,
+                            const int* rope_pos, void* k_codes, void* v_codes, float* k_scales, float* v_scales,
+                            int64_t cache_sb, int64_t cache_sh, int B, int Hq, int Hk, int D, int s_max, int dtype,
+                            void* stream);
+/* uamd_attn_decode over an FP8 cache: same key range, len_add, window, partials [B, Hq, nsplit, D + 2], split_keys rule and
+ * combine launch. score = (sum_j q_j code_j) * k_scale (q pre-multiplied by scale * log2 e), the key's softmax weight is
+ * multiplied by v_scale once per key; everything in fp32, one rounding at the output store. q and out are 16-bit (`dtype`). */
+int uamd_attn_decode_fp8(const void* q, int64_t q_sb, const void* k_codes, const void* v_codes, const float* k_scales,
+                         const float* v_scales, int64_t cache_sb, int64_t cache_sh, const int* kv_len, int len_add,
+                         float* partials, void* out, int64_t out_sb, int B, int Hq, int Hk, int D, int nsplit, int split_keys,
+                         int window, float scale, int dtype, void* stream);
+/* The three launches of the 16-bit cache (uamd_rope_kv_append, uamd_attn_decode and its combine) as ONE: every workgroup (split, kv head, batch) rotates
  * the G query heads it needs from the raw q|k|v row (qkv is NOT modified); the workgroup whose split owns position kv_len[b]
  * rotates the new k, appends k and v to the cache and uses them from LDS. Keys [max(0, len - window), len), len = kv_len[b] + 1.
  * D and split_keys as for uamd_attn_decode.

@@ -1168,6 +1168,265 @@ __global__ void __launch_bounds__(DD) attn_decode_combine_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// FP8 KV cache (opt-in; the format is defined once, in include/unsloth_amd.h): a cache row -- one (sequence, KV head, position)
+// vector of DD values -- is DD bytes of OCP e4m3fn codes plus ONE fp32 scale, amax / 448. Half the bytes of a 16-bit row (plus
+// 4), which is what a decode step of a batch at a long context reads. The lane geometry is DecGeo's throughout: DD / 8 lanes
+// per row, 8 columns each -- a 16-byte load of the 16-bit source, an 8-byte load or store of the codes.
+//
+// THE quantiser of a row, shared by the two writers (kv_store_fp8_kernel: prefill; rope_append_fp8_kernel: the token step), so a
+// key appended by a step and the same key stored by prefill are the same bytes. x: the lane's 8 columns, already rounded to the
+// activation type, as fp32; every lane of the row's group gets the row's scale back and returns its 8 codes. Both divisions are
+// IEEE (no fast-math in this build), the conversion is v_cvt_pk_fp8_f32: round to nearest even, the sign of zero kept. A row
+// with a non-finite element gets scale = NaN (its codes are unspecified): every score against that key is NaN.
+template <int LPK>
+__device__ __forceinline__ float lanes_max(float v) {
+    static_assert(LPK == 8 || LPK == 16, "half a DPP row or a whole one");
+#define UAMD_DPP_MAX(v, CTRL) fmaxf((v), __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, (v)), (CTRL), 0xf, 0xf, true)))
+    v = UAMD_DPP_MAX(v, 0xb1);      // quad_perm [1,0,3,2]
+    v = UAMD_DPP_MAX(v, 0x4e);      // quad_perm [2,3,0,1]
+    v = UAMD_DPP_MAX(v, 0x141);     // row_half_mirror
+    if constexpr (LPK == 16) v = UAMD_DPP_MAX(v, 0x140);     // row_mirror
+#undef UAMD_DPP_MAX
+    return v;
+}
+constexpr float FP8_MAX = 448.f;                     // largest finite e4m3fn value
+template <int LPK>
+__device__ __forceinline__ uint2 quant_row_fp8(const float (&x)[8], float& scale) {
+    float am = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float a = fabsf(x[j]);
+        am = a < INFINITY ? fmaxf(am, a) : INFINITY;       // NaN or inf: the row's amax becomes inf (fmaxf would drop a NaN)
+    }
+    am = lanes_max<LPK>(am);
+    scale = am == INFINITY ? __builtin_nanf("") : (am > 0.f ? am / FP8_MAX : 1.f);
+    int lo = 0, hi = 0;
+    float y[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) y[j] = fminf(fmaxf(x[j] / scale, -FP8_MAX), FP8_MAX);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
+    return make_uint2((uint32_t)lo, (uint32_t)hi);
+}
+// Prefill's writer: rows (b, h, t), t < T, of a strided 16-bit [B, Hk, T, DD] tensor (unit stride along DD: the transpose(1, 2)
+// view of the projection output, no contiguous copy) -> positions [0, T) of the code and scale caches. A wave-load covers KPW
+// rows (one lane group each), a block KPB; rows past the end are loaded from the last row and not stored.
+template <typename T, int DD>
+__global__ void __launch_bounds__(256) kv_store_fp8_kernel(const T* __restrict__ src, int64_t s_sb, int64_t s_sh, int64_t s_st,
+                                                           uint8_t* __restrict__ codes, float* __restrict__ scales,
+                                                           int64_t c_sb, int64_t c_sh, int Hk, int Tn, int64_t rows) {
+    constexpr int LPK = DecGeo<DD>::LPK, KPW = DecGeo<DD>::KPW, KPB = DecGeo<DD>::KPB;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lc = lane % LPK;
+    const int64_t row = (int64_t)blockIdx.x * KPB + wave * KPW + lane / LPK;
+    const bool valid = row < rows;
+    const int64_t r = valid ? row : rows - 1;
+    const int t = (int)(r % Tn);
+    const int h = (int)((r / Tn) % Hk);
+    const int64_t b = r / ((int64_t)Tn * Hk);
+    const Vec16<T> v = ld16(src + b * s_sb + h * s_sh + t * s_st + lc * 8);
+    float x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = to_f32(v.e[j]);
+    float scale;
+    const uint2 c = quant_row_fp8<LPK>(x, scale);
+    if (valid) {
+        *reinterpret_cast<uint2*>(codes + b * c_sb + h * c_sh + (int64_t)t * DD + lc * 8) = c;
+        if (lc == 0) scales[(b * c_sb + h * c_sh) / DD + t] = scale;
+    }
+}
+
+// The token step's writer: rope_append_kernel with an FP8 cache. q and k are rotated in place in the fused row with rope_pair's
+// rounding points; what is quantised is what that kernel would have stored -- the rotated k rounded to T, the raw v. The row
+// goes through LDS once to change hands from rope_pair's layout (a lane owns columns j and j + DD / 2) to the quantiser's (8
+// adjacent columns); every lane group quantises the same row, group 0 stores.
+template <typename T, int DD>
+__global__ void __launch_bounds__(64) rope_append_fp8_kernel(T* __restrict__ qkv, int64_t ld_qkv, const T* __restrict__ cos_t,
+                                                             const T* __restrict__ sin_t, int64_t ld_cs,
+                                                             const int* __restrict__ kv_len, const int* __restrict__ rope_pos,
+                                                             uint8_t* __restrict__ kc, float* __restrict__ ks,
+                                                             uint8_t* __restrict__ vc, float* __restrict__ vs, int64_t c_sb,
+                                                             int64_t c_sh, int Hq, int Hk, int s_max) {
+    constexpr int LPK = DecGeo<DD>::LPK, half = DD / 2;
+    const int h = blockIdx.x, b = blockIdx.y;            // h: q heads, then k heads, then v heads of the fused row
+    const int lane = threadIdx.x;
+    const int len = kv_len[b];
+    const int pos = rope_pos ? rope_pos[b] : len;
+    T* v = qkv + (int64_t)b * ld_qkv + (int64_t)h * DD;
+    __shared__ __attribute__((aligned(16))) T row[DD];
+    if (h < Hq + Hk) {
+        for (int j = lane; j < half; j += 64) {
+            const float c = to_f32(cos_t[(int64_t)pos * ld_cs + j]), s = to_f32(sin_t[(int64_t)pos * ld_cs + j]);
+            T r1, r2;
+            rope_pair(to_f32(v[j]), to_f32(v[j + half]), c, s, r1, r2);
+            v[j] = r1;
+            v[j + half] = r2;
+            row[j] = r1;
+            row[j + half] = r2;
+        }
+        if (h < Hq) return;
+    } else {
+        for (int j = lane; j < DD; j += 64) row[j] = v[j];
+    }
+    __syncthreads();
+    if (len < 0 || len >= s_max) return;                 // a full cache: nothing is written (as rope_append_kernel)
+    const bool is_k = h < Hq + Hk;
+    const int kvh = is_k ? h - Hq : h - Hq - Hk;
+    const int lc = lane % LPK;
+    const Vec16<T> rv = ld16(row + lc * 8);
+    float x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = to_f32(rv.e[j]);
+    float scale;
+    const uint2 c = quant_row_fp8<LPK>(x, scale);
+    if (lane < LPK) {
+        const int64_t base = (int64_t)b * c_sb + (int64_t)kvh * c_sh;
+        *reinterpret_cast<uint2*>((is_k ? kc : vc) + base + (int64_t)len * DD + lc * 8) = c;
+        if (lc == 0) (is_k ? ks : vs)[base / DD + len] = scale;
+    }
+}
+
+// attn_decode_kernel over the FP8 cache: the same grid, key range, key -> (wave, lane group) assignment, block merge
+// (waves_to_lds, block_partial) and partial layout, so attn_decode_combine_kernel finishes it unchanged. What differs:
+//   * a lane's 8 columns of a key are 8 bytes, converted by v_cvt_pk_f32_fp8 (exact); the score is (sum_j q_j code_j) x k_scale,
+//     the key's softmax weight is multiplied by v_scale ONCE and then meets the 8 converted codes. All fp32; the only rounding
+//     to T is the combine's store;
+//   * a trip is 128 keys: the NI block-loads of codes and scales of K and of V (8 at DD = 128, 4 at DD = 64) are all issued
+//     before the first is used -- at the engine's 128-key splits a workgroup has its whole split in flight at once, where a
+//     loop of one block-load per trip pays one HBM round trip each (the note in front of attn_decode_fused_kernel);
+//   * the trip's keys are accumulated in chunks of CH = 2 block-loads, the way attn_decode_fused_kernel does it for a whole trip
+//     (one running-max rescale per head and chunk, not one per key), and products run two columns at a time (v_pk_fma_f32 --
+//     the conversion delivers pairs). With half the bytes per key it is the per-key arithmetic and the number of workgroups a CU
+//     holds that bound this kernel, not HBM alone: key-at-a-time (36 vector instructions per key and head, 112 VGPRs at G = 4)
+//     the step of 16 sequences at context 8192 took 9.76 ms, with CH = 2 (125 VGPRs: still four workgroups per CU) 9.32, with
+//     the whole trip as one chunk (170 VGPRs: fewer instructions, three workgroups) 10.97; the 16-bit cache: 11.0 - 11.2.
+typedef __attribute__((ext_vector_type(2))) float dec_f32x2;
+__device__ __forceinline__ void fp8x8_to_f32x2(uint2 c, dec_f32x2 (&f)[4]) {
+    f[0] = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.x, false);
+    f[1] = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.x, true);
+    f[2] = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.y, false);
+    f[3] = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.y, true);
+}
+template <typename T, int G, int DD>
+__global__ void __launch_bounds__(256) attn_decode_fp8_kernel(const T* __restrict__ q, int64_t q_sb, const uint8_t* __restrict__ kc,
+                                                              const uint8_t* __restrict__ vc, const float* __restrict__ ks,
+                                                              const float* __restrict__ vs, int64_t c_sb, int64_t c_sh,
+                                                              const int* __restrict__ kv_len, float* __restrict__ part,
+                                                              int Hq, int nsplit, int split_keys, int window,
+                                                              float scale_log2, int len_add) {
+    const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int LPK = DecGeo<DD>::LPK, KPW = DecGeo<DD>::KPW, KPB = DecGeo<DD>::KPB;
+    constexpr int NI = 128 / KPB, CH = 2;
+    const int grp = lane / LPK, lc = lane % LPK;
+    const int len = kv_len[b] + len_add;
+    const int first = (window > 0 && len > window) ? len - window : 0;
+    const int s0 = split * split_keys, s1 = min(s0 + split_keys, len);
+    __shared__ float red[4][G][2];
+    __shared__ float red_o[4][G][DD];
+    float m[G], l[G];
+    dec_f32x2 o2[G][4], qv[G][4];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        m[g] = -INFINITY; l[g] = 0.f;
+        const T* qp = q + (int64_t)b * q_sb + (int64_t)(kvh * G + g) * DD + lc * 8;
+        const Vec16<T> v = ld16(qp);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            qv[g][j] = dec_f32x2{to_f32(v.e[2 * j]) * scale_log2, to_f32(v.e[2 * j + 1]) * scale_log2};
+            o2[g][j] = dec_f32x2{0.f, 0.f};
+        }
+    }
+    const int64_t base = (int64_t)b * c_sb + (int64_t)kvh * c_sh;
+    const uint8_t* kb = kc + base;
+    const uint8_t* vb = vc + base;
+    const float* ksb = ks + base / DD;
+    const float* vsb = vs + base / DD;
+    const int safe = len > 0 ? len - 1 : 0;               // the row a masked lane loads (weight zero)
+    for (int k0 = max(s0, first & ~(KPB - 1)) + wave * KPW; k0 < s1; k0 += NI * KPB) {
+        uint2 kk[NI], vv[NI];
+        float ksc[NI], vsc[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int key = k0 + i * KPB + grp;
+            const int kl = (key < s1 && key >= first) ? key : safe;
+            kk[i] = *reinterpret_cast<const uint2*>(kb + (int64_t)kl * DD + lc * 8);
+            vv[i] = *reinterpret_cast<const uint2*>(vb + (int64_t)kl * DD + lc * 8);
+            ksc[i] = ksb[kl];
+            vsc[i] = vsb[kl];
+        }
+        // the trip's keys in chunks of CH block-loads: scores of the chunk, ONE running-max rescale per head and chunk, then the
+        // chunk's keys accumulate; a key's weight meets v_scale once
+#pragma unroll
+        for (int c0 = 0; c0 < NI; c0 += CH) {
+            if (k0 + c0 * KPB >= s1) break;               // (wave-uniform) the split ends inside the trip
+            float sc[CH][G];
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                const int i = c0 + c;
+                const int key = k0 + i * KPB + grp;
+                const bool valid = key < s1 && key >= first;
+                dec_f32x2 kf[4];
+                fp8x8_to_f32x2(kk[i], kf);
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    dec_f32x2 a2 = qv[g][0] * kf[0];
+#pragma unroll
+                    for (int j = 1; j < 4; ++j) a2 = __builtin_elementwise_fma(qv[g][j], kf[j], a2);
+                    const float a = lanes_sum<LPK>(a2[0] + a2[1]) * ksc[i];  // the key's lanes all get (q . codes) x k_scale
+                    sc[c][g] = valid ? a : -INFINITY;
+                }
+            }
+            float mr[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                float mc = sc[0][g];
+#pragma unroll
+                for (int c = 1; c < CH; ++c) mc = fmaxf(mc, sc[c][g]);
+                const float mn = fmaxf(m[g], mc);
+                mr[g] = mn == -INFINITY ? 0.f : mn;       // nothing but masked keys so far: exp2(-inf - 0) = 0, not exp2(nan)
+                const float alpha = __builtin_amdgcn_exp2f(m[g] - mr[g]);
+                m[g] = mn;
+                l[g] *= alpha;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o2[g][j] *= alpha;
+            }
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                const int i = c0 + c;
+                dec_f32x2 vf[4];
+                fp8x8_to_f32x2(vv[i], vf);
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const float pe = __builtin_amdgcn_exp2f(sc[c][g] - mr[g]);
+                    l[g] += pe;
+                    const float w = pe * vsc[i];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o2[g][j] = __builtin_elementwise_fma(dec_f32x2{w, w}, vf[j], o2[g][j]);
+                }
+            }
+        }
+    }
+    float o[G][8];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { o[g][2 * j] = o2[g][j][0]; o[g][2 * j + 1] = o2[g][j][1]; }
+    waves_to_lds<G, DD>(m, l, o, red, red_o, lane, wave);
+    __syncthreads();
+    for (int i = tid; i < G * DD; i += 256) {
+        const int g = i / DD, d = i - g * DD;
+        float mm, ll, oo;
+        block_partial<G, DD>(red, red_o, g, d, mm, ll, oo);
+        float* pp = part + part_index<DD>((int64_t)b * Hq + kvh * G + g, nsplit, split);
+        pp[d] = oo;
+        if (d == 0) { pp[DD] = mm; pp[DD + 1] = ll; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // RoPE + cache append + split-KV attention + combine as ONE launch (uamd_attn_decode_fused). The rotation (rope_pair), the
 // merge of a block's partials (softmax_merge, waves_to_lds, block_partial), the partial layout (part_index) and the combine
 // (combine_splits) are the functions rope_append_kernel -> attn_decode_kernel -> attn_decode_combine_kernel call, and the key
@@ -1660,6 +1919,87 @@ extern "C" int uamd_attn_decode(const void* q, int64_t q_sb, const void* k_cache
         constexpr int G = decltype(g)::value, DD = decltype(dd)::value;
         hipLaunchKernelGGL((attn_decode_kernel<T, G, DD>), grid, dim3(256), 0, st, (const T*)q, q_sb, (const T*)k_cache,
                            (const T*)v_cache, cache_sb, cache_sh, kv_len, partials, Hq, nsplit, split_keys, window, sl2, len_add);
+        if (int rc = uamd_launch_status()) return rc;
+        hipLaunchKernelGGL((attn_decode_combine_kernel<T, DD>), dim3(Hq, B), dim3(DD), 0, st, partials, (T*)out, out_sb, Hq, nsplit);
+        return uamd_launch_status();
+    });
+}
+
+// ---- the FP8 KV cache (format: include/unsloth_amd.h). Codes [B, Hk, s_max, D] uint8 with strides (cache_sb, cache_sh, D, 1),
+//      scales [B, Hk, s_max] fp32 with strides (cache_sb / D, cache_sh / D, 1).
+static int fp8_cache_check(int D, const void* codes, const void* scales, int64_t cache_sb, int64_t cache_sh) {
+    if (D != 64 && D != 128) return UAMD_ERR_ARG;
+    if (!codes || !scales || cache_sb <= 0 || cache_sh <= 0) return UAMD_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(codes) & 7) || (reinterpret_cast<uintptr_t>(scales) & 3) || cache_sb % D || cache_sh % D)
+        return UAMD_ERR_ALIGN;
+    return UAMD_OK;
+}
+
+extern "C" int uamd_kv_store_fp8(const void* src, int64_t src_sb, int64_t src_sh, int64_t src_st, void* codes, float* scales,
+                                 int64_t cache_sb, int64_t cache_sh, int B, int Hk, int Tn, int D, int s_max, int dtype,
+                                 void* stream) {
+    if (!src || B <= 0 || Hk <= 0 || Tn <= 0 || Tn > s_max) return UAMD_ERR_ARG;
+    if (int rc = fp8_cache_check(D, codes, scales, cache_sb, cache_sh)) return rc;
+    if (cache_sh < (int64_t)s_max * D || cache_sb < (int64_t)Hk * cache_sh) return UAMD_ERR_ARG;
+    if (!aligned16(src) || (src_sb & 7) || (src_sh & 7) || (src_st & 7)) return UAMD_ERR_ALIGN;
+    const int64_t rows = (int64_t)B * Hk * Tn;
+    const int kpb = D == 128 ? DecGeo<128>::KPB : DecGeo<64>::KPB;
+    const int64_t blocks = (rows + kpb - 1) / kpb;
+    if (blocks > 0x7fffffff) return UAMD_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    UAMD_DISPATCH_HALF(dtype, {
+        if (D == 128)
+            hipLaunchKernelGGL((kv_store_fp8_kernel<T, 128>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)src, src_sb, src_sh,
+                               src_st, (uint8_t*)codes, scales, cache_sb, cache_sh, Hk, Tn, rows);
+        else
+            hipLaunchKernelGGL((kv_store_fp8_kernel<T, 64>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)src, src_sb, src_sh,
+                               src_st, (uint8_t*)codes, scales, cache_sb, cache_sh, Hk, Tn, rows);
+    })
+    return uamd_launch_status();
+}
+
+extern "C" int uamd_rope_kv_append_fp8(void* qkv, int64_t ld_qkv, const void* cos_t, const void* sin_t, int64_t ld_cs,
+                                       const int* kv_len, const int* rope_pos, void* k_codes, void* v_codes, float* k_scales,
+                                       float* v_scales, int64_t cache_sb, int64_t cache_sh, int B, int Hq, int Hk, int D,
+                                       int s_max, int dtype, void* stream) {
+    if (!qkv || !cos_t || !sin_t || !kv_len || B <= 0 || Hq <= 0 || Hk <= 0 || s_max <= 0) return UAMD_ERR_ARG;
+    if (int rc = fp8_cache_check(D, k_codes, k_scales, cache_sb, cache_sh)) return rc;
+    if (int rc = fp8_cache_check(D, v_codes, v_scales, cache_sb, cache_sh)) return rc;
+    if (cache_sh < (int64_t)s_max * D || cache_sb < (int64_t)Hk * cache_sh) return UAMD_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(Hq + 2 * Hk), (unsigned)B);
+    UAMD_DISPATCH_HALF(dtype, {
+        if (D == 128)
+            hipLaunchKernelGGL((rope_append_fp8_kernel<T, 128>), grid, dim3(64), 0, st, (T*)qkv, ld_qkv, (const T*)cos_t,
+                               (const T*)sin_t, ld_cs, kv_len, rope_pos, (uint8_t*)k_codes, k_scales, (uint8_t*)v_codes, v_scales,
+                               cache_sb, cache_sh, Hq, Hk, s_max);
+        else
+            hipLaunchKernelGGL((rope_append_fp8_kernel<T, 64>), grid, dim3(64), 0, st, (T*)qkv, ld_qkv, (const T*)cos_t,
+                               (const T*)sin_t, ld_cs, kv_len, rope_pos, (uint8_t*)k_codes, k_scales, (uint8_t*)v_codes, v_scales,
+                               cache_sb, cache_sh, Hq, Hk, s_max);
+    })
+    return uamd_launch_status();
+}
+
+extern "C" int uamd_attn_decode_fp8(const void* q, int64_t q_sb, const void* k_codes, const void* v_codes, const float* k_scales,
+                                    const float* v_scales, int64_t cache_sb, int64_t cache_sh, const int* kv_len, int len_add,
+                                    float* partials, void* out, int64_t out_sb, int B, int Hq, int Hk, int D, int nsplit,
+                                    int split_keys, int window, float scale, int dtype, void* stream) {
+    if (!q || !kv_len || !partials || !out || B <= 0 || Hq <= 0 || Hk <= 0) return UAMD_ERR_ARG;
+    if (Hq % Hk || nsplit <= 0 || split_keys <= 0) return UAMD_ERR_ARG;
+    if (int rc = fp8_cache_check(D, k_codes, k_scales, cache_sb, cache_sh)) return rc;
+    if (int rc = fp8_cache_check(D, v_codes, v_scales, cache_sb, cache_sh)) return rc;
+    if (split_keys % (D == 64 ? DecGeo<64>::KPB : DecGeo<128>::KPB)) return UAMD_ERR_ARG;
+    if (!aligned16(q) || (q_sb & 7)) return UAMD_ERR_ALIGN;
+    const float sl2 = scale * 1.4426950408889634f;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)nsplit, (unsigned)Hk, (unsigned)B);
+    return attn_decode_dispatch(dtype, D, Hq / Hk, [&](auto t, auto g, auto dd) -> int {
+        using T = decltype(t);
+        constexpr int G = decltype(g)::value, DD = decltype(dd)::value;
+        hipLaunchKernelGGL((attn_decode_fp8_kernel<T, G, DD>), grid, dim3(256), 0, st, (const T*)q, q_sb, (const uint8_t*)k_codes,
+                           (const uint8_t*)v_codes, k_scales, v_scales, cache_sb, cache_sh, kv_len, partials, Hq, nsplit,
+                           split_keys, window, sl2, len_add);
         if (int rc = uamd_launch_status()) return rc;
         hipLaunchKernelGGL((attn_decode_combine_kernel<T, DD>), dim3(Hq, B), dim3(DD), 0, st, partials, (T*)out, out_sb, Hq, nsplit);
         return uamd_launch_status();

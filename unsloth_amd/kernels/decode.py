@@ -386,6 +386,57 @@ def attn_decode(q, k_cache, v_cache, kv_len, out, partials, split_keys, scale, l
     return out
 
 
+def _fp8_cache(codes, scales):
+    """Asserts the layout of one FP8 cache (include/unsloth_amd.h): codes uint8 [B, Hk, S_max, D] and scales fp32 [B, Hk, S_max];
+    the batch stride is free (every n-th row of a cache is a cache), the rest is dense. Returns (B, Hk, S_max, D)."""
+    B, Hk, S_max, D = codes.shape
+    assert D in HEAD_DIMS and codes.dtype == torch.uint8 and scales.dtype == torch.float32 and scales.device == codes.device
+    assert tuple(scales.shape) == (B, Hk, S_max)
+    assert codes.stride()[1:] == (S_max * D, D, 1) and scales.stride()[1:] == (S_max, 1)
+    assert codes.stride(0) == scales.stride(0) * D and codes.stride(0) >= Hk * S_max * D
+    return B, Hk, S_max, D
+
+
+def kv_store_fp8(x, codes, scales):
+    """x [B, Hk, T, D] (16-bit, unit stride along D, any other strides that are multiples of 8: the transposed view of prefill)
+    -> positions [0, T) of the FP8 cache `codes` (uint8 [B, Hk, S_max, D]) / `scales` (fp32 [B, Hk, S_max])
+    (uamd_kv_store_fp8; the format is defined in include/unsloth_amd.h)."""
+    _lib.require_gpu(x)
+    B, Hk, S_max, D = _fp8_cache(codes, scales)
+    assert x.dim() == 4 and tuple(x.shape[:2]) == (B, Hk) and x.shape[3] == D and x.stride(3) == 1 and x.shape[2] <= S_max
+    assert codes.device == x.device
+    _lib.call("uamd_kv_store_fp8", x, _lib.ptr(x), x.stride(0), x.stride(1), x.stride(2), _lib.ptr(codes), _lib.ptr(scales),
+              codes.stride(0), codes.stride(1), B, Hk, x.shape[2], D, S_max, _lib.dtype_code(x.dtype), _lib.stream_of(x))
+
+
+def rope_kv_append_fp8(qkv, cos, sin, kv_len, k_codes, v_codes, k_scales, v_scales, Hq, Hk, D, rope_pos=None):
+    """`rope_kv_append` with an FP8 cache: in place on qkv [B, (Hq + 2 Hk) D]; the rotated k and the raw v are stored at
+    kv_len[b] as codes + scale."""
+    B = qkv.shape[0]
+    assert _fp8_cache(k_codes, k_scales) == _fp8_cache(v_codes, v_scales) == (B, Hk, k_codes.shape[2], D)
+    assert k_codes.stride() == v_codes.stride()
+    assert qkv.stride(1) == 1 and kv_len.dtype == torch.int32
+    assert cos.stride(1) == 1 and sin.stride() == cos.stride() and cos.dtype == qkv.dtype
+    _lib.call("uamd_rope_kv_append_fp8", qkv, _lib.ptr(qkv), qkv.stride(0), _lib.ptr(cos), _lib.ptr(sin), cos.stride(0),
+              _lib.ptr(kv_len), _lib.ptr(rope_pos) if rope_pos is not None else None, _lib.ptr(k_codes), _lib.ptr(v_codes),
+              _lib.ptr(k_scales), _lib.ptr(v_scales), k_codes.stride(0), k_codes.stride(1), B, Hq, Hk, D, k_codes.shape[2],
+              _lib.dtype_code(qkv.dtype), _lib.stream_of(qkv))
+
+
+def attn_decode_fp8(q, k_codes, v_codes, k_scales, v_scales, kv_len, out, partials, split_keys, scale, len_add=1, window=0):
+    """`attn_decode` over an FP8 cache: q [B, Hq*D] and out [B, Hq*D] 16-bit, partials fp32 [B, Hq, nsplit, D + 2]."""
+    B, Hk, S_max, D = _fp8_cache(k_codes, k_scales)
+    assert _fp8_cache(v_codes, v_scales) == (B, Hk, S_max, D) and k_codes.stride() == v_codes.stride()
+    Hq = partials.shape[1]
+    nsplit = partials.shape[2]
+    assert nsplit * split_keys >= S_max and q.stride(1) == 1 and out.stride(1) == 1 and kv_len.dtype == torch.int32
+    _lib.call("uamd_attn_decode_fp8", q, _lib.ptr(q), q.stride(0), _lib.ptr(k_codes), _lib.ptr(v_codes), _lib.ptr(k_scales),
+              _lib.ptr(v_scales), k_codes.stride(0), k_codes.stride(1), _lib.ptr(kv_len), int(len_add), _lib.ptr(partials),
+              _lib.ptr(out), out.stride(0), B, Hq, Hk, D, nsplit, int(split_keys), int(window), float(scale),
+              _lib.dtype_code(q.dtype), _lib.stream_of(q))
+    return out
+
+
 def fused_attn_workspace(B, Hq, Hk, S_max, D, split_keys, device, step_dev=None):
     """(HandOff holding the partials as granules, counters) of uamd_attn_decode_fused for a cache of S_max positions, zeroed
     here, once."""

@@ -21,6 +21,9 @@ hipGraph like the single-sequence step (`BATCH_ROWS`); a row's logits do not dep
 through the fused NF4 GEMM (as the reference does, utils.py:1095-1097), eager. Prompts of different lengths arrive LEFT-padded
 with their attention_mask: prefill treats the padding as documents, counts RoPE positions from each row's first real token
 and stores row b's keys at cache positions [0, L_b); the step works per row from kv_len[b] and needs nothing else.
+`kv_cache_dtype="fp8"` (opt-in): the cache holds e4m3 codes and one fp32 scale per key (include/unsloth_amd.h; uamd_kv_store_fp8,
+uamd_rope_kv_append_fp8, uamd_attn_decode_fp8) at (D + 4) / (2 D) of the bytes -- for batches and long contexts; one sequence
+leaves the 5-launch step for it.
 """
 import math
 import os
@@ -69,10 +72,20 @@ def left_pad_lengths(attention_mask):
     return n
 
 
+def kv_cache_kind(kv_cache_dtype):
+    """The cache type of an engine: None (`None` / "auto": the cache holds the activation type) or "fp8" (e4m3 codes + one fp32
+    scale per key, include/unsloth_amd.h). Anything else: ValueError."""
+    if kv_cache_dtype is None or kv_cache_dtype == "auto":
+        return None
+    if kv_cache_dtype == "fp8":
+        return "fp8"
+    raise ValueError(f"kv_cache_dtype: None, 'auto' or 'fp8' (got {kv_cache_dtype!r})")
+
+
 class DecodeEngine:
     """Greedy / sampled generation for a (PEFT-wrapped) Llama-family causal LM loaded by unsloth_amd."""
 
-    def __init__(self, model, max_seq_len=2048, batch=1, use_graph=True):
+    def __init__(self, model, max_seq_len=2048, batch=1, use_graph=True, kv_cache_dtype=None):
         from . import llama as _ll
         self.model = model
         self.lm = _base(model)                    # LlamaForCausalLM
@@ -94,9 +107,18 @@ class DecodeEngine:
         self.rows = bool(BATCH_ROWS) and 2 <= batch <= _dk.MAX_ROWS      # the batched step on uamd_gemv_rows
         self.use_graph = bool(use_graph) and (batch == 1 or self.rows)
         L = len(self.core.layers)
-        kw = dict(dtype=self.dtype, device=self.dev)
+        # "fp8": the caches hold e4m3 codes (uint8) and one fp32 scale per (sequence, KV head, position) beside them -- (D + 4) /
+        # (2 D) of the 16-bit cache's bytes. For batches and long contexts, where the cache is most of what a step reads; one
+        # sequence leaves the single-launch step for it (_step_body) and a short one is slower that way.
+        self.kv_cache_dtype = kv_cache_kind(kv_cache_dtype)
+        kw = dict(dtype=torch.uint8 if self.kv_cache_dtype == "fp8" else self.dtype, device=self.dev)
         self.k_cache = [torch.zeros(batch, self.Hk, self.S, self.D, **kw) for _ in range(L)]
         self.v_cache = [torch.zeros(batch, self.Hk, self.S, self.D, **kw) for _ in range(L)]
+        self.k_scale = self.v_scale = None
+        if self.kv_cache_dtype == "fp8":
+            # (codes 0, scale 1: what the quantiser makes of the zero rows a 16-bit cache starts with)
+            self.k_scale = [torch.ones(batch, self.Hk, self.S, dtype=torch.float32, device=self.dev) for _ in range(L)]
+            self.v_scale = [torch.ones(batch, self.Hk, self.S, dtype=torch.float32, device=self.dev) for _ in range(L)]
         # [kv_len per sequence ..., step counter]: ONE add_(1) per token advances both. The step counter (never reset) is the
         # device half of the hand-off tags of the fused kernels (kernels/decode.HandOff): unlike the position it cannot repeat
         # when a new prompt is prefilled or a caller rewinds kv_len
@@ -207,10 +229,19 @@ class DecodeEngine:
             if lens is not None:
                 zero = torch.zeros((), dtype=self.dtype, device=self.dev)
                 Kc, Vc = torch.where(live, K.gather(2, src), zero), torch.where(live, V.gather(2, src), zero)
-            if repeat > 1:
-                Kc, Vc = Kc.repeat_interleave(repeat, 0), Vc.repeat_interleave(repeat, 0)
-            self.k_cache[li][:, :, :T].copy_(Kc)
-            self.v_cache[li][:, :, :T].copy_(Vc)
+            if self.kv_cache_dtype == "fp8":
+                # quantise each prompt once, into the first of its `repeat` rows; the replicas are copies of codes and scales
+                for rows_, codes, scales in ((Kc, self.k_cache[li], self.k_scale[li]), (Vc, self.v_cache[li], self.v_scale[li])):
+                    _dk.kv_store_fp8(rows_, codes[::repeat], scales[::repeat])
+                    if repeat > 1:
+                        c5, s4 = codes.view(B, repeat, self.Hk, self.S, self.D), scales.view(B, repeat, self.Hk, self.S)
+                        c5[:, 1:, :, :T].copy_(c5[:, :1, :, :T])
+                        s4[:, 1:, :, :T].copy_(s4[:, :1, :, :T])
+            else:
+                if repeat > 1:
+                    Kc, Vc = Kc.repeat_interleave(repeat, 0), Vc.repeat_interleave(repeat, 0)
+                self.k_cache[li][:, :, :T].copy_(Kc)
+                self.v_cache[li][:, :, :T].copy_(Vc)
             A = _ll._attention(Q, K, V, seq_info, None, self.window or None)
             o = attn.apply_o(attn, A)
             w2, e2 = self._params[li]["ln2"]
@@ -288,7 +319,7 @@ class DecodeEngine:
 
     @torch.no_grad()
     def _step_body(self):
-        if self.B == 1 and FUSED_STEP:
+        if self.B == 1 and FUSED_STEP and self.kv_cache_dtype is None:       # (the single-launch attention reads a 16-bit cache)
             return self._step_body_fused()
         return self._step_body_plain()
 
@@ -364,11 +395,18 @@ class DecodeEngine:
                 _dk.linear_group_rows(x, P["qkv"], out=qkv)
             else:
                 qkv = torch.cat(self._linear(x, P["qkv"]), dim=1)
-            _dk.rope_kv_append(qkv, self.cos, self.sin, self.kv_len, self.k_cache[li], self.v_cache[li],
-                               self.Hq, self.Hk, self.D)
             a_out = torch.empty(B, self.Hq * self.D, dtype=self.dtype, device=self.dev)
-            _dk.attn_decode(qkv[:, :self.Hq * self.D], self.k_cache[li], self.v_cache[li], self.kv_len, a_out,
-                            self.partials, SPLIT_KEYS, self.scale, len_add=1, window=self.window)
+            if self.kv_cache_dtype == "fp8":
+                _dk.rope_kv_append_fp8(qkv, self.cos, self.sin, self.kv_len, self.k_cache[li], self.v_cache[li],
+                                       self.k_scale[li], self.v_scale[li], self.Hq, self.Hk, self.D)
+                _dk.attn_decode_fp8(qkv[:, :self.Hq * self.D], self.k_cache[li], self.v_cache[li], self.k_scale[li],
+                                    self.v_scale[li], self.kv_len, a_out, self.partials, SPLIT_KEYS, self.scale, len_add=1,
+                                    window=self.window)
+            else:
+                _dk.rope_kv_append(qkv, self.cos, self.sin, self.kv_len, self.k_cache[li], self.v_cache[li],
+                                   self.Hq, self.Hk, self.D)
+                _dk.attn_decode(qkv[:, :self.Hq * self.D], self.k_cache[li], self.v_cache[li], self.kv_len, a_out,
+                                self.partials, SPLIT_KEYS, self.scale, len_add=1, window=self.window)
             (o,) = self._linear(a_out, P["o"])
             resid, x, _ = add_rms_fwd(o, resid, *P["ln2"])
             gate, up = self._linear(x, P["gu"])
@@ -505,7 +543,7 @@ def _eps(norm):
 # silently ignored
 _ENGINE_KWARGS = {"max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "do_sample", "temperature", "top_k", "top_p",
                   "min_p", "attention_mask", "use_cache", "generator", "max_seq_len", "return_dict_in_generate", "output_scores",
-                  "generation_config", "tokenizer", "num_return_sequences"}
+                  "generation_config", "tokenizer", "num_return_sequences", "kv_cache_dtype"}
 
 
 # generation_config fields the engine reads (below the explicit keywords, above the model's own generation config)
@@ -600,6 +638,19 @@ def route_generate(model, input_ids, max_new_tokens, kwargs):
                           num_return_sequences=n, batch=input_ids.shape[0] * n, need=input_ids.shape[1] + int(max_new_tokens))
 
 
+def wanted_kv_cache(model, kv_cache_dtype=None):
+    """The cache type a `generate` call decodes with: its `kv_cache_dtype=` keyword, else what `from_pretrained(...,
+    float8_kv_cache=True)` / `for_inference(model, float8_kv_cache=True)` recorded on the model, else None (the activation
+    type). An unknown string raises ValueError."""
+    if kv_cache_dtype is not None:
+        return kv_cache_kind(kv_cache_dtype)
+    for m in (model, _base(model)):
+        mark = getattr(m, "_uamd_float8_kv_cache", None)
+        if mark is not None:
+            return "fp8" if mark else None
+    return None
+
+
 def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_len=None, **kwargs):
     """llama.py:2167-2259 counterpart: `model.generate(...)` after `FastLanguageModel.for_inference(model)`.
     The reference forwards every keyword to HF's generate; the engine covers greedy / temperature / top-k / top-p / min-p
@@ -608,6 +659,7 @@ def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_le
     right-padded or holey attention_mask, ...) are handed to HF's own generate (`model._old_generate`) -- or raise when it is
     unavailable."""
     input_ids = kwargs.pop("inputs", input_ids)
+    kind = wanted_kv_cache(model, kwargs.pop("kv_cache_dtype", None))       # (the engine's own keyword: HF's generate has none)
     where, what = route_generate(model, input_ids, max_new_tokens, kwargs)
     if where == "old":
         old = getattr(model, "_old_generate", None)
@@ -616,8 +668,9 @@ def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_le
         return old(input_ids, max_new_tokens=max_new_tokens, **kwargs) if max_new_tokens is not None else old(input_ids, **kwargs)
     batch, need = what.pop("batch"), what.pop("need")
     eng = getattr(model, "_uamd_decode_engine", None)
-    if eng is None or eng.B != batch or eng.S < need:
-        eng = DecodeEngine(model, max_seq_len=max(need, max_seq_len or 0), batch=batch)
+    if eng is None or eng.B != batch or eng.S < need or getattr(eng, "kv_cache_dtype", None) != kind:
+        # (kwargs only when asked for: the default engine is built exactly as before)
+        eng = DecodeEngine(model, max_seq_len=max(need, max_seq_len or 0), batch=batch, **(dict(kv_cache_dtype=kind) if kind else {}))
         model._uamd_decode_engine = eng
     return eng.generate(input_ids, **what)
 

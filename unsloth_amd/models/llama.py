@@ -784,10 +784,12 @@ class FastLlamaModel:
         return model
 
     @staticmethod
-    def for_inference(model):
+    def for_inference(model, float8_kv_cache=None):
         """llama.py:3888-3929: eval mode, no checkpointing, and `model.generate` = the KV-cache decode engine
         (models/decode.py: unsloth_fast_generate, the counterpart of llama.py:2167-2259) for the architectures it covers
-        (head_dim 64 or 128, SwiGLU); the HF `generate` stays reachable as `model._old_generate`, as in the reference."""
+        (head_dim 64 or 128, SwiGLU); the HF `generate` stays reachable as `model._old_generate`, as in the reference.
+        `float8_kv_cache` True / False: the engine's KV cache as e4m3 codes + per-key scales, or not (recorded on the model;
+        None leaves what `from_pretrained(..., float8_kv_cache=)` recorded)."""
         from types import MethodType
         from . import decode as _decode
         base = model.get_base_model() if hasattr(model, "get_base_model") else model
@@ -795,6 +797,8 @@ class FastLlamaModel:
             if hasattr(m, "gradient_checkpointing"):
                 m.gradient_checkpointing = False
         model.eval()
+        if float8_kv_cache is not None:
+            model._uamd_float8_kv_cache = bool(float8_kv_cache)
         cfg = base.config
         head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         if head_dim in _decode._dk.HEAD_DIMS and getattr(cfg, "hidden_act", "silu") == "silu" and not hasattr(model, "_old_generate"):

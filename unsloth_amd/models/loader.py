@@ -45,6 +45,9 @@ class FastLanguageModel:
                         device_map="sequential", rope_scaling=None, fix_tokenizer=True,
                         trust_remote_code=False, use_gradient_checkpointing="unsloth", config=None,
                         device=None, random_state=3407, *args, **kwargs):
+        # the reference's name (it hands it to its vLLM engine); here: the decode engine of `model.generate` keeps its KV cache
+        # as e4m3 codes + per-key scales (models/decode.py). Popped before anything else looks at kwargs.
+        float8_kv_cache = bool(kwargs.pop("float8_kv_cache", False))
         if load_in_8bit:
             raise NotImplementedError(
                 "8-bit loading goes through FastModel + the unsloth_zoo compiler in the reference "
@@ -123,6 +126,8 @@ class FastLanguageModel:
         post_patch_loss_function(model)
         FastLlamaModel.for_training(model, use_gradient_checkpointing)
         model._unsloth_full_finetuning = bool(full_finetuning)                                  # _utils.py:2899-2908
+        if float8_kv_cache:
+            model._uamd_float8_kv_cache = True
         if full_finetuning:
             FastLlamaModel.patch_full_finetune(model)
         return model, tokenizer
@@ -143,8 +148,8 @@ class FastLanguageModel:
         return FastLlamaModel.for_training(model, use_gradient_checkpointing)
 
     @staticmethod
-    def for_inference(model):
-        return FastLlamaModel.for_inference(model)
+    def for_inference(model, float8_kv_cache=None):
+        return FastLlamaModel.for_inference(model, float8_kv_cache)
 
 
 # VLM configs whose language tower is a Llama-family decoder the hand-kernel path covers (text_config.model_type -> the
