@@ -520,6 +520,31 @@ int uamd_attn_decode(const void* q, int64_t q_sb, const void* k_cache, const voi
                      int64_t cache_sh, const int* kv_len, int len_add, float* partials, void* out, int64_t out_sb,
                      int B, int Hq, int Hk, int D, int nsplit, int split_keys, int window, float scale, int dtype,
                      void* stream);
+/* uamd_attn_decode for P groups of n_share adjacent rows (row p * n_share + i is sample i of prompt p; 2 <= n_share <= 16, anything
+ * else: UAMD_ERR_ARG before any launch) whose first prompt_len[p] keys are THE SAME and are stored once:
+ *   pk / pv [P, Hk, >= nsplit_prompt * split_keys, D]  (strides p_sb, p_sh, D, 1) the shared prompt caches, prompt_len int32 [P];
+ *   sk / sv [P * n_share, Hk, >= nsplit_new * split_keys, D] (strides s_sb, s_sh, D, 1) every row's own keys after the prompt,
+ *   new_len int32 [P * n_share] how many of them are stored; the step attends new = new_len[row] + len_add of them.
+ * Row r attends the keys [max(0, total - window), total) of the concatenation prompt | suffix, total = prompt_len[r / n_share] +
+ * new (window 0: all): prompt keys [max(0, total - window), prompt_len) and suffix keys [max(0, new - window), new).
+ * D = 64 or 128, bf16 / fp16, Hq / Hk = 1 .. 8, split_keys as for uamd_attn_decode. partials: fp32 workspace
+ * [P * n_share, Hq, nsplit_prompt + nsplit_new, D + 2]. Three plain launches on `stream`:
+ *   1. prefix scan, grid (nsplit_prompt, Hk, P): the online-softmax partials of all n_share * Hq / Hk query rows of (p, kv head)
+ *      over the split's prompt keys -> slots [0, nsplit_prompt) of each of those rows. A prompt K / V byte is fetched once per
+ *      (p, kv head, split), whatever n_share is. Scores and P V run on v_mfma_f32_16x16x32 with the query rows in 16-row tiles.
+ *      Roundings: fp32 accumulation of the exact 16-bit products q_j k_j, times scale * log2 e in fp32; running max and sum in
+ *      fp32 (exp2 domain); P = exp2(s - m) rounded ONCE to `dtype` and the sum taken over the rounded P (all the mass on one
+ *      key returns that V row exactly); P V accumulated in fp32.
+ *   2. suffix scan: uamd_attn_decode's kernel over sk / sv with kv_len = new_len -> slots [nsplit_prompt, nsplit_prompt + nsplit_new).
+ *   3. uamd_attn_decode's combine over all slots, one rounding at the store of `out` [P * n_share, Hq * D] (row stride out_sb).
+ * A split without a valid key enters the combine as (m, l) = (-inf, 0), o = 0. At a fixed (P, n_share, nsplit_*, split_keys) row
+ * r's output is a fixed sequence of operations on its own query, its prompt's cache and its own suffix: bitwise independent of
+ * the other rows and prompts; a NaN query stays in its row. */
+int uamd_attn_decode_shared(const void* q, int64_t q_sb, const void* pk, const void* pv, int64_t p_sb, int64_t p_sh,
+                            const int* prompt_len, int n_share, const void* sk, const void* sv, int64_t s_sb, int64_t s_sh,
+                            const int* new_len, int len_add, float* partials, void* out, int64_t out_sb, int P, int Hq, int Hk,
+                            int D, int nsplit_prompt, int nsplit_new, int split_keys, int window, float scale, int dtype,
+                            void* stream);
 /* ---- FP8 KV cache (opt-in: DecodeEngine(kv_cache_dtype="fp8")) -- THE definition of the stored format --------------------
  * A cache row is one (sequence, KV head, position) vector of D elements, D = 64 or 128. It is stored as D bytes of OCP e4m3fn
  * codes in `codes` [B, Hk, s_max, D] (uint8; strides cache_sb, cache_sh, D, 1) and ONE fp32 scale in `scales` [B, Hk, s_max]

@@ -23,7 +23,9 @@
 //     whole step is replayable as a hipGraph.
 //   * attention: grid (split, kv head, batch); the G query heads of a KV head share every K / V row read; each split
 //     keeps an online-softmax partial (m, l, o[D]) that a second tiny kernel combines. The split count is fixed at
-//     capture time; splits past the current length exit immediately.
+//     capture time; splits past the current length exit immediately. n samples of one prompt (uamd_attn_decode_shared) keep
+//     the prompt's K / V once: a prefix scan scores the n * G query rows of a (prompt, kv head) against one fetch of every
+//     prompt key on the MFMA, the scan above runs over each row's own suffix, and the same kernel combines both.
 #include "nf4_decode.h"
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
@@ -1168,6 +1170,188 @@ __global__ void __launch_bounds__(DD) attn_decode_combine_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Shared-prompt decode attention (uamd_attn_decode_shared), the prefix scan: the n samples of prompt p share ONE prompt cache
+// pk / pv [P, Hk, S_p, DD], so the R = n * G query rows of (p, kv head) -- sample i, head g of the group: row i * G + g -- are
+// scored against every prompt key from one fetch of it. Block (prompt split, kvh, p) = 4 waves:
+//   * the split's keys come in fills of SH_CK = 128: every thread loads its 16-byte pieces of K and V (all loads of a fill in
+//     flight at once; keys outside [oldest key any row of the group attends, min(split end, L_p)) are not loaded and enter as
+//     zeros), K goes to LDS row-major, V transposed ([column][key], two keys per 32-bit word), one barrier;
+//   * the rows are cut into tiles of 16; wave w owns tiles w and w + 4 for the whole split (no merge across waves). Rows >= R
+//     of the last tile are zero fragments: never loaded, never stored;
+//   * per 32 keys and tile: S^T = K Q^T as 2 x DD / 32 v_mfma_f32_16x16x32 (A = 16 keys from LDS, B = the tile's Q fragments,
+//     raw 16-bit q), which leaves lane (row, j) with the row's scores of keys 4 j .. 4 j + 3 of both 16-key halves -- exactly
+//     the 8 contraction slots the lane feeds to O^T += V^T P^T (A = 16 columns of V^T from LDS, B = P), DD / 16 more MFMAs.
+//     The contraction order of the keys is permuted the same way on both operands, nothing is shuffled.
+// Roundings: q . k is the MFMA's fp32 accumulation of exact 16-bit products; the score is that times scale * log2 e in fp32;
+// running max and sum are fp32 in the exp2 domain (softmax_merge); P = exp2(s - m) is rounded ONCE to the activation type, the
+// sum l adds the ROUNDED P (a row whose mass sits on one key returns that V row exactly); P V accumulates in fp32. The partial
+// (o, m, l) is fp32; the combine rounds the output once. A row's partial is a fixed sequence of operations on its own query
+// (one B column of every MFMA), its own new_len and the prompt's cache: no other row's data enters it, a NaN query stays in
+// its row.
+constexpr int SH_CK = 128;
+template <int DD> struct SharedGeo {
+    static constexpr int KROW = DD + 8;                    // elements of a K row in LDS (16 bytes of padding)
+    static constexpr int VROW = SH_CK / 2 + 2;             // 32-bit words of a V^T row: key pairs, 8 bytes of padding
+    static constexpr int LDS = SH_CK * KROW * 2 + DD * VROW * 4;
+};
+
+template <typename T, int DD>
+__global__ void __launch_bounds__(256) attn_decode_prefix_kernel(const T* __restrict__ q, int64_t q_sb, const T* __restrict__ pk,
+                                                                 const T* __restrict__ pv, int64_t p_sb, int64_t p_sh,
+                                                                 const int* __restrict__ prompt_len,
+                                                                 const int* __restrict__ new_len, float* __restrict__ part,
+                                                                 int n_share, int G, int Hq, int nsplit, int split_keys,
+                                                                 int window, float scale_log2, int len_add) {
+    typedef typename RowsMfma<T>::frag frag;
+    union F { uint4 u; uint2 h[2]; uint32_t w[4]; frag f; };
+    constexpr int LPK = DecGeo<DD>::LPK, KROW = SharedGeo<DD>::KROW, VROW = SharedGeo<DD>::VROW;
+    constexpr int KIT = SH_CK * LPK / 256, VIT = KIT / 2;  // 16-byte K loads / V key pairs of a thread per fill
+    constexpr int QF = DD / 32, OT = DD / 16;              // Q fragments of a row; 16-column tiles of O^T
+    extern __shared__ __attribute__((aligned(16))) unsigned char sh_smem[];
+    T* const Ks = reinterpret_cast<T*>(sh_smem);
+    uint32_t* const Vt = reinterpret_cast<uint32_t*>(sh_smem + SH_CK * KROW * 2);
+    const int split = blockIdx.x, kvh = blockIdx.y, p = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, qq = lane >> 4;
+    const int R = n_share * G;
+    const int Lp = prompt_len[p];
+    int first_min = 0;                                     // the oldest key any row of the group attends
+    if (window > 0) {
+        int mn = new_len[p * n_share];
+        for (int i = 1; i < n_share; ++i) mn = min(mn, new_len[p * n_share + i]);
+        first_min = max(0, Lp + mn + len_add - window);
+    }
+    const int s0 = split * split_keys, s1 = min(s0 + split_keys, Lp);
+    // the wave's two tiles: lane (r, qq) works for row 16 t + r
+    bool rok[2];
+    int first[2];
+    int64_t bh[2];
+    F qf[2][QF];
+    float m[2], l[2];
+    rows_f32x4 o[2][OT];
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti) {
+        const int row = (wave + 4 * ti) * 16 + r;
+        rok[ti] = row < R;
+        const int smp = rok[ti] ? row / G : 0, g = rok[ti] ? row - smp * G : 0;
+        const int b = p * n_share + smp;
+        first[ti] = window > 0 ? max(0, Lp + new_len[b] + len_add - window) : 0;
+        bh[ti] = (int64_t)b * Hq + kvh * G + g;
+        const T* qp = q + (int64_t)b * q_sb + (int64_t)(kvh * G + g) * DD + qq * 8;
+#pragma unroll
+        for (int j = 0; j < QF; ++j)
+            qf[ti][j].u = rok[ti] ? *reinterpret_cast<const uint4*>(qp + j * 32) : make_uint4(0, 0, 0, 0);
+        m[ti] = -INFINITY; l[ti] = 0.f;
+#pragma unroll
+        for (int dt = 0; dt < OT; ++dt) o[ti][dt] = rows_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const T* const kb = pk + (int64_t)p * p_sb + (int64_t)kvh * p_sh;
+    const T* const vb = pv + (int64_t)p * p_sb + (int64_t)kvh * p_sh;
+    const int live0 = max(s0, first_min);                  // keys [live0, s1) are loaded
+    const int c_first = s0 + (live0 - s0) / SH_CK * SH_CK; // the first fill with a live key (fills start on the split's grid)
+    for (int c0 = c_first; c0 < s1; c0 += SH_CK) {
+        if (c0 != c_first) __syncthreads();                // the previous fill is still being read
+        uint4 kr[KIT], vr[VIT][2];
+#pragma unroll
+        for (int it = 0; it < KIT; ++it) {
+            const int i = tid + 256 * it, key = c0 + i / LPK, lc = i % LPK;
+            kr[it] = (key >= live0 && key < s1) ? *reinterpret_cast<const uint4*>(kb + (int64_t)key * DD + lc * 8)
+                                                : make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int it = 0; it < VIT; ++it) {
+            const int i = tid + 256 * it, key = c0 + 2 * (i / LPK), lc = i % LPK;
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                vr[it][e] = (key + e >= live0 && key + e < s1)
+                                ? *reinterpret_cast<const uint4*>(vb + (int64_t)(key + e) * DD + lc * 8) : make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int it = 0; it < KIT; ++it) {
+            const int i = tid + 256 * it;
+            *reinterpret_cast<uint4*>(Ks + (i / LPK) * KROW + (i % LPK) * 8) = kr[it];
+        }
+#pragma unroll
+        for (int it = 0; it < VIT; ++it) {
+            const int i = tid + 256 * it, kp = i / LPK, lc = i % LPK;
+            const uint32_t a[4] = {vr[it][0].x, vr[it][0].y, vr[it][0].z, vr[it][0].w};
+            const uint32_t b[4] = {vr[it][1].x, vr[it][1].y, vr[it][1].z, vr[it][1].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                  // columns lc * 8 + 2 j, + 1: (even key, odd key) per word
+                Vt[(lc * 8 + 2 * j) * VROW + kp] = (a[j] & 0xffffu) | (b[j] << 16);
+                Vt[(lc * 8 + 2 * j + 1) * VROW + kp] = (a[j] >> 16) | (b[j] & 0xffff0000u);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti) {
+            if ((wave + 4 * ti) * 16 >= R) continue;       // (wave-uniform)
+            for (int kg = 0; kg < SH_CK / 32; ++kg) {
+                const int k0 = c0 + kg * 32;
+                if (k0 + 32 <= live0 || k0 >= s1) continue;
+                rows_f32x4 sc[2];
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                    sc[hf] = rows_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int j = 0; j < QF; ++j) {
+                        F a;
+                        a.u = *reinterpret_cast<const uint4*>(Ks + (kg * 32 + hf * 16 + r) * KROW + j * 32 + qq * 8);
+                        sc[hf] = RowsMfma<T>::run(a.f, qf[ti][j].f, sc[hf]);
+                    }
+                }
+                // lane (row r, qq): keys k0 + 16 hf + 4 qq + e
+                float s[8], mx = -INFINITY;
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int key = k0 + hf * 16 + qq * 4 + e;
+                        s[hf * 4 + e] = (key >= first[ti] && key < s1) ? sc[hf][e] * scale_log2 : -INFINITY;
+                        mx = fmaxf(mx, s[hf * 4 + e]);
+                    }
+                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+                float alpha, unused;
+                softmax_merge(m[ti], l[ti], mx, 0.f, alpha, unused);      // l: the lane's own keys, summed over qq at the end
+                const float mr = m[ti] == -INFINITY ? 0.f : m[ti];
+                float pr[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    pr[e] = round_to<T>(__builtin_amdgcn_exp2f(s[e] - mr));
+                    l[ti] += pr[e];
+                }
+                F pf;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pf.w[e] = pack2<T>(pr[2 * e], pr[2 * e + 1]);
+#pragma unroll
+                for (int dt = 0; dt < OT; ++dt) {
+                    F a;                                   // V^T[column 16 dt + r][the lane's 8 keys]
+                    const uint32_t* vp = Vt + (dt * 16 + r) * VROW + kg * 16 + qq * 2;
+                    a.h[0] = *reinterpret_cast<const uint2*>(vp);
+                    a.h[1] = *reinterpret_cast<const uint2*>(vp + 8);
+                    o[ti][dt] = RowsMfma<T>::run(a.f, pf.f, o[ti][dt] * alpha);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti) {
+        float ll = l[ti];                                  // fixed order: (qq, qq ^ 1), then (.., .. ^ 2)
+        ll += __shfl_xor(ll, 16, 64);
+        ll += __shfl_xor(ll, 32, 64);
+        if (!rok[ti]) continue;
+        float* pp = part + part_index<DD>(bh[ti], nsplit, split);
+#pragma unroll
+        for (int dt = 0; dt < OT; ++dt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pp[dt * 16 + qq * 4 + e] = o[ti][dt][e];
+        if (qq == 0) { pp[DD] = m[ti]; pp[DD + 1] = ll; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // FP8 KV cache (opt-in; the format is defined once, in include/unsloth_amd.h): a cache row -- one (sequence, KV head, position)
 // vector of DD values -- is DD bytes of OCP e4m3fn codes plus ONE fp32 scale, amax / 448. Half the bytes of a 16-bit row (plus
 // 4), which is what a decode step of a batch at a long context reads. The lane geometry is DecGeo's throughout: DD / 8 lanes
@@ -1919,6 +2103,42 @@ extern "C" int uamd_attn_decode(const void* q, int64_t q_sb, const void* k_cache
         constexpr int G = decltype(g)::value, DD = decltype(dd)::value;
         hipLaunchKernelGGL((attn_decode_kernel<T, G, DD>), grid, dim3(256), 0, st, (const T*)q, q_sb, (const T*)k_cache,
                            (const T*)v_cache, cache_sb, cache_sh, kv_len, partials, Hq, nsplit, split_keys, window, sl2, len_add);
+        if (int rc = uamd_launch_status()) return rc;
+        hipLaunchKernelGGL((attn_decode_combine_kernel<T, DD>), dim3(Hq, B), dim3(DD), 0, st, partials, (T*)out, out_sb, Hq, nsplit);
+        return uamd_launch_status();
+    });
+}
+
+// uamd_attn_decode for P groups of n_share rows that share their first prompt_len[p] keys (include/unsloth_amd.h). Three plain
+// launches on one stream: attn_decode_prefix_kernel over the shared prompt caches -> partial slots [0, nsplit_prompt) of every
+// row; attn_decode_kernel, as it is, over the per-row suffix caches with kv_len = new_len -> slots [nsplit_prompt, nsplit_prompt +
+// nsplit_new) (the first-slot offset rides in the partials pointer, the total split count is the stride); the combine over all.
+extern "C" int uamd_attn_decode_shared(const void* q, int64_t q_sb, const void* pk, const void* pv, int64_t p_sb, int64_t p_sh,
+                                       const int* prompt_len, int n_share, const void* sk, const void* sv, int64_t s_sb,
+                                       int64_t s_sh, const int* new_len, int len_add, float* partials, void* out, int64_t out_sb,
+                                       int P, int Hq, int Hk, int D, int nsplit_prompt, int nsplit_new, int split_keys,
+                                       int window, float scale, int dtype, void* stream) {
+    if (!q || !prompt_len || !new_len || !partials || !out || P <= 0 || Hq <= 0 || Hk <= 0) return UAMD_ERR_ARG;
+    if (n_share < 2 || n_share > 16) return UAMD_ERR_ARG;
+    if (!pk || !pv || !sk || !sv) return UAMD_ERR_ARG;
+    if (int rc = attn_decode_check(Hq, Hk, D, nsplit_prompt, split_keys, pk, pv, p_sb, p_sh)) return rc;
+    if (int rc = attn_decode_check(Hq, Hk, D, nsplit_new, split_keys, sk, sv, s_sb, s_sh)) return rc;
+    if (Hq / Hk > 8) return UAMD_ERR_ARG;
+    if (!aligned16(q) || (q_sb & 7)) return UAMD_ERR_ALIGN;
+    const float sl2 = scale * 1.4426950408889634f;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = P * n_share, nsplit = nsplit_prompt + nsplit_new;
+    return attn_decode_dispatch(dtype, D, Hq / Hk, [&](auto t, auto g, auto dd) -> int {
+        using T = decltype(t);
+        constexpr int G = decltype(g)::value, DD = decltype(dd)::value;
+        if (int rc = uamd_launch_lds<&attn_decode_prefix_kernel<T, DD>>(
+                dim3((unsigned)nsplit_prompt, (unsigned)Hk, (unsigned)P), dim3(256), SharedGeo<DD>::LDS, st, (const T*)q, q_sb,
+                (const T*)pk, (const T*)pv, p_sb, p_sh, prompt_len, new_len, partials, n_share, G, Hq, nsplit, split_keys, window,
+                sl2, len_add))
+            return rc;
+        hipLaunchKernelGGL((attn_decode_kernel<T, G, DD>), dim3((unsigned)nsplit_new, (unsigned)Hk, (unsigned)B), dim3(256), 0, st,
+                           (const T*)q, q_sb, (const T*)sk, (const T*)sv, s_sb, s_sh, new_len,
+                           partials + (int64_t)nsplit_prompt * (DD + 2), Hq, nsplit, split_keys, window, sl2, len_add);
         if (int rc = uamd_launch_status()) return rc;
         hipLaunchKernelGGL((attn_decode_combine_kernel<T, DD>), dim3(Hq, B), dim3(DD), 0, st, partials, (T*)out, out_sb, Hq, nsplit);
         return uamd_launch_status();

@@ -386,6 +386,34 @@ def attn_decode(q, k_cache, v_cache, kv_len, out, partials, split_keys, scale, l
     return out
 
 
+MAX_SHARE = 16                        # samples per prompt of one uamd_attn_decode_shared launch (n * G <= 128 query rows)
+
+
+def attn_decode_shared(q, pk, pv, prompt_len, n_share, sk, sv, new_len, out, partials, split_keys, scale, len_add=1, window=0):
+    """`attn_decode` for P groups of `n_share` adjacent rows that share their prompt's keys (uamd_attn_decode_shared): q, out
+    [P * n, Hq*D]; pk / pv [P, Hk, S_p, D] with prompt_len int32 [P]; sk / sv [P * n, Hk, S_n, D] with new_len int32 [P * n];
+    partials fp32 [P * n, Hq, S_p / split_keys + S_n / split_keys, D + 2]. Row r attends the last `window` keys (0: all) of
+    prompt r // n followed by its own new_len[r] + len_add suffix keys."""
+    _lib.require_gpu(q)
+    P, Hk, S_p, D = pk.shape
+    B, _, S_n, _ = sk.shape
+    Hq = partials.shape[1]
+    nsp, nsn = S_p // split_keys, S_n // split_keys
+    assert pv.shape == pk.shape and sv.shape == sk.shape and tuple(sk.shape[1::2]) == (Hk, D) and B == P * int(n_share)
+    assert S_p % split_keys == 0 and S_n % split_keys == 0 and tuple(partials.shape) == (B, Hq, nsp + nsn, D + 2)
+    assert partials.is_contiguous() and partials.dtype == torch.float32
+    assert q.stride(1) == 1 and out.stride(1) == 1 and q.shape[0] == B and out.shape[0] == B
+    assert pk.stride()[2:] == (D, 1) and pv.stride() == pk.stride() and sk.stride()[2:] == (D, 1) and sv.stride() == sk.stride()
+    assert pk.dtype == pv.dtype == sk.dtype == sv.dtype == q.dtype == out.dtype
+    assert prompt_len.dtype == torch.int32 and new_len.dtype == torch.int32 and prompt_len.numel() == P and new_len.numel() == B
+    assert prompt_len.is_contiguous() and new_len.is_contiguous()
+    _lib.call("uamd_attn_decode_shared", q, _lib.ptr(q), q.stride(0), _lib.ptr(pk), _lib.ptr(pv), pk.stride(0), pk.stride(1),
+              _lib.ptr(prompt_len), int(n_share), _lib.ptr(sk), _lib.ptr(sv), sk.stride(0), sk.stride(1), _lib.ptr(new_len),
+              int(len_add), _lib.ptr(partials), _lib.ptr(out), out.stride(0), P, Hq, Hk, D, nsp, nsn, int(split_keys),
+              int(window), float(scale), _lib.dtype_code(q.dtype), _lib.stream_of(q))
+    return out
+
+
 def _fp8_cache(codes, scales):
     """Asserts the layout of one FP8 cache (include/unsloth_amd.h): codes uint8 [B, Hk, S_max, D] and scales fp32 [B, Hk, S_max];
     the batch stride is free (every n-th row of a cache is a cache), the rest is dense. Returns (B, Hk, S_max, D)."""

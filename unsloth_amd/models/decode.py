@@ -24,6 +24,9 @@ and stores row b's keys at cache positions [0, L_b); the step works per row from
 `kv_cache_dtype="fp8"` (opt-in): the cache holds e4m3 codes and one fp32 scale per key (include/unsloth_amd.h; uamd_kv_store_fp8,
 uamd_rope_kv_append_fp8, uamd_attn_decode_fp8) at (D + 4) / (2 D) of the bytes -- for batches and long contexts; one sequence
 leaves the 5-launch step for it.
+`share_prompt=n` (opt-in, 16-bit cache): rows p n .. p n + n - 1 are n samples of prompt p (num_return_sequences; GRPO's n
+completions of one prompt). The prompt's K / V are stored once per prompt and each row keeps only the keys it appended; the step's
+attention (uamd_attn_decode_shared) scores the n x G query rows of a (prompt, KV head) against one fetch of every prompt key.
 """
 import math
 import os
@@ -85,7 +88,8 @@ def kv_cache_kind(kv_cache_dtype):
 class DecodeEngine:
     """Greedy / sampled generation for a (PEFT-wrapped) Llama-family causal LM loaded by unsloth_amd."""
 
-    def __init__(self, model, max_seq_len=2048, batch=1, use_graph=True, kv_cache_dtype=None):
+    def __init__(self, model, max_seq_len=2048, batch=1, use_graph=True, kv_cache_dtype=None, share_prompt=None,
+                 max_new_tokens=None):
         from . import llama as _ll
         self.model = model
         self.lm = _base(model)                    # LlamaForCausalLM
@@ -112,8 +116,27 @@ class DecodeEngine:
         # sequence leaves the single-launch step for it (_step_body) and a short one is slower that way.
         self.kv_cache_dtype = kv_cache_kind(kv_cache_dtype)
         kw = dict(dtype=torch.uint8 if self.kv_cache_dtype == "fp8" else self.dtype, device=self.dev)
-        self.k_cache = [torch.zeros(batch, self.Hk, self.S, self.D, **kw) for _ in range(L)]
-        self.v_cache = [torch.zeros(batch, self.Hk, self.S, self.D, **kw) for _ in range(L)]
+        # share_prompt = n >= 2: rows p n .. p n + n - 1 are the n samples of prompt p. The prompt's K / V are stored ONCE, in
+        # pk / pv [P, Hk, S, D] (S: the prompt capacity, `max_seq_len`), and k_cache / v_cache [P n, Hk, S_n, D] hold only what
+        # each row appended after it (S_n: `max_new_tokens`, default max_seq_len). prompt_len [P] is fixed by prefill, new_len
+        # [P n] counts the suffix keys and kv_len stays the total; the step reads every counter from device memory.
+        self.share_prompt = None if share_prompt is None else int(share_prompt)
+        self.S_n = self.S
+        self.pk = self.pv = self.prompt_len = self.new_len = None
+        if self.share_prompt is not None:
+            n = self.share_prompt
+            if n < 2 or batch % n:
+                raise ValueError(f"share_prompt: n >= 2 samples per prompt and a batch of P * n rows (got n = {n}, batch = {batch})")
+            if n > _dk.MAX_SHARE:
+                raise NotImplementedError(f"uamd_attn_decode_shared takes up to {_dk.MAX_SHARE} samples per prompt (got {n})")
+            if self.kv_cache_dtype == "fp8":
+                raise NotImplementedError("share_prompt together with kv_cache_dtype='fp8': the shared FP8 prompt cache is not built")
+            self.S_n = int(math.ceil((max_new_tokens or max_seq_len) / SPLIT_KEYS) * SPLIT_KEYS)
+            self.pk = [torch.zeros(batch // n, self.Hk, self.S, self.D, **kw) for _ in range(L)]
+            self.pv = [torch.zeros(batch // n, self.Hk, self.S, self.D, **kw) for _ in range(L)]
+            self.prompt_len = torch.zeros(batch // n, dtype=torch.int32, device=self.dev)
+        self.k_cache = [torch.zeros(batch, self.Hk, self.S_n, self.D, **kw) for _ in range(L)]
+        self.v_cache = [torch.zeros(batch, self.Hk, self.S_n, self.D, **kw) for _ in range(L)]
         self.k_scale = self.v_scale = None
         if self.kv_cache_dtype == "fp8":
             # (codes 0, scale 1: what the quantiser makes of the zero rows a 16-bit cache starts with)
@@ -122,12 +145,18 @@ class DecodeEngine:
         # [kv_len per sequence ..., step counter]: ONE add_(1) per token advances both. The step counter (never reset) is the
         # device half of the hand-off tags of the fused kernels (kernels/decode.HandOff): unlike the position it cannot repeat
         # when a new prompt is prefilled or a caller rewinds kv_len
-        self._pos = torch.zeros(batch + 1, dtype=torch.int32, device=self.dev)
-        self._pos[batch] = 1
+        # (a shared prompt: [kv_len ..., new_len ..., step counter] -- the same add_(1) advances the suffix count)
+        npos = batch * (2 if self.share_prompt else 1)
+        self._pos = torch.zeros(npos + 1, dtype=torch.int32, device=self.dev)
+        self._pos[npos] = 1
         self.kv_len = self._pos[:batch]
-        self.step_ctr = self._pos[batch:]
+        self._lens = self._pos[:npos]                 # every length counter: what a capture's warm-up has to put back
+        if self.share_prompt:
+            self.new_len = self._pos[batch:npos]
+        self.step_ctr = self._pos[npos:]
         self._steps = 1                               # host mirror of step_ctr (no sync): wrap-around guard
-        self.partials = torch.empty(batch, self.Hq, self.S // SPLIT_KEYS, self.D + 2, dtype=torch.float32, device=self.dev)
+        nsplit = self.S // SPLIT_KEYS + (self.S_n // SPLIT_KEYS if self.share_prompt else 0)      # prompt splits, then suffix splits
+        self.partials = torch.empty(batch, self.Hq, nsplit, self.D + 2, dtype=torch.float32, device=self.dev)
         # the fused attention's splits: 128 keys each (64 keys = 256 workgroups at context 2048 measured 3.5 % slower per token,
         # profiles/r04_decode_split_keys_ab.txt), longer ones where 128 would mean more than 256 workgroups -- up to 256 of them
         # combine through granules, a larger launch pays the 21 us fence + arrival-counter tail: 256 keys at context 8192 with 8 KV
@@ -141,7 +170,7 @@ class DecodeEngine:
         self.next_tok = torch.zeros(batch, dtype=torch.long, device=self.dev)
         self.logits = None
         tables = _ll._rope_tables(self.core)
-        self.cos, self.sin = tables.get(self.S, self.dev, self.dtype)
+        self.cos, self.sin = tables.get(self.S + (self.S_n if self.share_prompt else 0), self.dev, self.dtype)
         self._graph = None
         assert 5 * L + 1 < 1024, "hand-off tag sites: 5 per layer below UAMD_TAG_STRIDE"
         self._params = [self._layer_params(l) for l in self.core.layers]
@@ -176,6 +205,7 @@ class DecodeEngine:
         from ..kernels import attention as _flash
         B, T = input_ids.shape
         assert B * repeat == self.B and T <= self.S
+        assert self.share_prompt is None or repeat == self.share_prompt, "an engine with share_prompt = n prefills with repeat = n"
         lens = pad = seq_info = rope_pos = None
         if attention_mask is not None and not bool((attention_mask != 0).all()):
             attention_mask = attention_mask.to(self.dev)
@@ -237,6 +267,9 @@ class DecodeEngine:
                         c5, s4 = codes.view(B, repeat, self.Hk, self.S, self.D), scales.view(B, repeat, self.Hk, self.S)
                         c5[:, 1:, :, :T].copy_(c5[:, :1, :, :T])
                         s4[:, 1:, :, :T].copy_(s4[:, :1, :, :T])
+            elif self.share_prompt:                 # once per prompt: no replicas
+                self.pk[li][:, :, :T].copy_(Kc)
+                self.pv[li][:, :, :T].copy_(Vc)
             else:
                 if repeat > 1:
                     Kc, Vc = Kc.repeat_interleave(repeat, 0), Vc.repeat_interleave(repeat, 0)
@@ -254,6 +287,9 @@ class DecodeEngine:
             self.kv_len.fill_(T)
         else:
             self.kv_len.copy_(lens.repeat_interleave(repeat, 0))
+        if self.share_prompt:
+            self.prompt_len.copy_(self.kv_len[::repeat])
+            self.new_len.zero_()
         xn = xn.view(B, -1)
         self.logits = self._lm_head(xn if repeat == 1 else xn.repeat_interleave(repeat, 0))
         return self.logits
@@ -402,6 +438,12 @@ class DecodeEngine:
                 _dk.attn_decode_fp8(qkv[:, :self.Hq * self.D], self.k_cache[li], self.v_cache[li], self.k_scale[li],
                                     self.v_scale[li], self.kv_len, a_out, self.partials, SPLIT_KEYS, self.scale, len_add=1,
                                     window=self.window)
+            elif self.share_prompt:                 # slot new_len[b] of the row's suffix, RoPE position = the total length
+                _dk.rope_kv_append(qkv, self.cos, self.sin, self.new_len, self.k_cache[li], self.v_cache[li],
+                                   self.Hq, self.Hk, self.D, rope_pos=self.kv_len)
+                _dk.attn_decode_shared(qkv[:, :self.Hq * self.D], self.pk[li], self.pv[li], self.prompt_len, self.share_prompt,
+                                       self.k_cache[li], self.v_cache[li], self.new_len, a_out, self.partials, SPLIT_KEYS,
+                                       self.scale, len_add=1, window=self.window)
             else:
                 _dk.rope_kv_append(qkv, self.cos, self.sin, self.kv_len, self.k_cache[li], self.v_cache[li],
                                    self.Hq, self.Hk, self.D)
@@ -437,16 +479,16 @@ class DecodeEngine:
         g, gl = ("_graph", "_graph_logits") if self._sample is None else ("_graph_s", "_graph_s_logits")
         if getattr(self, g) is None:
             # eager warm-up (first-use attribute calls, allocator growth), with the position restored afterwards
-            kv0, ctr0 = self.kv_len.clone(), self._draw_ctr.clone()
+            kv0, ctr0 = self._lens.clone(), self._draw_ctr.clone()
             self._step_body()
-            self.kv_len.copy_(kv0)
+            self._lens.copy_(kv0)
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 self._step_body()
             setattr(self, g, graph)
             setattr(self, gl, self.logits)       # the graph's static output buffer (prefill() rebinds self.logits)
-            self.kv_len.copy_(kv0)               # the capture itself does not execute
+            self._lens.copy_(kv0)                # the capture itself does not execute
             self._draw_ctr.copy_(ctr0)
         getattr(self, g).replay()
         self.logits = getattr(self, gl)
@@ -460,7 +502,8 @@ class DecodeEngine:
         `attention_mask`: left-padded prompts (see `prefill`); the padded prompt is returned in front of the new tokens.
         `num_return_sequences` = n > 1 (sampling only): the engine's batch is B * n, every prompt is prefilled once and decoded
         as n adjacent rows that draw differently (the draw is keyed on the row) -- the tokens of the same call on
-        input_ids.repeat_interleave(n, 0).
+        input_ids.repeat_interleave(n, 0). An engine built with share_prompt = n takes exactly that n, and at most its suffix
+        capacity of new tokens.
         Sampling happens on the device (uamd_sample_f32): one 64-bit seed per call is drawn from `generator` (the default
         generator of its device when None) without a sync, the first token is drawn from the prefill logits at draw 0 and every
         later one inside the token step, so equally seeded generators give equal tokens."""
@@ -483,7 +526,7 @@ class DecodeEngine:
         eos_t = None if eos is None else torch.tensor(eos, device=self.dev)
         pad = pad_token_id if pad_token_id is not None else (eos[0] if eos else 0)
         done = torch.zeros(self.B, dtype=torch.bool, device=self.dev)
-        room = self.S - input_ids.shape[1]
+        room = self.S_n if self.share_prompt else self.S - input_ids.shape[1]      # (a shared prompt: the suffix caches' slots)
         # a hand-off inside the fused decode launches that times out (csrc/decode.hip: a workgroup polled 2^18 times for a granule
         # that never came) poisons its output with NaN on purpose; NaN logits would otherwise turn into plausible-looking token ids
         # through argmax / multinomial. One element per row and token is accumulated (NaN * 0 = NaN) and looked at ONCE, after
@@ -543,7 +586,7 @@ def _eps(norm):
 # silently ignored
 _ENGINE_KWARGS = {"max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "do_sample", "temperature", "top_k", "top_p",
                   "min_p", "attention_mask", "use_cache", "generator", "max_seq_len", "return_dict_in_generate", "output_scores",
-                  "generation_config", "tokenizer", "num_return_sequences", "kv_cache_dtype"}
+                  "generation_config", "tokenizer", "num_return_sequences", "kv_cache_dtype", "share_prompt_cache"}
 
 
 # generation_config fields the engine reads (below the explicit keywords, above the model's own generation config)
@@ -651,15 +694,31 @@ def wanted_kv_cache(model, kv_cache_dtype=None):
     return None
 
 
+def wanted_share_prompt(model, share_prompt_cache=None):
+    """Whether a `generate` call with num_return_sequences = n > 1 keeps ONE prompt cache for the n samples of a prompt: its
+    `share_prompt_cache=` keyword, else what `from_pretrained(..., share_prompt_cache=True)` / `for_inference(model,
+    share_prompt_cache=True)` recorded on the model, else False."""
+    if share_prompt_cache is not None:
+        return bool(share_prompt_cache)
+    for m in (model, _base(model)):
+        mark = getattr(m, "_uamd_share_prompt_cache", None)
+        if mark is not None:
+            return bool(mark)
+    return False
+
+
 def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_len=None, **kwargs):
     """llama.py:2167-2259 counterpart: `model.generate(...)` after `FastLanguageModel.for_inference(model)`.
     The reference forwards every keyword to HF's generate; the engine covers greedy / temperature / top-k / top-p / min-p
     decoding of unpadded and LEFT-padded batches (pad tokens under the mask's zeros), `num_return_sequences` when sampling and a `generation_config=` object
     whose other fields are at their defaults. Calls outside that (repetition_penalty, beams, streamers, logits processors, a
     right-padded or holey attention_mask, ...) are handed to HF's own generate (`model._old_generate`) -- or raise when it is
-    unavailable."""
+    unavailable. `share_prompt_cache=True` (the keyword, or the model's record: `wanted_share_prompt`) with
+    num_return_sequences = n > 1: the engine is built with share_prompt = n -- one prompt cache for the n samples of a prompt;
+    with n = 1 it does nothing."""
     input_ids = kwargs.pop("inputs", input_ids)
     kind = wanted_kv_cache(model, kwargs.pop("kv_cache_dtype", None))       # (the engine's own keyword: HF's generate has none)
+    share = wanted_share_prompt(model, kwargs.pop("share_prompt_cache", None))      # (likewise)
     where, what = route_generate(model, input_ids, max_new_tokens, kwargs)
     if where == "old":
         old = getattr(model, "_old_generate", None)
@@ -668,7 +727,19 @@ def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_le
         return old(input_ids, max_new_tokens=max_new_tokens, **kwargs) if max_new_tokens is not None else old(input_ids, **kwargs)
     batch, need = what.pop("batch"), what.pop("need")
     eng = getattr(model, "_uamd_decode_engine", None)
-    if eng is None or eng.B != batch or eng.S < need or getattr(eng, "kv_cache_dtype", None) != kind:
+    n = what["num_return_sequences"]
+    if share and n > 1:
+        # one prompt cache for the n samples of a prompt: prompt capacity >= T, suffix capacity >= the call's new tokens
+        if kind == "fp8":
+            raise NotImplementedError("share_prompt_cache together with kv_cache_dtype='fp8': the shared FP8 prompt cache is not built")
+        T, new = input_ids.shape[1], need - input_ids.shape[1]
+        if (eng is None or eng.B != batch or getattr(eng, "share_prompt", None) != n or eng.S < T or eng.S_n < new
+                or getattr(eng, "kv_cache_dtype", None) is not None):
+            eng = DecodeEngine(model, max_seq_len=max(T, max_seq_len or 0), batch=batch, share_prompt=n, max_new_tokens=max(new, 1))
+            model._uamd_decode_engine = eng
+        return eng.generate(input_ids, **what)
+    if (eng is None or eng.B != batch or eng.S < need or getattr(eng, "kv_cache_dtype", None) != kind
+            or getattr(eng, "share_prompt", None) is not None):
         # (kwargs only when asked for: the default engine is built exactly as before)
         eng = DecodeEngine(model, max_seq_len=max(need, max_seq_len or 0), batch=batch, **(dict(kv_cache_dtype=kind) if kind else {}))
         model._uamd_decode_engine = eng

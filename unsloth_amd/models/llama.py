@@ -784,12 +784,13 @@ class FastLlamaModel:
         return model
 
     @staticmethod
-    def for_inference(model, float8_kv_cache=None):
+    def for_inference(model, float8_kv_cache=None, share_prompt_cache=None):
         """llama.py:3888-3929: eval mode, no checkpointing, and `model.generate` = the KV-cache decode engine
         (models/decode.py: unsloth_fast_generate, the counterpart of llama.py:2167-2259) for the architectures it covers
         (head_dim 64 or 128, SwiGLU); the HF `generate` stays reachable as `model._old_generate`, as in the reference.
         `float8_kv_cache` True / False: the engine's KV cache as e4m3 codes + per-key scales, or not (recorded on the model;
-        None leaves what `from_pretrained(..., float8_kv_cache=)` recorded)."""
+        None leaves what `from_pretrained(..., float8_kv_cache=)` recorded). `share_prompt_cache` True / False, recorded the
+        same way: `generate(..., num_return_sequences=n)` stores each prompt's K / V once for its n samples, or n times."""
         from types import MethodType
         from . import decode as _decode
         base = model.get_base_model() if hasattr(model, "get_base_model") else model
@@ -799,6 +800,8 @@ class FastLlamaModel:
         model.eval()
         if float8_kv_cache is not None:
             model._uamd_float8_kv_cache = bool(float8_kv_cache)
+        if share_prompt_cache is not None:
+            model._uamd_share_prompt_cache = bool(share_prompt_cache)
         cfg = base.config
         head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         if head_dim in _decode._dk.HEAD_DIMS and getattr(cfg, "hidden_act", "silu") == "silu" and not hasattr(model, "_old_generate"):

@@ -48,6 +48,7 @@ class FastLanguageModel:
         # the reference's name (it hands it to its vLLM engine); here: the decode engine of `model.generate` keeps its KV cache
         # as e4m3 codes + per-key scales (models/decode.py). Popped before anything else looks at kwargs.
         float8_kv_cache = bool(kwargs.pop("float8_kv_cache", False))
+        share_prompt_cache = bool(kwargs.pop("share_prompt_cache", False))      # (the decode engine's own switch, recorded below)
         if load_in_8bit:
             raise NotImplementedError(
                 "8-bit loading goes through FastModel + the unsloth_zoo compiler in the reference "
@@ -128,6 +129,8 @@ class FastLanguageModel:
         model._unsloth_full_finetuning = bool(full_finetuning)                                  # _utils.py:2899-2908
         if float8_kv_cache:
             model._uamd_float8_kv_cache = True
+        if share_prompt_cache:
+            model._uamd_share_prompt_cache = True
         if full_finetuning:
             FastLlamaModel.patch_full_finetune(model)
         return model, tokenizer
@@ -148,8 +151,8 @@ class FastLanguageModel:
         return FastLlamaModel.for_training(model, use_gradient_checkpointing)
 
     @staticmethod
-    def for_inference(model, float8_kv_cache=None):
-        return FastLlamaModel.for_inference(model, float8_kv_cache)
+    def for_inference(model, float8_kv_cache=None, share_prompt_cache=None):
+        return FastLlamaModel.for_inference(model, float8_kv_cache, share_prompt_cache)
 
 
 # VLM configs whose language tower is a Llama-family decoder the hand-kernel path covers (text_config.model_type -> the
