@@ -463,6 +463,12 @@ int uamd_gemv(const void* x, int K, const uamd_gemv_group* groups, int n_groups,
  * [0, N) is written. */
 int uamd_gemv_rows(const void* x, int64_t ldx, int M, int K, const uamd_gemv_group* groups, int n_groups, int64_t ldy,
                    int64_t ldt, int nf4, int blocksize, int dtype, void* stream);
+/* uamd_gemv_rows64: uamd_gemv_rows for M = 1 .. 64 token rows, still ONE pass over the weights (17 rows and up: every decoded
+ * weight fragment meets 2 or 4 token tiles; M <= 16 is uamd_gemv_rows' own launch). Same arguments, limits and errors
+ * (M > 64: UAMD_ERR_ARG). The row-independence contract extends: Y[m, n] is bit for bit what uamd_gemv_rows stores for that
+ * token row and weight row, so a 64-row launch equals four 16-row launches on its slices. */
+int uamd_gemv_rows64(const void* x, int64_t ldx, int M, int K, const uamd_gemv_group* groups, int n_groups, int64_t ldy,
+                     int64_t ldt, int nf4, int blocksize, int dtype, void* stream);
 /* uamd_gemv_fused: the same launch with the token PRODUCED inside it and the LoRA `t = A x` computed INSIDE it, once, so that
  * one decoder layer of a decode step is 5 launches (q|k|v, attention, o, gate|up -> h, down) instead of 14
  * (LlamaModel_fast_forward_inference, llama.py:1249-1364: residual adds, fast_rms_layernorm_inference, fast_swiglu_inference

@@ -1,7 +1,8 @@
-"""Batched decode: ms per step and aggregate tokens/s of the token step at batch 1, 2, 4, 8, 16 -- Llama-3-8B shape, NF4, LoRA
-r = 16, the benchmark's synthetic weights, context 2048.
+"""Batched decode: ms per step and aggregate tokens/s of the token step at batch 1, 2, 4, 8, 16, 24, 32, 48, 64 -- Llama-3-8B
+shape, NF4, LoRA r = 16, the benchmark's synthetic weights, context 2048.
 
-Route `rows` is the step on uamd_gemv_rows, replayed as a hipGraph (batch 1: the fused single-sequence step, replayed). Route
+Route `rows` is the step on uamd_gemv_rows (17 rows and up: uamd_gemv_rows64), replayed as a hipGraph (batch 1: the fused
+single-sequence step, replayed). Route
 `gemm` is the step through the 128 x 128-tile NF4 GEMM + separate LoRA / bias launches, eager, selected in the same process
 with models.decode.BATCH_ROWS = False: what a batch > 1 cost before the rows kernel. The two routes alternate round by round;
 every round decodes the same positions (the cache holds random keys: the step's traffic does not depend on their values).
@@ -84,7 +85,7 @@ def main():
     ap.add_argument("--kv-cache", default="auto", help="auto (the activation type), or a list such as auto,fp8: compare cache types")
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--batches", default="1,2,4,8,16")
+    ap.add_argument("--batches", default="1,2,4,8,16,24,32,48,64")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():

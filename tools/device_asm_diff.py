@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Is the device code of two trees the same?  python tools/device_asm_diff.py OTHER_TREE [THIS_TREE]
+"""Is the device code of two trees the same?  python tools/device_asm_diff.py [--rename REGEX=REPL] OTHER_TREE [THIS_TREE]
 
 Compiles every file of _build.SOURCES in both trees to device-only assembly with the build's own flags (_build._flags(source)
 + --cuda-device-only -S) and compares. Lines naming __hip_cuid_ (a hash of the translation unit) may differ. A file whose
 lines differ otherwise is compared kernel by kernel (a host-side change of dispatch order makes the compiler emit the same
 kernels in another order, which renumbers the local labels): same set of kernels, same body and .amdhsa_ block per kernel,
-same metadata entry per kernel; every kernel that differs is named. Exit status 0 = the same device code. No GPU needed."""
+same metadata entry per kernel; every kernel that differs is named. `--rename REGEX=REPL` rewrites THIS tree's assembly first:
+a kernel template that gained a parameter keeps its old symbol for the instances that existed (the new instances are then the
+only kernels named). Exit status 0 = the same device code. No GPU needed."""
 import difflib
 import importlib.util
 import os
@@ -59,10 +61,16 @@ def kernels(text):
 
 
 def main():
-    other = os.path.abspath(sys.argv[1])
-    this = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    argv, renames = sys.argv[1:], []
+    while argv and argv[0] == "--rename":
+        renames.append(argv[1].split("=", 1))
+        argv = argv[2:]
+    other = os.path.abspath(argv[0])
+    this = os.path.abspath(argv[1]) if len(argv) > 1 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
         a, b = assemble(other, ta), assemble(this, tb)
+    for pat, repl in renames:
+        b = {s: re.sub(pat, repl, t) for s, t in b.items()}
     if set(a) != set(b):
         print("different SOURCES:", sorted(set(a) ^ set(b)))
         return 1

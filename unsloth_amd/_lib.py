@@ -166,6 +166,8 @@ SIGNATURES = {
     "uamd_gemv": (c_int, [c_void_p, c_int, ctypes.POINTER(GemvGroup), c_int, c_int, c_int, c_int, c_void_p]),
     "uamd_gemv_rows": (c_int, [c_void_p, c_int64, c_int, c_int, ctypes.POINTER(GemvGroup), c_int, c_int64, c_int64, c_int, c_int,
                                c_int, c_void_p]),
+    "uamd_gemv_rows64": (c_int, [c_void_p, c_int64, c_int, c_int, ctypes.POINTER(GemvGroup), c_int, c_int64, c_int64, c_int, c_int,
+                                 c_int, c_void_p]),
     "uamd_gemv_fused": (c_int, [c_void_p, c_int, ctypes.POINTER(GemvGroup), c_int, c_int, c_int, c_int, c_void_p,
                                 ctypes.POINTER(GemvPrologue)]),
     "uamd_rope_kv_append": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -741,6 +741,14 @@ int launch_gemv(const GemvArgs& a, hipStream_t st) {
 //     (the MFMA computes each D element from its own A row and B column). A NaN in one token row stays in its column of D.
 //   * The epilogue (all 512 threads, one output each per pass) adds the LoRA term s * B[n, :] . t[m, :] (t fp32, from an
 //     earlier launch over the stacked A rows) and the bias, and stores to y + m * ldy + n.
+//   * uamd_gemv_rows64, M = 17 .. 64: MT = 2 | 4 token tiles of 16 rows. Every weight fragment is decoded once and feeds MT
+//     MFMAs against MT token fragments into acc[RT][MT]; chunk-to-wave assignment, MFMA order per accumulator, the wave-order
+//     sum and the epilogue are those of MT = 1, so Y[m][n] has the bits the 16-row launch gives that token row -- it does
+//     not depend on MT either. Registers: two stages of 16 MT token-fragment registers are not to be had (MT = 4: 128), so
+//     only the weights are double-buffered and ONE set of token fragments is requested right before the next stage's
+//     weights; the widest instances (RT MT >= 8: 64 accumulator + 64 fragment registers, up to 221 VGPRs, 64 - 128 KiB of
+//     partial tiles) take one workgroup per CU rather than spill -- none uses scratch (tests/test_decode_batch64_host.py).
+//     The MT = 1 instances are the code they were (profiles/rows64_mt1_device_asm_diff.txt).
 constexpr int ROWS_THREADS = 512, ROWS_WAVES = ROWS_THREADS / 64, ROWS_CHUNK = 128;
 struct GemvRowsArgs {
     const void* x;
@@ -764,12 +772,12 @@ template <> struct RowsMfma<f16_t> {
     }
 };
 
-template <typename T, bool NF4, int RT>
+template <typename T, bool NF4, int RT, int MT>
 __global__ void __launch_bounds__(ROWS_THREADS) gemv_rows_kernel(GemvRowsArgs p) {
     typedef typename RowsMfma<T>::frag frag;
     constexpr int WV = NF4 ? 1 : 4;                  // 16-byte weight loads per lane, tile and chunk
     extern __shared__ __attribute__((aligned(16))) unsigned char rows_smem[];
-    // layout: code2 [256] float | lut2 [256][32] u32 (NF4); after the K loop the partial tiles [8][RT][64] x 16 bytes from 0
+    // layout: code2 [256] float | lut2 [256][32] u32 (NF4); after the K loop the partial tiles [8][RT][MT][64] x 16 bytes from 0
     float* code2 = reinterpret_cast<float*>(rows_smem);
     uint32_t* lut2 = reinterpret_cast<uint32_t*>(rows_smem + 1024);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -792,9 +800,14 @@ __global__ void __launch_bounds__(ROWS_THREADS) gemv_rows_kernel(GemvRowsArgs p)
         for (int c = 0; c < 8; ++c) dst[c] = make_uint4(v, v, v, v);
     }
     // a lane's rows: weight row n0 + 16 t + r of tile t (past the group's end: its last row again, never stored) and token row
-    // r (rows >= M: row 0's address, the fragment zeroed -- such rows are not read)
-    const bool mok = r < M;
-    const T* const xrow = (const T*)p.x + (int64_t)(mok ? r : 0) * p.ldx;
+    // 16 u + r of token tile u (rows >= M: row 0's address, the fragment zeroed -- such rows are not read)
+    bool mok[MT];
+    const T* xrow[MT];
+#pragma unroll
+    for (int u = 0; u < MT; ++u) {
+        mok[u] = 16 * u + r < M;
+        xrow[u] = (const T*)p.x + (int64_t)(mok[u] ? 16 * u + r : 0) * p.ldx;
+    }
     int64_t wrow[RT];                                // NF4: first code of the row; dense: first element
 #pragma unroll
     for (int t = 0; t < RT; ++t) {
@@ -813,13 +826,28 @@ __global__ void __launch_bounds__(ROWS_THREADS) gemv_rows_kernel(GemvRowsArgs p)
         uint4 w[RT][WV];
         uint32_t a8[RT];
         float a2[RT];
-        uint4 x[4];
+        uint4 x[4];                                  // (MT = 1 only)
+    };
+    // The token fragments of a chunk. One token tile: they travel with the chunk's weights, a stage ahead. More tiles: 16 MT
+    // registers a stage are not to be had twice, so ONE set is loaded (from L2: all workgroups read the same X) right before
+    // the next stage's weights are requested -- the wait for it leaves those in flight -- and serves the RT weight tiles.
+    struct XFrags { uint4 x[MT][4]; };
+    auto load_x = [&](XFrags& f, int c) {
+#pragma unroll
+        for (int u = 0; u < MT; ++u)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int col = col_of(c, j);
+                f.x[u][j] = *reinterpret_cast<const uint4*>(xrow[u] + (col < K ? col : 0));
+            }
     };
     auto load = [&](Stage& s, int c) {
+        if constexpr (MT == 1) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int col = col_of(c, j);
-            s.x[j] = *reinterpret_cast<const uint4*>(xrow + (col < K ? col : 0));
+            for (int j = 0; j < 4; ++j) {
+                const int col = col_of(c, j);
+                s.x[j] = *reinterpret_cast<const uint4*>(xrow[0] + (col < K ? col : 0));
+            }
         }
 #pragma unroll
         for (int t = 0; t < RT; ++t) {
@@ -845,18 +873,26 @@ __global__ void __launch_bounds__(ROWS_THREADS) gemv_rows_kernel(GemvRowsArgs p)
             }
         }
     };
-    rows_f32x4 acc[RT];
+    rows_f32x4 acc[RT][MT];
 #pragma unroll
-    for (int t = 0; t < RT; ++t) acc[t] = rows_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int u = 0; u < MT; ++u) acc[t][u] = rows_f32x4{0.f, 0.f, 0.f, 0.f};
     const uint32_t* const lut_lane = lut2 + (lane & 31);
     union F { uint4 u; uint32_t w[4]; frag f; };
+    XFrags xf;                                       // (MT > 1)
     auto compute = [&](const Stage& s, int c) {
-        F xb[4];
+        F xb[MT][4];
         bool in[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             in[j] = col_of(c, j) < K;
-            xb[j].u = (mok && in[j]) ? s.x[j] : make_uint4(0, 0, 0, 0);
+            if constexpr (MT == 1) {
+                xb[0][j].u = (mok[0] && in[j]) ? s.x[j] : make_uint4(0, 0, 0, 0);
+            } else {
+#pragma unroll
+                for (int u = 0; u < MT; ++u) xb[u][j].u = (mok[u] && in[j]) ? xf.x[u][j] : make_uint4(0, 0, 0, 0);
+            }
         }
 #pragma unroll
         for (int t = 0; t < RT; ++t) {
@@ -877,14 +913,16 @@ __global__ void __launch_bounds__(ROWS_THREADS) gemv_rows_kernel(GemvRowsArgs p)
                         const uint32_t pr = dec[4 * j + b];
                         a.w[b] = pack2<T>(bits16_to_f32<T>(pr & 0xffffu) * am, bits16_to_f32<T>(pr >> 16) * am);
                     }
-                    acc[t] = RowsMfma<T>::run(a.f, xb[j].f, acc[t]);
+#pragma unroll
+                    for (int u = 0; u < MT; ++u) acc[t][u] = RowsMfma<T>::run(a.f, xb[u][j].f, acc[t][u]);
                 }
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     F a;                                     // columns past K: zero (the bits read there may be a NaN's)
                     a.u = in[j] ? s.w[t][j] : make_uint4(0, 0, 0, 0);
-                    acc[t] = RowsMfma<T>::run(a.f, xb[j].f, acc[t]);
+#pragma unroll
+                    for (int u = 0; u < MT; ++u) acc[t][u] = RowsMfma<T>::run(a.f, xb[u][j].f, acc[t][u]);
                 }
             }
         }
@@ -895,9 +933,11 @@ __global__ void __launch_bounds__(ROWS_THREADS) gemv_rows_kernel(GemvRowsArgs p)
     if (NF4) __syncthreads();                        // the tables
     for (; c < nch; c += 2 * ROWS_WAVES) {
         const bool more = c + ROWS_WAVES < nch;
+        if constexpr (MT > 1) load_x(xf, c);
         if (more) load(s1, c + ROWS_WAVES);
         compute(s0, c);
         if (more) {
+            if constexpr (MT > 1) load_x(xf, c + ROWS_WAVES);
             if (c + 2 * ROWS_WAVES < nch) load(s0, c + 2 * ROWS_WAVES);
             compute(s1, c + ROWS_WAVES);
         }
@@ -906,18 +946,21 @@ __global__ void __launch_bounds__(ROWS_THREADS) gemv_rows_kernel(GemvRowsArgs p)
     __syncthreads();                                 // (the tables are dead)
     rows_f32x4* red = reinterpret_cast<rows_f32x4*>(rows_smem);
 #pragma unroll
-    for (int t = 0; t < RT; ++t) red[(wave * RT + t) * 64 + lane] = acc[t];
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int u = 0; u < MT; ++u) red[((wave * RT + t) * MT + u) * 64 + lane] = acc[t][u];
     __syncthreads();
     const float* redf = reinterpret_cast<const float*>(rows_smem);
     const int R = g.lora_b ? g.R : 0;
-    for (int o = tid; o < RT * 256; o += ROWS_THREADS) {
-        const int nl = o & 15, m = (o >> 4) & 15, t = o >> 8;
-        const int n = n0 + 16 * t + nl;
+    for (int o = tid; o < RT * MT * 256; o += ROWS_THREADS) {
+        const int nl = o & 15, mc = (o >> 4) & 15, tu = o >> 8;      // tu = t * MT + u
+        const int m = 16 * (tu % MT) + mc;
+        const int n = n0 + 16 * (tu / MT) + nl;
         if (m >= M || n >= N) continue;
-        const int src = ((nl >> 2) * 16 + m) * 4 + (nl & 3);        // D[row nl][col m]: lane (nl / 4) * 16 + m, register nl % 4
+        const int src = ((nl >> 2) * 16 + mc) * 4 + (nl & 3);       // D[row nl][col mc]: lane (nl / 4) * 16 + mc, register nl % 4
         float v = 0.f;
 #pragma unroll
-        for (int w = 0; w < ROWS_WAVES; ++w) v += redf[(w * RT + t) * 256 + src];
+        for (int w = 0; w < ROWS_WAVES; ++w) v += redf[(w * RT * MT + tu) * 256 + src];
         if (R > 0) {
             const float* tv = g.lora_t + (int64_t)m * p.ldt;
             float l = 0.f;
@@ -936,7 +979,7 @@ __global__ void __launch_bounds__(ROWS_THREADS) gemv_rows_kernel(GemvRowsArgs p)
     }
 }
 
-template <typename T, bool NF4, int RT>
+template <typename T, bool NF4, int RT, int MT = 1>
 int launch_gemv_rows_rt(GemvRowsArgs a, hipStream_t st) {
     int blocks = 0;
     for (int i = 0; i < UAMD_GEMV_MAX_GROUPS; ++i) {
@@ -944,11 +987,11 @@ int launch_gemv_rows_rt(GemvRowsArgs a, hipStream_t st) {
         if (i < a.n_groups) blocks += (a.g[i].N + 16 * RT - 1) / (16 * RT);
     }
     a.blk_start[UAMD_GEMV_MAX_GROUPS] = blocks;
-    const int tables = NF4 ? 1024 + 256 * 32 * 4 : 0, red = ROWS_WAVES * RT * 64 * 16;
+    const int tables = NF4 ? 1024 + 256 * 32 * 4 : 0, red = ROWS_WAVES * RT * MT * 64 * 16;
     const int lds = tables > red ? tables : red;
     if (lds > 48 * 1024)
-        if (int rc = uamd_lds_optin<&gemv_rows_kernel<T, NF4, RT>>(lds)) return rc;
-    hipLaunchKernelGGL((gemv_rows_kernel<T, NF4, RT>), dim3(blocks), dim3(ROWS_THREADS), lds, st, a);
+        if (int rc = uamd_lds_optin<&gemv_rows_kernel<T, NF4, RT, MT>>(lds)) return rc;
+    hipLaunchKernelGGL((gemv_rows_kernel<T, NF4, RT, MT>), dim3(blocks), dim3(ROWS_THREADS), lds, st, a);
     return uamd_launch_status();
 }
 
@@ -963,6 +1006,30 @@ int launch_gemv_rows(const GemvRowsArgs& a, hipStream_t st) {
     }
     if (tiles >= 2 * want) return launch_gemv_rows_rt<T, NF4, 2>(a, st);
     return launch_gemv_rows_rt<T, NF4, 1>(a, st);
+}
+
+// 17 .. 64 token rows: MT = 2 (M <= 32) or 4 token tiles against every decoded weight fragment. A workgroup reads all of X
+// (from L2) beside 16 RT weight rows -- M / (4 RT) bytes of X per NF4 byte -- so RT depends on MT as well as on the tile count.
+// Measured on the Llama-3-8B projections with RT forced ("RT by MT"; us per launch at M = 64, RT = 1 / 2 / 4):
+// q|k|v (384 tiles) 71.5 / 65.6 / 87.6, o (256) 49.5 / 61.8 / 83.3, gate|up (1792) 192 / 177 / 147, down (256, K = 14336)
+// 135 / 156 / 191 -- MT = 4 takes the larger RT down to 192 workgroups (3/4 of the CUs) and loses below (128, 96). At M = 32
+// the same table is flat within 2 % between the rule of the narrow launches (two workgroups per CU) and its neighbours, and
+// worse beyond them: MT = 2 keeps that rule.
+template <typename T, bool NF4, int MT>
+int launch_gemv_rows_mt(const GemvRowsArgs& a, hipStream_t st) {
+    int tiles = 0;
+    for (int i = 0; i < a.n_groups; ++i) tiles += (a.g[i].N + 15) / 16;
+    const int want = MT == 2 ? 2 * uamd_cu_count_or_256() : 3 * uamd_cu_count_or_256() / 4;
+    if constexpr (NF4) {
+        if (tiles >= 4 * want) return launch_gemv_rows_rt<T, true, 4, MT>(a, st);
+    }
+    if (tiles >= 2 * want) return launch_gemv_rows_rt<T, NF4, 2, MT>(a, st);
+    return launch_gemv_rows_rt<T, NF4, 1, MT>(a, st);
+}
+template <typename T, bool NF4>
+int launch_gemv_rows_wide(const GemvRowsArgs& a, hipStream_t st) {
+    if (a.M <= 16) return launch_gemv_rows<T, NF4>(a, st);
+    return a.M <= 32 ? launch_gemv_rows_mt<T, NF4, 2>(a, st) : launch_gemv_rows_mt<T, NF4, 4>(a, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1986,9 +2053,9 @@ extern "C" int uamd_gemv_fused(const void* x, int K, const uamd_gemv_group* grou
 // Y_g[m, n] = W_g[n, :] . X[m, :] (+ s_g * B_g[n, :] . T_g[m, :] + bias_g[n]) for M = 1 .. 16 token rows in ONE pass over the
 // weights: the decode step of a batch (gemv_rows_kernel). The groups are uamd_gemv's; every group's y and lora_t address
 // rows of stride ldy / ldt.
-extern "C" int uamd_gemv_rows(const void* x, int64_t ldx, int M, int K, const uamd_gemv_group* groups, int n_groups,
-                              int64_t ldy, int64_t ldt, int nf4, int blocksize, int dtype, void* stream) {
-    if (!x || !groups || n_groups < 1 || n_groups > UAMD_GEMV_MAX_GROUPS || M < 1 || M > 16 || K <= 0 || K > 16384 || ldx < K ||
+static int gemv_rows_entry(const void* x, int64_t ldx, int M, int max_m, int K, const uamd_gemv_group* groups, int n_groups,
+                           int64_t ldy, int64_t ldt, int nf4, int blocksize, int dtype, void* stream) {
+    if (!x || !groups || n_groups < 1 || n_groups > UAMD_GEMV_MAX_GROUPS || M < 1 || M > max_m || K <= 0 || K > 16384 || ldx < K ||
         ldy < 1 || ldt < 0)
         return UAMD_ERR_ARG;
     if (nf4 && (blocksize < 32 || (blocksize & 31) || (K & 31))) return UAMD_ERR_ARG;
@@ -2016,8 +2083,18 @@ extern "C" int uamd_gemv_rows(const void* x, int64_t ldx, int M, int K, const ua
         if (!g.lora_t) g.lora_b = nullptr;            // (a B without a t: no LoRA term)
     }
     hipStream_t st = (hipStream_t)stream;
-    UAMD_DISPATCH_HALF(dtype, return nf4 ? launch_gemv_rows<T, true>(a, st) : launch_gemv_rows<T, false>(a, st))
+    UAMD_DISPATCH_HALF(dtype, return nf4 ? launch_gemv_rows_wide<T, true>(a, st) : launch_gemv_rows_wide<T, false>(a, st))
     return UAMD_ERR_DTYPE;
+}
+extern "C" int uamd_gemv_rows(const void* x, int64_t ldx, int M, int K, const uamd_gemv_group* groups, int n_groups,
+                              int64_t ldy, int64_t ldt, int nf4, int blocksize, int dtype, void* stream) {
+    return gemv_rows_entry(x, ldx, M, 16, K, groups, n_groups, ldy, ldt, nf4, blocksize, dtype, stream);
+}
+// The same for M = 1 .. 64 (17 and up: the kernel's MT = 2 | 4 token-tile instances; M <= 16: uamd_gemv_rows' launch). Y[m, n]
+// is bit for bit what uamd_gemv_rows stores for that token row and weight row.
+extern "C" int uamd_gemv_rows64(const void* x, int64_t ldx, int M, int K, const uamd_gemv_group* groups, int n_groups,
+                                int64_t ldy, int64_t ldt, int nf4, int blocksize, int dtype, void* stream) {
+    return gemv_rows_entry(x, ldx, M, 64, K, groups, n_groups, ldy, ldt, nf4, blocksize, dtype, stream);
 }
 
 // RoPE on the new token's q, k (in place in the fused qkv row) + append of k, v at cache position kv_len[b]

@@ -3,8 +3,9 @@
 `fast_gemv` / the bsz == 1 branch of `fast_linear_forward` (utils.py:872-977, :1082-1125) become ONE `uamd_gemv`
 launch per group of projections that share the token (q|k|v, gate|up), plus one small `uamd_gemv` over the LoRA A rows
 that share it. NF4 weights are read in bitsandbytes' format straight from the `Params4bit` storage: nothing is
-dequantised to memory. The token rows of a batch of 2 .. 16 sequences share one pass over the weights: `uamd_gemv_rows`
-(`gemv_rows`, `linear_group_rows`), where utils.py:1095-1097 dequantises and calls matmul.
+dequantised to memory. The token rows of a batch of 2 .. 64 sequences share one pass over the weights: `uamd_gemv_rows`
+up to 16 rows, `uamd_gemv_rows64` above (`gemv_rows`, `gemv_rows64`, `linear_group_rows`), where utils.py:1095-1097
+dequantises and calls matmul.
 """
 import ctypes
 
@@ -230,6 +231,7 @@ def linear_group(x, projs, out=None, fused=None):
 
 
 MAX_ROWS = 16                         # token rows of one uamd_gemv_rows launch
+MAX_ROWS_WIDE = 64                    # token rows of one uamd_gemv_rows64 launch
 
 
 def gemv_rows(x, groups, nf4, blocksize=64, M=None):
@@ -237,6 +239,16 @@ def gemv_rows(x, groups, nf4, blocksize=64, M=None):
     groups of `gemv`. A group's `y` is an [M, N] view whose rows may be strided (all groups of a launch share the row stride:
     adjacent column ranges of one buffer) and is allocated when absent; `lora_t` is fp32 [M, R] (a column range of the t
     buffer, one row stride for all groups). `M` < x.shape[0] launches the first M rows only. Returns the outputs."""
+    return _rows_launch("uamd_gemv_rows", x, groups, nf4, blocksize, M)
+
+
+def gemv_rows64(x, groups, nf4, blocksize=64, M=None):
+    """`gemv_rows` for M <= 64 token rows: one uamd_gemv_rows64 launch, still one pass over the weights. Every output row has
+    the bits `gemv_rows` gives that token row (a 64-row launch equals four 16-row launches on its slices)."""
+    return _rows_launch("uamd_gemv_rows64", x, groups, nf4, blocksize, M)
+
+
+def _rows_launch(symbol, x, groups, nf4, blocksize, M):
     _lib.require_gpu(x)
     assert x.dim() == 2 and x.stride(1) == 1
     M = x.shape[0] if M is None else int(M)
@@ -283,19 +295,21 @@ def gemv_rows(x, groups, nf4, blocksize=64, M=None):
         bias = g.get("bias")
         e.bias = bias.data_ptr() if bias is not None else None
         e.N, e.y_f32 = N, int(y_f32)
-    _lib.call("uamd_gemv_rows", x, _lib.ptr(x), x.stride(0) if M > 1 else K, M, K, arr, len(groups),
+    _lib.call(symbol, x, _lib.ptr(x), x.stride(0) if M > 1 else K, M, K, arr, len(groups),
               int(ldy), int(ldt), int(bool(nf4)), int(blocksize), _lib.dtype_code(dtype), _lib.stream_of(x))
     return outs
 
 
 def linear_group_rows(x2d, projs, out=None, y_f32=False, t_buf=None):
-    """`linear_group` for M = 1 .. 16 token rows x2d [M, K] that share one pass over the weights (uamd_gemv_rows): at most two
+    """`linear_group` for M = 1 .. 64 token rows x2d [M, K] that share one pass over the weights (uamd_gemv_rows up to 16 rows,
+    uamd_gemv_rows64 above; the same bits per row either way): at most two
     launches per four projections (the stacked A rows of all members -> t fp32 [M, sum R], then the weights). `out`: an
     [M, sum N_i] buffer (rows may be strided) the outputs are written into side by side -- q|k|v land in the fused row with no
     concatenation; `t_buf`: an fp32 [M, >= sum R] buffer to reuse under a hipGraph. Returns the [M, N_i] views. The value of a
     row depends on that row and the weights alone (the kernel's row-independence contract)."""
-    assert x2d.dim() == 2 and 1 <= x2d.shape[0] <= MAX_ROWS
+    assert x2d.dim() == 2 and 1 <= x2d.shape[0] <= MAX_ROWS_WIDE
     M, dtype = x2d.shape[0], x2d.dtype
+    launch = gemv_rows if M <= MAX_ROWS else gemv_rows64
     nf4 = projs[0][1] is not None
     assert all((p[1] is not None) == nf4 for p in projs), "a launch is all-NF4 or all-16-bit"
     Ns = [int(p[1].shape[0]) if p[1] is not None else int(p[0].shape[0]) for p in projs]
@@ -308,7 +322,7 @@ def linear_group_rows(x2d, projs, out=None, y_f32=False, t_buf=None):
         A_rows = lora_a_rows([p[2] for p in with_lora], dtype)
         Rt = A_rows.shape[0]
         t_all = t_buf[:M, :Rt] if t_buf is not None else torch.empty(M, Rt, dtype=torch.float32, device=x2d.device)
-        gemv_rows(x2d, [dict(W=A_rows, N=Rt, y=t_all, y_f32=True)], nf4=False)
+        launch(x2d, [dict(W=A_rows, N=Rt, y=t_all, y_f32=True)], nf4=False)
     groups, col, r0 = [], 0, 0
     for p, N in zip(projs, Ns):
         W, qs, A, B, s = p[:5]
@@ -322,7 +336,7 @@ def linear_group_rows(x2d, projs, out=None, y_f32=False, t_buf=None):
     blocksize = int(projs[0][1].blocksize) if nf4 else 64
     ys = []
     for i in range(0, len(groups), MAX_GROUPS):
-        ys += gemv_rows(x2d, groups[i:i + MAX_GROUPS], nf4=nf4, blocksize=blocksize)
+        ys += launch(x2d, groups[i:i + MAX_GROUPS], nf4=nf4, blocksize=blocksize)
     return ys
 
 

@@ -15,8 +15,8 @@ MI355X design: one `DecodeEngine` per (model, max_seq_len, batch):
     once as a hipGraph and replayed per token. (Rounds 2-3: 14 launches per layer, ~450 kernels
     of ~9 us for ~0.6 ms of HBM traffic; still the batch > 1 path and `UNSLOTH_AMD_DECODE_FUSED=0`.);
   * prefill runs the training-path kernels (flash attention over the prompt) and writes K (post-RoPE) / V into the cache.
-Batches of 2 .. 16 sequences run the 14-launch step with every linear on uamd_gemv_rows -- ONE pass over the weights for all
-token rows, LoRA term and bias inside the launch, q|k|v written straight into the fused row -- captured and replayed as a
+Batches of 2 .. 64 sequences run the 14-launch step with every linear on uamd_gemv_rows (17 rows and up: uamd_gemv_rows64, the
+same bits per row) -- ONE pass over the weights for all token rows, LoRA term and bias inside the launch, q|k|v written straight into the fused row -- captured and replayed as a
 hipGraph like the single-sequence step (`BATCH_ROWS`); a row's logits do not depend on its companions. Larger batches decode
 through the fused NF4 GEMM (as the reference does, utils.py:1095-1097), eager. Prompts of different lengths arrive LEFT-padded
 with their attention_mask: prefill treats the padding as documents, counts RoPE positions from each row's first real token
@@ -53,10 +53,10 @@ def _base(model):
 # launch and handed over through a device workspace, RoPE / append / combine ride in the attention launch and SwiGLU in the
 # gate|up epilogue.)
 FUSED_STEP = True
-# Batches of 2 .. 16 sequences: every linear of the token step through uamd_gemv_rows (one pass over the weights for all rows,
-# LoRA term and bias inside the launch) and the step captured as a hipGraph, against the 128 x 128-tile NF4 GEMM + separate
+# Batches of 2 .. 64 sequences: every linear of the token step through uamd_gemv_rows / uamd_gemv_rows64 (one pass over the
+# weights for all rows, LoRA term and bias inside the launch) and the step captured as a hipGraph, against the 128 x 128-tile NF4 GEMM + separate
 # LoRA / bias launches, eager (False: the route of every larger batch). Read when an engine is built; only tests and
-# tools/decode_batch_bench.py flip it (profiles/decode_batch_bench.jsonl is the A/B).
+# tools/decode_batch_bench.py flip it (profiles/decode_batch_bench.jsonl and decode_batch64_bench.jsonl are the A/B).
 BATCH_ROWS = True
 
 
@@ -108,7 +108,7 @@ class DecodeEngine:
             raise NotImplementedError("decode path: SwiGLU MLP only")
         self.window = int(getattr(cfg, "sliding_window", None) or 0)
         self.scale = 1.0 / math.sqrt(self.D)
-        self.rows = bool(BATCH_ROWS) and 2 <= batch <= _dk.MAX_ROWS      # the batched step on uamd_gemv_rows
+        self.rows = bool(BATCH_ROWS) and 2 <= batch <= _dk.MAX_ROWS_WIDE      # the batched step on uamd_gemv_rows / _rows64
         self.use_graph = bool(use_graph) and (batch == 1 or self.rows)
         L = len(self.core.layers)
         # "fp8": the caches hold e4m3 codes (uint8) and one fp32 scale per (sequence, KV head, position) beside them -- (D + 4) /
@@ -334,7 +334,8 @@ class DecodeEngine:
             (y,) = _dk.gemv(x.reshape(-1), [dict(W=W, N=W.shape[0], y_f32=True)], nf4=False)
             return y.view(1, -1)
         if self.rows and W.dtype == x.dtype and W.shape[1] <= 16384:
-            (y,) = _dk.gemv_rows(x, [dict(W=W, N=W.shape[0], y_f32=True)], nf4=False)
+            launch = _dk.gemv_rows if self.B <= _dk.MAX_ROWS else _dk.gemv_rows64
+            (y,) = launch(x, [dict(W=W, N=W.shape[0], y_f32=True)], nf4=False)
             return y
         return (x @ W.t().to(x.dtype)).float()
 
