@@ -551,6 +551,57 @@ int uamd_attn_decode_shared(const void* q, int64_t q_sb, const void* pk, const v
                             const int* new_len, int len_add, float* partials, void* out, int64_t out_sb, int P, int Hq, int Hk,
                             int D, int nsplit_prompt, int nsplit_new, int split_keys, int window, float scale, int dtype,
                             void* stream);
+/* ---- a span of R new tokens per sequence in ONE step: prompt-lookup drafts verified on one pass over the weights ------------
+ * (DecodeEngine.generate(prompt_lookup_num_tokens=K): R = K + 1 token rows -- the last token and K drafts taken from the
+ * sequence's own context -- go through uamd_gemv_rows, the two span kernels below, an R-row arg-max and uamd_accept_greedy.)
+ *
+ * uamd_rope_kv_append for R tokens per sequence: qkv [B * R, (Hq + 2 Hk) D], row b * R + j is the j-th new token of sequence b;
+ * its RoPE position and its cache slot are kv_len[b] + j (kv_len: DEVICE, not advanced here). The arithmetic and the rounding
+ * points are uamd_rope_kv_append's (fp32 products each rounded to the activation type, their sum rounded once; v copied): q, k
+ * and the cache rows are bit-identical to R successive calls of it with kv_len advanced by one in between. A slot >= s_max is
+ * not written. Any even D. */
+int uamd_rope_kv_append_span(void* qkv, int64_t ld_qkv, const void* cos_t, const void* sin_t, int64_t ld_cs, const int* kv_len,
+                             void* k_cache, void* v_cache, int64_t cache_sb, int64_t cache_sh, int B, int R, int Hq, int Hk,
+                             int D, int s_max, int dtype, void* stream);
+/* uamd_attn_decode for the R tokens uamd_rope_kv_append_span has just appended to every sequence: q [B * R, Hq * D] (row stride
+ * q_sb), out [B * R, Hq * D] (row stride out_sb), partials fp32 [B * R, Hq, nsplit, D + 2]. Row (b, j, head h) attends keys
+ * [max(0, t_j - window), t_j) of sequence b's cache, t_j = kv_len[b] + j + 1 (window 0: all): everything before the span and a
+ * causal triangle over the span's own keys. The cache holds at least kv_len[b] + R <= nsplit * split_keys keys.
+ * Refused with UAMD_ERR_ARG before any launch: R < 1, R > 16, R * Hq / Hk > 128, D not 64 or 128, a split_keys that
+ * uamd_attn_decode refuses. bf16 / fp16. Two plain launches on `stream`:
+ *   1. span scan, grid (nsplit, Hk, B): the online-softmax partials of the R * Hq / Hk query rows of (b, kv head) over the
+ *      split's keys from ONE fetch of them, scores and P V on v_mfma_f32_16x16x32 with the rows in 16-row tiles, as the prefix
+ *      scan of uamd_attn_decode_shared does. Roundings, the same as there: fp32 accumulation of the exact 16-bit products
+ *      q_j k_j, times scale * log2 e in fp32; running max and sum in fp32 (exp2 domain); P = exp2(s - m) rounded ONCE to `dtype`
+ *      and the sum taken over the rounded P (all the mass on one key returns that V row exactly); P V accumulated in fp32. A
+ *      score outside the row's key range is -inf by selection; a V value outside it is masked to zero bits before the product
+ *      wherever the rows of a tile disagree about a 32-key group, so 0 * NaN never forms.
+ *   2. uamd_attn_decode's combine over all slots, one rounding at the store of `out`.
+ * A row without a key in a split enters the combine as (m, l) = (-inf, 0), o = 0. At a fixed (R, Hq / Hk, nsplit, split_keys,
+ * window) a row's output is a fixed sequence of operations on its own query, kv_len[b], j and the keys of its range: bitwise
+ * independent of the other rows' queries, of the keys at or past t_j (NaN included) and of the slots past kv_len[b] + R, which
+ * are never read. */
+int uamd_attn_decode_span(const void* q, int64_t q_sb, const void* k_cache, const void* v_cache, int64_t cache_sb,
+                          int64_t cache_sh, const int* kv_len, int R, float* partials, void* out, int64_t out_sb, int B, int Hq,
+                          int Hk, int D, int nsplit, int split_keys, int window, float scale, int dtype, void* stream);
+/* The draft: K tokens that followed an earlier occurrence of the sequence's last n-gram in its own context (what HF's
+ * `prompt_lookup_num_tokens` proposes). hist: int64 [cap] and hist_len: int32 [1], both on the DEVICE; len = min(*hist_len, cap).
+ * For n = min(n_max, len - 1) .. 1, with suffix = hist[len - n, len): among the starts i with i + n <= len - 1 and
+ * hist[i, i + n) == suffix the LARGEST wins; the first n that has such a start wins. (HF takes the first match; the rule changes
+ * how often drafts hit, never the text.) draft = hist[i + n, min(i + n + K, len)), *n_draft = its length, 0 without a match.
+ * Written: tok[0] = hist[len - 1], tok[1 .. n_draft] = the draft, tok[n_draft + 1 .. K] = 0 (verified like drafts: an
+ * accidental hit is a correct token). 1 <= K <= 15, n_max >= 1. One workgroup, integer compares only. */
+int uamd_ngram_draft(const int64_t* hist, const int* hist_len, int cap, int n_max, int K, int64_t* tok, int* n_draft,
+                     void* stream);
+/* The verdict of a greedy verify step, everything on the DEVICE: tok int64 [K + 1] the step's token rows, amax int64 [K + 1] the
+ * arg-max of each row's logits (amax[j]: the model's token after tok[0 .. j]), eos int64 [n_eos <= 8].
+ * m = the number of leading j = 1 .. K with tok[j] == amax[j - 1]; counting stops behind an amax[j - 1] that is an eos id, and m
+ * + 1 <= *remaining (and hist_len + m + 1 <= cap). Then hist[*hist_len + j] = amax[j] for j = 0 .. m; *hist_len, *kv_len += m + 1;
+ * *remaining -= m + 1; *done = 1 when an eos was emitted or *remaining reached 0; stats int64 [4] += (1, *n_draft, m, m + 1) =
+ * (steps, drafted, accepted, tokens). The K / V rows of rejected drafts stay behind *kv_len and are overwritten by later
+ * appends. A call with *done set or *remaining <= 0 changes nothing (but sets *done). 0 <= K <= 15. One wave, integers only. */
+int uamd_accept_greedy(const int64_t* tok, const int64_t* amax, int K, const int64_t* eos, int n_eos, int64_t* hist, int cap,
+                       int* hist_len, int* kv_len, int* remaining, int* done, const int* n_draft, int64_t* stats, void* stream);
 /* ---- FP8 KV cache (opt-in: DecodeEngine(kv_cache_dtype="fp8")) -- THE definition of the stored format --------------------
  * A cache row is one (sequence, KV head, position) vector of D elements, D = 64 or 128. It is stored as D bytes of OCP e4m3fn
  * codes in `codes` [B, Hk, s_max, D] (uint8; strides cache_sb, cache_sh, D, 1) and ONE fp32 scale in `scales` [B, Hk, s_max]

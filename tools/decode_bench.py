@@ -4,6 +4,7 @@
 
     python tools/decode_bench.py [--shape llama3-8b] [--layers 32] [--context 2048] [--new 64] [--out decode.jsonl]
     python tools/decode_bench.py --sampler [--out sampler.jsonl]     the device sampler: launch and sampled step
+    python tools/decode_bench.py --lookup [--out lookup.jsonl]       prompt-lookup verify replays (K = 2, 4, 8, 15) against the plain step
 """
 import argparse
 import json
@@ -121,6 +122,53 @@ def sampled_step_ab(eng, emit, steps, rounds=5, T=0.8, top_k=50, top_p=0.9, min_
               greedy_ms=g, sampled_ms=s, sampled_minus_greedy_us=round((s["median"] - g["median"]) * 1e3, 1)))
 
 
+def lookup_ab(eng, emit, context, steps, rounds=5, Ks=(2, 4, 8, 15), n_max=2):
+    """ms per verify replay of prompt-lookup decoding (K drafts: K + 1 token rows on one pass over the weights) against ms per
+    plain fused step, every one a replayed hipGraph of ONE engine, rounds interleaved in one process; every round starts at the
+    same cache length. The prompt is random tokens, so hardly a draft is found or accepted and the context stays where it
+    started; what a verify step costs does not depend on how many drafts it keeps (rejected rows ran all the same). From the
+    costs: the accepted drafts per step at which a verify step breaks even with plain steps, t_K / t_plain - 1, and the
+    tokens/s ceiling when every draft is accepted, (K + 1) / t_K."""
+    lk = eng._lookup_state()
+    kv0 = eng.kv_len.clone()
+    st0 = torch.tensor([int(kv0[0]) + 1, 1 << 30, 0, 0], dtype=torch.int32, device=eng.dev)
+    lk["hist"][int(kv0[0])] = 1
+    tok = torch.zeros(1, dtype=torch.long, device=eng.dev)
+    ms = {k: [] for k in ("plain",) + tuple(Ks)}
+    accepted = {k: 0 for k in Ks}
+    for r in range(rounds + 1):                          # round 0 captures and warms every graph
+        for mode in ms:
+            eng.kv_len.copy_(kv0)
+            if mode == "plain":
+                eng.step(tok)
+                run = lambda: eng.step(eng.next_tok)
+            else:
+                lk["state"].copy_(st0)
+                lk["stats"].zero_()
+                eng._lookup_step(mode + 1, n_max)
+                run = lambda: eng._lookup_step(mode + 1, n_max)
+            torch.cuda.synchronize()
+            t0 = time.time()
+            for _ in range(steps):
+                run()
+            torch.cuda.synchronize()
+            if r:
+                ms[mode].append((time.time() - t0) / steps * 1e3)
+                if mode != "plain":
+                    accepted[mode] += int(lk["stats"][2])
+    plain = _spread(ms["plain"])
+    emit(dict(metric="decode ms per step: plain fused step, hipGraph, batch 1", layers=len(eng.core.layers), context=context,
+              steps=steps, rounds=rounds, ms=plain, tokens_per_s=round(1e3 / plain["median"], 1)))
+    for K in Ks:
+        v = _spread(ms[K])
+        emit(dict(metric="decode ms per verify replay (prompt lookup), hipGraph, batch 1", K=K, rows=K + 1,
+                  layers=len(eng.core.layers), context=context, steps=steps, rounds=rounds, ms=v, plain_ms=plain,
+                  ratio_to_plain=round(v["median"] / plain["median"], 3),
+                  break_even_accepted_per_step=round(v["median"] / plain["median"] - 1.0, 3),
+                  tokens_per_s_ceiling_all_accepted=round((K + 1) * 1e3 / v["median"], 1),
+                  accepted_while_timing=accepted[K], acceptance_on_real_text="not measured"))
+
+
 def whole_model(a, dev):
     """The benchmark's synthetic Llama-shaped QLoRA model (NF4, r = 16 on every projection, random B factors)."""
     import bench as B                                   # the benchmark's synthetic Llama-3-8B-shaped config
@@ -149,6 +197,8 @@ def main():
     ap.add_argument("--attn-ab", action="store_true", help="only the fused attention launch, head_dim 64 against 128")
     ap.add_argument("--sampler", action="store_true",
                     help="only the sampler: its launch against the torch chain, and the sampled against the greedy hipGraph step")
+    ap.add_argument("--lookup", action="store_true",
+                    help="only prompt-lookup decoding: ms per verify replay at K = 2, 4, 8, 15 against the plain fused step")
     a = ap.parse_args()
     H, I, L0, Hq, Hk, Dh, V = SHAPES[a.shape]
     if a.layers is None:
@@ -169,6 +219,14 @@ def main():
         eng = DecodeEngine(whole_model(a, "cuda"), max_seq_len=a.context, batch=1, use_graph=True)
         eng.prefill(torch.randint(0, 32000, (1, a.context - a.new), device="cuda"))
         return sampled_step_ab(eng, emit, steps=a.new - 4)
+    if a.lookup:
+        from unsloth_amd.models.decode import DecodeEngine
+        steps = 40                                      # replays per timed window; room for 16 new keys per replay behind the context
+        eng = DecodeEngine(whole_model(a, "cuda"), max_seq_len=a.context + (steps + 2) * 16, batch=1, use_graph=True)
+        ids = torch.randint(0, 32000, (1, a.context), device="cuda")
+        eng.prefill(ids)
+        eng._lookup_state()["hist"][:a.context].copy_(ids[0])
+        return lookup_ab(eng, emit, a.context, steps)
     from unsloth_amd.kernels import decode as D
     from unsloth_amd.nf4 import quantize_nf4
     dev, bf = "cuda", torch.bfloat16

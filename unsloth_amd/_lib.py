@@ -178,6 +178,14 @@ SIGNATURES = {
     "uamd_attn_decode_shared": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p,
                                         c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int,
                                         c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "uamd_rope_kv_append_span": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                         c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "uamd_attn_decode_span": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p,
+                                      c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+                                      c_void_p]),
+    "uamd_ngram_draft": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "uamd_accept_greedy": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "uamd_kv_store_fp8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
                                   c_int, c_int, c_int, c_void_p]),
     "uamd_rope_kv_append_fp8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,

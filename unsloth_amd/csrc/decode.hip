@@ -1070,6 +1070,36 @@ __global__ void __launch_bounds__(64) rope_append_kernel(T* __restrict__ qkv, in
     }
 }
 
+// uamd_rope_kv_append_span: row b * R + j of qkv is the j-th new token of sequence b -- RoPE position and cache slot
+// kv_len[b] + j, statement for statement the arithmetic of rope_append_kernel, so R successive appends give the same bits. (A
+// body of its own: a device function shared with rope_append_kernel changed that kernel's instruction stream.)
+template <typename T>
+__global__ void __launch_bounds__(64) rope_append_span_kernel(T* __restrict__ qkv, int64_t ld_qkv, const T* __restrict__ cos_t,
+                                                              const T* __restrict__ sin_t, int64_t ld_cs,
+                                                              const int* __restrict__ kv_len, T* __restrict__ kc,
+                                                              T* __restrict__ vc, int64_t c_sb, int64_t c_sh, int R, int Hq,
+                                                              int Hk, int D, int s_max) {
+    const int h = blockIdx.x, row = blockIdx.y;          // h: q heads, then k heads, then v heads of the fused row
+    const int b = row / R;
+    const int half = D >> 1;
+    const int len = kv_len[b] + (row - b * R);
+    T* v = qkv + (int64_t)row * ld_qkv + (int64_t)h * D;
+    if (h < Hq + Hk) {
+        T* kd = (h >= Hq && len < s_max) ? kc + (int64_t)b * c_sb + (int64_t)(h - Hq) * c_sh + (int64_t)len * D : nullptr;
+        for (int j = threadIdx.x; j < half; j += 64) {
+            const float c = to_f32(cos_t[(int64_t)len * ld_cs + j]), s = to_f32(sin_t[(int64_t)len * ld_cs + j]);
+            T r1, r2;
+            rope_pair(to_f32(v[j]), to_f32(v[j + half]), c, s, r1, r2);
+            v[j] = r1;
+            v[j + half] = r2;
+            if (kd) { kd[j] = r1; kd[j + half] = r2; }
+        }
+    } else if (len < s_max) {
+        T* vd = vc + (int64_t)b * c_sb + (int64_t)(h - Hq - Hk) * c_sh + (int64_t)len * D;
+        for (int j = threadIdx.x; j < D; j += 64) vd[j] = v[j];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Split-KV decode attention, head dim DD = 128 or 64. Block (split, kvh, b) = 4 waves; a key is DD / 8 lanes x 16 B, so a
 // wave-load (all 64 lanes, 1 KiB) covers 4 keys at DD = 128 and 8 at DD = 64; every such lane group keeps, for each of the G
@@ -1416,6 +1446,276 @@ __global__ void __launch_bounds__(256) attn_decode_prefix_kernel(const T* __rest
             for (int e = 0; e < 4; ++e) pp[dt * 16 + qq * 4 + e] = o[ti][dt][e];
         if (qq == 0) { pp[DD] = m[ti]; pp[DD + 1] = ll; }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// One fill of the span scan, the prefix scan's statement for statement: keys [c0, c0 + SH_CK) of a (sequence, kv head) cache kb /
+// vb into LDS -- K row-major, V transposed with two keys per word; keys outside [live0, s1) are not loaded and enter as zeros.
+// The caller's barrier follows. (attn_decode_prefix_kernel keeps its own copy: calling this from it changed its instruction
+// stream, and its outputs are pinned bit for bit.)
+template <typename T, int DD>
+__device__ __forceinline__ void shared_fill(T* const Ks, uint32_t* const Vt, const T* const kb, const T* const vb, int c0,
+                                            int live0, int s1, int tid) {
+    constexpr int LPK = DecGeo<DD>::LPK, KROW = SharedGeo<DD>::KROW, VROW = SharedGeo<DD>::VROW;
+    constexpr int KIT = SH_CK * LPK / 256, VIT = KIT / 2;  // 16-byte K loads / V key pairs of a thread per fill
+    uint4 kr[KIT], vr[VIT][2];
+#pragma unroll
+    for (int it = 0; it < KIT; ++it) {
+        const int i = tid + 256 * it, key = c0 + i / LPK, lc = i % LPK;
+        kr[it] = (key >= live0 && key < s1) ? *reinterpret_cast<const uint4*>(kb + (int64_t)key * DD + lc * 8)
+                                            : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int it = 0; it < VIT; ++it) {
+        const int i = tid + 256 * it, key = c0 + 2 * (i / LPK), lc = i % LPK;
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+            vr[it][e] = (key + e >= live0 && key + e < s1)
+                            ? *reinterpret_cast<const uint4*>(vb + (int64_t)(key + e) * DD + lc * 8) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int it = 0; it < KIT; ++it) {
+        const int i = tid + 256 * it;
+        *reinterpret_cast<uint4*>(Ks + (i / LPK) * KROW + (i % LPK) * 8) = kr[it];
+    }
+#pragma unroll
+    for (int it = 0; it < VIT; ++it) {
+        const int i = tid + 256 * it, kp = i / LPK, lc = i % LPK;
+        const uint32_t a[4] = {vr[it][0].x, vr[it][0].y, vr[it][0].z, vr[it][0].w};
+        const uint32_t b[4] = {vr[it][1].x, vr[it][1].y, vr[it][1].z, vr[it][1].w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                  // columns lc * 8 + 2 j, + 1: (even key, odd key) per word
+            Vt[(lc * 8 + 2 * j) * VROW + kp] = (a[j] & 0xffffu) | (b[j] << 16);
+            Vt[(lc * 8 + 2 * j + 1) * VROW + kp] = (a[j] >> 16) | (b[j] & 0xffff0000u);
+        }
+    }
+}
+
+// Span decode attention (uamd_attn_decode_span): sequence b has just appended R tokens at cache slots kv_len[b] .. kv_len[b] +
+// R - 1 (a draft span being verified); its R * G query rows of a kv head -- token j, head g of the group: row j * G + g, q row
+// b * R + j -- are scored against ONE fetch of the cache. Row (j, g) attends keys [max(0, t_j - window), t_j), t_j = kv_len[b] +
+// j + 1: the old cache in full and a causal triangle over the R new keys. The prefix scan's structure throughout -- fills of
+// SH_CK keys (shared_fill), 16-row tiles, wave w owns tiles w and w + 4, S^T and O^T on v_mfma_f32_16x16x32, the same rounding
+// points (P rounded once, the sum over the rounded P) -- with a key range PER ROW:
+//   * a score outside the row's [first, end) is -inf by a select (a NaN key there never enters the row); a row without a key in a
+//     32-key group leaves the group with (m, l, o) unchanged in value: exp2(-inf - mr) = 0 with mr = 0 for an empty row, never
+//     exp2(-inf + inf); a row without a key in the split is stored as (-inf, 0, 0);
+//   * O^T += V^T P^T shares V among the 16 rows of a tile, and 0 * NaN = NaN: a group that is not inside the range of EVERY row
+//     of the tile (the triangle, a window's start) runs the product once per token j of the tile with the V fragment masked to
+//     j's keys -- bit masks, no arithmetic -- and every lane keeps the pass of its own row's token. A row's partial stays a fixed
+//     sequence of operations on its own query, its own range and the cache keys inside it.
+template <typename T, int DD>
+__global__ void __launch_bounds__(256) attn_decode_span_kernel(const T* __restrict__ q, int64_t q_sb, const T* __restrict__ kc,
+                                                               const T* __restrict__ vc, int64_t c_sb, int64_t c_sh,
+                                                               const int* __restrict__ kv_len, float* __restrict__ part, int R,
+                                                               int G, int Hq, int nsplit, int split_keys, int window,
+                                                               float scale_log2) {
+    typedef typename RowsMfma<T>::frag frag;
+    union F { uint4 u; uint2 h[2]; uint32_t w[4]; frag f; };
+    constexpr int KROW = SharedGeo<DD>::KROW, VROW = SharedGeo<DD>::VROW;
+    constexpr int QF = DD / 32, OT = DD / 16;              // Q fragments of a row; 16-column tiles of O^T
+    extern __shared__ __attribute__((aligned(16))) unsigned char sh_smem[];
+    T* const Ks = reinterpret_cast<T*>(sh_smem);
+    uint32_t* const Vt = reinterpret_cast<uint32_t*>(sh_smem + SH_CK * KROW * 2);
+    const int split = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, qq = lane >> 4;
+    const int NR = R * G;
+    const int len0 = kv_len[b];
+    const int first_min = window > 0 ? max(0, len0 + 1 - window) : 0;      // the oldest key any row attends (token 0's)
+    const int s0 = split * split_keys, s1 = min(s0 + split_keys, len0 + R);
+    // the wave's two tiles: lane (r, qq) works for row 16 t + r
+    bool rok[2];
+    int jrow[2], first[2], end[2], jlo[2], jhi[2];
+    int64_t bh[2];
+    F qf[2][QF];
+    float m[2], l[2];
+    rows_f32x4 o[2][OT];
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti) {
+        const int row0 = (wave + 4 * ti) * 16, row = row0 + r;
+        rok[ti] = row < NR;
+        const int j = rok[ti] ? row / G : 0, g = rok[ti] ? row - j * G : 0;
+        jrow[ti] = j;
+        jlo[ti] = min(R - 1, row0 / G);                    // the tokens of the tile's rows (wave-uniform)
+        jhi[ti] = min(R - 1, (row0 + 15) / G);
+        first[ti] = window > 0 ? max(0, len0 + j + 1 - window) : 0;
+        end[ti] = min(len0 + j + 1, s1);
+        bh[ti] = ((int64_t)b * R + j) * Hq + kvh * G + g;
+        const T* qp = q + ((int64_t)b * R + j) * q_sb + (int64_t)(kvh * G + g) * DD + qq * 8;
+#pragma unroll
+        for (int jf = 0; jf < QF; ++jf)
+            qf[ti][jf].u = rok[ti] ? *reinterpret_cast<const uint4*>(qp + jf * 32) : make_uint4(0, 0, 0, 0);
+        m[ti] = -INFINITY; l[ti] = 0.f;
+#pragma unroll
+        for (int dt = 0; dt < OT; ++dt) o[ti][dt] = rows_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const T* const kb = kc + (int64_t)b * c_sb + (int64_t)kvh * c_sh;
+    const T* const vb = vc + (int64_t)b * c_sb + (int64_t)kvh * c_sh;
+    const int live0 = max(s0, first_min);                  // keys [live0, s1) are loaded
+    const int c_first = s0 + (live0 - s0) / SH_CK * SH_CK; // the first fill with a live key (fills start on the split's grid)
+    for (int c0 = c_first; c0 < s1; c0 += SH_CK) {
+        if (c0 != c_first) __syncthreads();                // the previous fill is still being read
+        shared_fill<T, DD>(Ks, Vt, kb, vb, c0, live0, s1, tid);
+        __syncthreads();
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti) {
+            if ((wave + 4 * ti) * 16 >= NR) continue;      // (wave-uniform)
+            const int t_lo = len0 + jlo[ti] + 1;           // the shortest range's end, the latest range's start of the tile
+            const int f_hi = window > 0 ? max(0, len0 + jhi[ti] + 1 - window) : 0;
+            for (int kg = 0; kg < SH_CK / 32; ++kg) {
+                const int k0 = c0 + kg * 32;
+                if (k0 + 32 <= live0 || k0 >= s1) continue;
+                rows_f32x4 sc[2];
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                    sc[hf] = rows_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int jf = 0; jf < QF; ++jf) {
+                        F a;
+                        a.u = *reinterpret_cast<const uint4*>(Ks + (kg * 32 + hf * 16 + r) * KROW + jf * 32 + qq * 8);
+                        sc[hf] = RowsMfma<T>::run(a.f, qf[ti][jf].f, sc[hf]);
+                    }
+                }
+                // lane (row r, qq): keys k0 + 16 hf + 4 qq + e
+                float s[8], mx = -INFINITY;
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int key = k0 + hf * 16 + qq * 4 + e;
+                        s[hf * 4 + e] = (key >= first[ti] && key < end[ti]) ? sc[hf][e] * scale_log2 : -INFINITY;
+                        mx = fmaxf(mx, s[hf * 4 + e]);
+                    }
+                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+                float alpha, unused;
+                softmax_merge(m[ti], l[ti], mx, 0.f, alpha, unused);      // l: the lane's own keys, summed over qq at the end
+                const float mr = m[ti] == -INFINITY ? 0.f : m[ti];
+                float pr[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    pr[e] = round_to<T>(__builtin_amdgcn_exp2f(s[e] - mr));
+                    l[ti] += pr[e];
+                }
+                F pf;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pf.w[e] = pack2<T>(pr[2 * e], pr[2 * e + 1]);
+                // every loaded key of the group inside every row's range: one product for the tile (keys outside [live0, s1) are
+                // zeros in LDS)
+                const bool whole = k0 >= f_hi && min(k0 + 32, s1) <= t_lo;      // (wave-uniform)
+#pragma unroll
+                for (int dt = 0; dt < OT; ++dt) {
+                    F a;                                   // V^T[column 16 dt + r][the lane's 8 keys]
+                    const uint32_t* vp = Vt + (dt * 16 + r) * VROW + kg * 16 + qq * 2;
+                    a.h[0] = *reinterpret_cast<const uint2*>(vp);
+                    a.h[1] = *reinterpret_cast<const uint2*>(vp + 8);
+                    const rows_f32x4 oa = o[ti][dt] * alpha;
+                    if (whole) {
+                        o[ti][dt] = RowsMfma<T>::run(a.f, pf.f, oa);
+                    } else {
+                        rows_f32x4 on = oa;
+                        for (int jj = jlo[ti]; jj <= jhi[ti]; ++jj) {
+                            const int ke = min(len0 + jj + 1, s1), kf = window > 0 ? max(0, len0 + jj + 1 - window) : 0;
+                            F am;
+#pragma unroll
+                            for (int w = 0; w < 4; ++w) {  // word w: keys k0 + 16 (w / 2) + 4 qq + 2 (w % 2), + 1
+                                const int key = k0 + (w >> 1) * 16 + qq * 4 + (w & 1) * 2;
+                                const uint32_t keep = ((key >= kf && key < ke) ? 0xffffu : 0u) |
+                                                      ((key + 1 >= kf && key + 1 < ke) ? 0xffff0000u : 0u);
+                                am.w[w] = a.w[w] & keep;
+                            }
+                            const rows_f32x4 acc = RowsMfma<T>::run(am.f, pf.f, oa);
+                            if (jrow[ti] == jj) on = acc;
+                        }
+                        o[ti][dt] = on;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti) {
+        float ll = l[ti];                                  // fixed order: (qq, qq ^ 1), then (.., .. ^ 2)
+        ll += __shfl_xor(ll, 16, 64);
+        ll += __shfl_xor(ll, 32, 64);
+        if (!rok[ti]) continue;
+        float* pp = part + part_index<DD>(bh[ti], nsplit, split);
+#pragma unroll
+        for (int dt = 0; dt < OT; ++dt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pp[dt * 16 + qq * 4 + e] = o[ti][dt][e];
+        if (qq == 0) { pp[DD] = m[ti]; pp[DD + 1] = ll; }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Prompt-lookup drafts (uamd_ngram_draft, uamd_accept_greedy): the two tiny kernels that turn the span step into speculative
+// decoding of ONE sequence from its own context. Plain C++; every input and counter lives on the device, so draft -> R-row
+// step -> argmax -> accept replays as one hipGraph.
+//
+// The draft. For n = n_max .. 1: suffix = hist[len - n, len); among the starts i with i + n <= len - 1 (the match is followed
+// by at least one token) and hist[i, i + n) == suffix the LARGEST wins, and the first n with a match wins. tok[0] = the last
+// token, tok[1 .. n_draft] = what followed the match (at most K), the other slots 0.
+__global__ void __launch_bounds__(256) ngram_draft_kernel(const long long* __restrict__ hist, const int* __restrict__ hist_len,
+                                                          int cap, int n_max, int K, long long* __restrict__ tok,
+                                                          int* __restrict__ n_draft) {
+    __shared__ int best;
+    const int tid = threadIdx.x;
+    const int len = min(*hist_len, cap);
+    int at = -1, n_hit = 0;
+    for (int n = min(n_max, len - 1); n >= 1 && at < 0; --n) {
+        if (tid == 0) best = -1;
+        __syncthreads();
+        for (int i = tid; i + n <= len - 1; i += 256) {
+            bool same = true;
+            for (int e = 0; e < n; ++e) same = same && hist[i + e] == hist[len - n + e];
+            if (same) atomicMax(&best, i);
+        }
+        __syncthreads();
+        at = best;
+        n_hit = n;
+        __syncthreads();                                   // everyone has read `best` before the next n clears it
+    }
+    const int from = at + n_hit;
+    const int nd = at >= 0 ? min(K, len - from) : 0;
+    if (tid == 0) *n_draft = nd;
+    if (tid <= K) tok[tid] = tid == 0 ? (len > 0 ? hist[len - 1] : 0) : (tid <= nd ? hist[from + tid - 1] : 0);
+}
+
+// The verdict. tok[0 .. K] were the step's token rows, a[j] the arg-max of row j's logits, i.e. the model's token AFTER
+// tok[0 .. j]. m = the number of leading drafts with tok[j] == a[j - 1]; a[0 .. m] are emitted. Nothing follows an emitted eos
+// and no more than `remaining` tokens are emitted. Lane 0 of one wave does it all (K <= 15).
+__global__ void __launch_bounds__(64) accept_greedy_kernel(const long long* __restrict__ tok, const long long* __restrict__ a, int K,
+                                                           const long long* __restrict__ eos, int n_eos,
+                                                           long long* __restrict__ hist, int cap, int* __restrict__ hist_len,
+                                                           int* __restrict__ kv_len, int* __restrict__ remaining,
+                                                           int* __restrict__ done, const int* __restrict__ n_draft,
+                                                           long long* __restrict__ stats) {
+    if (threadIdx.x != 0) return;
+    const int rem = *remaining, len = *hist_len;
+    if (*done || rem <= 0 || len >= cap) { *done = 1; return; }
+    auto is_eos = [&](long long t) {
+        bool hit = false;
+        for (int e = 0; e < n_eos; ++e) hit = hit || eos[e] == t;
+        return hit;
+    };
+    int m = 0;
+    bool stop = is_eos(a[0]);
+    while (!stop && m < K && m + 1 < rem && len + m + 1 < cap && tok[m + 1] == a[m]) {
+        ++m;
+        stop = is_eos(a[m]);
+    }
+    for (int j = 0; j <= m; ++j) hist[len + j] = a[j];
+    *hist_len = len + m + 1;
+    *kv_len += m + 1;
+    *remaining = rem - (m + 1);
+    if (stop || rem - (m + 1) <= 0) *done = 1;
+    stats[0] += 1;
+    stats[1] += *n_draft;
+    stats[2] += m;
+    stats[3] += m + 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2220,6 +2520,67 @@ extern "C" int uamd_attn_decode_shared(const void* q, int64_t q_sb, const void* 
         hipLaunchKernelGGL((attn_decode_combine_kernel<T, DD>), dim3(Hq, B), dim3(DD), 0, st, partials, (T*)out, out_sb, Hq, nsplit);
         return uamd_launch_status();
     });
+}
+
+// ---- a span of R new tokens per sequence in one step (include/unsloth_amd.h): the append, the attention, and the draft /
+//      accept kernels of prompt-lookup decoding.
+extern "C" int uamd_rope_kv_append_span(void* qkv, int64_t ld_qkv, const void* cos_t, const void* sin_t, int64_t ld_cs,
+                                        const int* kv_len, void* k_cache, void* v_cache, int64_t cache_sb, int64_t cache_sh,
+                                        int B, int R, int Hq, int Hk, int D, int s_max, int dtype, void* stream) {
+    if (!qkv || !cos_t || !sin_t || !kv_len || !k_cache || !v_cache || B <= 0 || R <= 0 || Hq <= 0 || Hk <= 0 || D <= 0 || (D & 1))
+        return UAMD_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    UAMD_DISPATCH_HALF(dtype, hipLaunchKernelGGL((rope_append_span_kernel<T>), dim3(Hq + 2 * Hk, B * R), dim3(64), 0, st, (T*)qkv,
+                                                 ld_qkv, (const T*)cos_t, (const T*)sin_t, ld_cs, kv_len, (T*)k_cache,
+                                                 (T*)v_cache, cache_sb, cache_sh, R, Hq, Hk, D, s_max))
+    return uamd_launch_status();
+}
+
+extern "C" int uamd_attn_decode_span(const void* q, int64_t q_sb, const void* k_cache, const void* v_cache, int64_t cache_sb,
+                                     int64_t cache_sh, const int* kv_len, int R, float* partials, void* out, int64_t out_sb,
+                                     int B, int Hq, int Hk, int D, int nsplit, int split_keys, int window, float scale, int dtype,
+                                     void* stream) {
+    if (!q || !k_cache || !v_cache || !kv_len || !partials || !out || B <= 0 || Hq <= 0 || Hk <= 0) return UAMD_ERR_ARG;
+    if (R < 1 || R > 16 || window < 0) return UAMD_ERR_ARG;
+    if (int rc = attn_decode_check(Hq, Hk, D, nsplit, split_keys, k_cache, v_cache, cache_sb, cache_sh)) return rc;
+    const int G = Hq / Hk;
+    if (R * G > 128) return UAMD_ERR_ARG;
+    if (!aligned16(q) || (q_sb & 7)) return UAMD_ERR_ALIGN;
+    const float sl2 = scale * 1.4426950408889634f;
+    hipStream_t st = (hipStream_t)stream;
+    UAMD_DISPATCH_HALF(dtype, {
+        auto launch = [&](auto dd) -> int {
+            constexpr int DD = decltype(dd)::value;
+            if (int rc = uamd_launch_lds<&attn_decode_span_kernel<T, DD>>(
+                    dim3((unsigned)nsplit, (unsigned)Hk, (unsigned)B), dim3(256), SharedGeo<DD>::LDS, st, (const T*)q, q_sb,
+                    (const T*)k_cache, (const T*)v_cache, cache_sb, cache_sh, kv_len, partials, R, G, Hq, nsplit, split_keys,
+                    window, sl2))
+                return rc;
+            hipLaunchKernelGGL((attn_decode_combine_kernel<T, DD>), dim3(Hq, B * R), dim3(DD), 0, st, partials, (T*)out, out_sb, Hq,
+                               nsplit);
+            return uamd_launch_status();
+        };
+        return D == 128 ? launch(IntC<128>()) : launch(IntC<64>());
+    })
+}
+
+extern "C" int uamd_ngram_draft(const int64_t* hist, const int* hist_len, int cap, int n_max, int K, int64_t* tok, int* n_draft,
+                                void* stream) {
+    if (!hist || !hist_len || !tok || !n_draft || cap <= 0 || n_max < 1 || K < 1 || K > 15) return UAMD_ERR_ARG;
+    hipLaunchKernelGGL(ngram_draft_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const long long*)hist, hist_len, cap, n_max,
+                       K, (long long*)tok, n_draft);
+    return uamd_launch_status();
+}
+
+extern "C" int uamd_accept_greedy(const int64_t* tok, const int64_t* amax, int K, const int64_t* eos, int n_eos, int64_t* hist,
+                                  int cap, int* hist_len, int* kv_len, int* remaining, int* done, const int* n_draft,
+                                  int64_t* stats, void* stream) {
+    if (!tok || !amax || !hist || !hist_len || !kv_len || !remaining || !done || !n_draft || !stats) return UAMD_ERR_ARG;
+    if (K < 0 || K > 15 || n_eos < 0 || n_eos > 8 || (n_eos > 0 && !eos) || cap <= 0) return UAMD_ERR_ARG;
+    hipLaunchKernelGGL(accept_greedy_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const long long*)tok,
+                       (const long long*)amax, K, (const long long*)eos, n_eos, (long long*)hist, cap, hist_len, kv_len, remaining,
+                       done, n_draft, (long long*)stats);
+    return uamd_launch_status();
 }
 
 // ---- the FP8 KV cache (format: include/unsloth_amd.h). Codes [B, Hk, s_max, D] uint8 with strides (cache_sb, cache_sh, D, 1),

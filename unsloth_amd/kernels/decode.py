@@ -428,6 +428,66 @@ def attn_decode_shared(q, pk, pv, prompt_len, n_share, sk, sv, new_len, out, par
     return out
 
 
+MAX_SPAN = 16                         # token rows per sequence of one span step (uamd_gemv_rows' 16 rows; R * G <= 128 query rows)
+MAX_EOS = 8                           # eos ids uamd_accept_greedy compares against
+
+
+def rope_kv_append_span(qkv, cos, sin, kv_len, k_cache, v_cache, R, Hq, Hk, D):
+    """`rope_kv_append` for R new tokens per sequence (uamd_rope_kv_append_span): in place on qkv [B * R, (Hq + 2 Hk) D], row
+    b * R + j at RoPE position and cache slot kv_len[b] + j; kv_len is not advanced. The bits of R successive appends."""
+    B = k_cache.shape[0]
+    assert qkv.shape[0] == B * int(R) and qkv.stride(1) == 1 and k_cache.is_contiguous() and v_cache.is_contiguous()
+    assert kv_len.dtype == torch.int32 and kv_len.numel() >= B
+    assert cos.stride(1) == 1 and sin.stride() == cos.stride() and cos.dtype == qkv.dtype
+    _lib.call("uamd_rope_kv_append_span", qkv, _lib.ptr(qkv), qkv.stride(0), _lib.ptr(cos), _lib.ptr(sin), cos.stride(0),
+              _lib.ptr(kv_len), _lib.ptr(k_cache), _lib.ptr(v_cache), k_cache.stride(0), k_cache.stride(1), B, int(R), Hq, Hk, D,
+              k_cache.shape[2], _lib.dtype_code(qkv.dtype), _lib.stream_of(qkv))
+
+
+def attn_decode_span(q, k_cache, v_cache, kv_len, R, out, partials, split_keys, scale, window=0):
+    """Attention of the R tokens per sequence that `rope_kv_append_span` has just appended (uamd_attn_decode_span): q, out
+    [B * R, Hq*D] (q may be a view into the fused qkv rows); partials fp32 [B * R, Hq, nsplit, D + 2]. Row (b, j) attends keys
+    [max(0, t - window), t), t = kv_len[b] + j + 1, of sequence b's cache, which holds kv_len[b] + R keys by now."""
+    _lib.require_gpu(q)
+    B, Hk, S_max, D = k_cache.shape
+    Hq, nsplit = partials.shape[1], partials.shape[2]
+    assert tuple(partials.shape) == (B * int(R), Hq, nsplit, D + 2) and partials.is_contiguous() and partials.dtype == torch.float32
+    assert nsplit * split_keys >= S_max and q.stride(1) == 1 and out.stride(1) == 1
+    assert q.shape[0] == B * int(R) and out.shape[0] == B * int(R)
+    assert k_cache.stride()[2:] == (D, 1) and v_cache.stride() == k_cache.stride() and v_cache.shape == k_cache.shape
+    assert k_cache.dtype == v_cache.dtype == q.dtype == out.dtype and kv_len.dtype == torch.int32 and kv_len.numel() >= B
+    _lib.call("uamd_attn_decode_span", q, _lib.ptr(q), q.stride(0), _lib.ptr(k_cache), _lib.ptr(v_cache), k_cache.stride(0),
+              k_cache.stride(1), _lib.ptr(kv_len), int(R), _lib.ptr(partials), _lib.ptr(out), out.stride(0), B, Hq, Hk, D,
+              nsplit, int(split_keys), int(window), float(scale), _lib.dtype_code(q.dtype), _lib.stream_of(q))
+    return out
+
+
+def ngram_draft(hist, hist_len, K, n_max, tok, n_draft):
+    """The prompt-lookup draft of one sequence (uamd_ngram_draft; the rule is stated in include/unsloth_amd.h): hist int64 [cap],
+    hist_len int32 [1] -> tok int64 [K + 1] = (last token, the draft, zeros), n_draft int32 [1]. Everything on the device."""
+    _lib.require_gpu(hist)
+    assert hist.dtype == torch.long and hist.is_contiguous() and tok.dtype == torch.long and tok.is_contiguous()
+    assert tok.numel() >= int(K) + 1 and hist_len.dtype == torch.int32 and n_draft.dtype == torch.int32
+    _lib.call("uamd_ngram_draft", hist, _lib.ptr(hist), _lib.ptr(hist_len), hist.numel(), int(n_max), int(K), _lib.ptr(tok),
+              _lib.ptr(n_draft), _lib.stream_of(hist))
+
+
+def accept_greedy(tok, amax, K, eos, hist, hist_len, kv_len, remaining, done, n_draft, stats):
+    """The verdict of a greedy verify step (uamd_accept_greedy; the rule is stated in include/unsloth_amd.h): tok, amax int64
+    [K + 1]; eos int64 [<= 8] or None; hist int64 [cap]; hist_len, kv_len, remaining, done, n_draft int32 [1]; stats int64 [4]
+    (steps, drafted, accepted, tokens). Everything on the device, updated in place."""
+    _lib.require_gpu(tok)
+    n_eos = 0 if eos is None else eos.numel()
+    assert n_eos <= MAX_EOS and (eos is None or (eos.dtype == torch.long and eos.is_contiguous()))
+    assert tok.dtype == amax.dtype == hist.dtype == stats.dtype == torch.long and stats.numel() >= 4
+    assert tok.numel() >= int(K) + 1 and amax.numel() >= int(K) + 1
+    assert all(t.dtype == torch.int32 for t in (hist_len, kv_len, remaining, done, n_draft))
+    assert all(t.is_contiguous() for t in (tok, amax, hist, stats))
+    _lib.call("uamd_accept_greedy", tok, _lib.ptr(tok), _lib.ptr(amax), int(K), _lib.ptr(eos), n_eos, _lib.ptr(hist),
+              hist.numel(), _lib.ptr(hist_len), _lib.ptr(kv_len), _lib.ptr(remaining), _lib.ptr(done), _lib.ptr(n_draft),
+              _lib.ptr(stats), _lib.stream_of(tok))
+
+
 def _fp8_cache(codes, scales):
     """Asserts the layout of one FP8 cache (include/unsloth_amd.h): codes uint8 [B, Hk, S_max, D] and scales fp32 [B, Hk, S_max];
     the batch stride is free (every n-th row of a cache is a cache), the rest is dense. Returns (B, Hk, S_max, D)."""

@@ -27,6 +27,9 @@ leaves the 5-launch step for it.
 `share_prompt=n` (opt-in, 16-bit cache): rows p n .. p n + n - 1 are n samples of prompt p (num_return_sequences; GRPO's n
 completions of one prompt). The prompt's K / V are stored once per prompt and each row keeps only the keys it appended; the step's
 attention (uamd_attn_decode_shared) scores the n x G query rows of a (prompt, KV head) against one fetch of every prompt key.
+`generate(..., prompt_lookup_num_tokens=K)` (opt-in, one greedy sequence, 16-bit cache): every step verifies the last token and K
+drafts found in the sequence's own context as K + 1 token rows on one pass over the weights (uamd_ngram_draft, uamd_gemv_rows,
+uamd_rope_kv_append_span, uamd_attn_decode_span, uamd_accept_greedy), a third captured graph beside the greedy and the sampled step.
 """
 import math
 import os
@@ -183,6 +186,11 @@ class DecodeEngine:
         self._sparams = _dk.sample_params(self.dev)
         self._draw_ctr = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self._graph_s = None
+        # prompt-lookup decoding (generate(prompt_lookup_num_tokens=K)): the verify step of R = K + 1 token rows, one capture
+        # per (R, n-gram size); its device state (`_lookup_state`) is allocated by the first call that asks for it
+        self._graph_l = {}
+        self._lk = None
+        self.lookup_stats = None
 
     # ---- per-layer parameter tuples, read once (adapters must not be switched under a live engine) -------------------
     @staticmethod
@@ -237,6 +245,7 @@ class DecodeEngine:
             sig = tuple(sig)
             if getattr(self, "_ptr_sig", None) != sig:
                 self._graph = self._graph_s = None
+                self._graph_l = {}
                 self._ptr_sig = sig
         core = self.core
         h = core.embed_tokens(input_ids.to(self.dev)).to(self.dtype)
@@ -495,9 +504,131 @@ class DecodeEngine:
         self.logits = getattr(self, gl)
         return self.logits
 
+    # ---- prompt-lookup decoding: K drafts from the sequence's own context, verified in one pass over the weights ----------------
+    def _lookup_fallback(self, K, T, max_new_tokens, do_sample, attention_mask, eos):
+        """Why a call with prompt_lookup_num_tokens = K runs the plain token steps instead (None: it takes the lookup path)."""
+        if self.B != 1:
+            return "more than one sequence"
+        if do_sample:
+            return "sampling"
+        if self.kv_cache_dtype is not None:
+            return "fp8 KV cache"
+        if self.share_prompt is not None:
+            return "shared prompt cache"
+        if attention_mask is not None and not bool((attention_mask != 0).all()):
+            return "padded prompt"
+        if not 1 <= K <= _dk.MAX_SPAN - 1:
+            return f"prompt_lookup_num_tokens outside 1 .. {_dk.MAX_SPAN - 1}"
+        if (K + 1) * (self.Hq // self.Hk) > 128:
+            return "more than 128 query rows per KV head"
+        if self.S < T + max_new_tokens + K:
+            return "cache capacity below prompt + max_new_tokens + prompt_lookup_num_tokens"
+        if eos is not None and len(eos) > _dk.MAX_EOS:
+            return f"more than {_dk.MAX_EOS} eos ids"
+        if self._head.dtype != self.dtype or self._head.shape[1] > 16384:
+            return "lm_head outside uamd_gemv_rows"
+        return None
+
+    def _lookup_state(self):
+        """Device state of the lookup path: hist [S] the sequence, state = (hist_len, remaining, done, n_draft), stats = (steps,
+        drafted, accepted, tokens), tok / amax the token rows of a step and the arg-max of their logits, eos (-1: no id)."""
+        if self._lk is None:
+            R = _dk.MAX_SPAN
+            z = lambda *shape, dtype=torch.long: torch.zeros(*shape, dtype=dtype, device=self.dev)
+            self._lk = dict(hist=z(self.S), state=z(4, dtype=torch.int32), stats=z(4), tok=z(R), amax=z(R),
+                            eos=torch.full((_dk.MAX_EOS,), -1, dtype=torch.long, device=self.dev),
+                            partials=torch.empty(R, self.Hq, self.S // SPLIT_KEYS, self.D + 2, dtype=torch.float32, device=self.dev),
+                            amax_ws=(torch.empty(R * 64, dtype=torch.float32, device=self.dev), z(R * 64)))
+        return self._lk
+
+    @torch.no_grad()
+    def _lookup_body(self, R, n_max):
+        """One verify step: draft -> the R token rows through every layer on ONE pass over the weights (uamd_gemv_rows; the span
+        append and the span attention put row j at position kv_len + j) -> fp32 logits [R, V] -> arg-max per row -> accept.
+        Everything it reads and advances is on the device."""
+        lk, core = self._lk, self.core
+        st = lk["state"]
+        kw = dict(dtype=self.dtype, device=self.dev)
+        _dk.ngram_draft(lk["hist"], st[0:1], R - 1, n_max, lk["tok"], st[3:4])
+        resid, delta = core.embed_tokens(lk["tok"][:R]).to(self.dtype), None
+        part = lk["partials"][:R]
+        for li in range(len(core.layers)):
+            P = self._params[li]
+            if delta is None:
+                x = rms_fwd(resid, *P["ln1"])[0]
+            else:
+                resid, x, _ = add_rms_fwd(delta, resid, *P["ln1"])
+            qkv = torch.empty(R, (self.Hq + 2 * self.Hk) * self.D, **kw)
+            _dk.linear_group_rows(x, P["qkv"], out=qkv)
+            a_out = torch.empty(R, self.Hq * self.D, **kw)
+            _dk.rope_kv_append_span(qkv, self.cos, self.sin, self.kv_len, self.k_cache[li], self.v_cache[li], R,
+                                    self.Hq, self.Hk, self.D)
+            _dk.attn_decode_span(qkv[:, :self.Hq * self.D], self.k_cache[li], self.v_cache[li], self.kv_len, R, a_out, part,
+                                 SPLIT_KEYS, self.scale, window=self.window)
+            (o,) = _dk.linear_group_rows(a_out, P["o"])
+            resid, x, _ = add_rms_fwd(o, resid, *P["ln2"])
+            gate, up = _dk.linear_group_rows(x, P["gu"])
+            hmid = swiglu_fg_kernel(gate.view(R, 1, -1), up.view(R, 1, -1)).view(R, -1)
+            (delta,) = _dk.linear_group_rows(hmid, P["down"])
+        _, xn, _ = add_rms_fwd(delta, resid, core.norm.weight, _eps(core.norm))
+        W = self._head
+        (logits,) = _dk.gemv_rows(xn.view(R, -1), [dict(W=W, N=W.shape[0], y_f32=True)], nf4=False)
+        _dk.argmax_f32(logits, out=lk["amax"][:R], ws=lk["amax_ws"])
+        _dk.accept_greedy(lk["tok"], lk["amax"], R - 1, lk["eos"], lk["hist"], st[0:1], self.kv_len, st[1:2], st[2:3], st[3:4],
+                          lk["stats"])
+        self.step_ctr.add_(1)
+
+    def _lookup_step(self, R, n_max):
+        """`_lookup_body`, eagerly or as the replay of its capture (one per (R, n_max))."""
+        self._steps += 1
+        if not self.use_graph:
+            return self._lookup_body(R, n_max)
+        graph = self._graph_l.get((R, n_max))
+        if graph is None:
+            # eager warm-up, with every counter put back afterwards (the K / V it appended sit behind kv_len again)
+            lk = self._lk
+            saved = [(t, t.clone()) for t in (self._lens, lk["state"], lk["stats"])]
+            self._lookup_body(R, n_max)
+            for t, v in saved:
+                t.copy_(v)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                self._lookup_body(R, n_max)
+            self._graph_l[(R, n_max)] = graph
+            for t, v in saved:                  # the capture itself does not execute
+                t.copy_(v)
+        graph.replay()
+
+    @torch.no_grad()
+    def _generate_lookup(self, input_ids, logits, max_new_tokens, eos, K, n_max):
+        """The greedy tokens of the plain steps, several per pass over the weights where the drafts hit. hist = prompt + first
+        token; every iteration is one verify step and ONE host read (done flag, hist_len)."""
+        T = input_ids.shape[1]
+        lk = self._lookup_state()
+        hist, st = lk["hist"], lk["state"]
+        first = torch.argmax(logits, dim=-1)                         # the first token: from the prefill logits, as today
+        hist[:T].copy_(input_ids[0])
+        hist[T:T + 1].copy_(first)
+        lk["eos"].fill_(-1)
+        if eos:
+            lk["eos"][:len(eos)].copy_(torch.tensor(eos, device=self.dev))
+        lk["stats"].zero_()
+        done0 = torch.isin(first, lk["eos"]).to(torch.int32).view(1) if max_new_tokens > 1 else torch.ones(1, dtype=torch.int32, device=self.dev)
+        st.copy_(torch.cat([torch.tensor([T + 1, max_new_tokens - 1], dtype=torch.int32, device=self.dev), done0, done0 * 0]))
+        while True:
+            hist_len, _, done, _ = st.tolist()                       # the loop's one sync per step
+            if done:
+                break
+            self._lookup_step(K + 1, n_max)
+        steps, drafted, accepted, tokens = lk["stats"].tolist()
+        self.lookup_stats = dict(steps=steps, drafted=drafted, accepted=accepted, tokens=tokens, fallback=None)
+        return hist[:hist_len].clone().view(1, -1)
+
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens=32, eos_token_id=None, do_sample=False, temperature=1.0, top_k=0,
-                 generator=None, pad_token_id=None, top_p=1.0, min_p=0.0, attention_mask=None, num_return_sequences=1):
+                 generator=None, pad_token_id=None, top_p=1.0, min_p=0.0, attention_mask=None, num_return_sequences=1,
+                 prompt_lookup_num_tokens=None, max_matching_ngram_size=2):
         """Greedy (default) or temperature / top-k / top-p / min-p sampling. Returns [B, T + new] token ids. Rows that have
         produced an end-of-sequence token keep emitting `pad_token_id` (default: the first eos id), like HF's generate.
         `attention_mask`: left-padded prompts (see `prefill`); the padded prompt is returned in front of the new tokens.
@@ -507,11 +638,30 @@ class DecodeEngine:
         capacity of new tokens.
         Sampling happens on the device (uamd_sample_f32): one 64-bit seed per call is drawn from `generator` (the default
         generator of its device when None) without a sync, the first token is drawn from the prefill logits at draw 0 and every
-        later one inside the token step, so equally seeded generators give equal tokens."""
+        later one inside the token step, so equally seeded generators give equal tokens.
+        `prompt_lookup_num_tokens` = K (1 .. 15; HF's keyword, with `max_matching_ngram_size`): one greedy sequence is decoded by
+        verify steps -- the last token and K drafts that followed the latest earlier occurrence of the sequence's last n-gram
+        go through the layers as K + 1 token rows on one pass over the weights, and the longest prefix of the drafts the model
+        agrees with is kept (uamd_ngram_draft, uamd_attn_decode_span, uamd_accept_greedy). The tokens are those of the plain
+        steps up to the rounding of a batched step against a single one; `lookup_stats` = steps / drafted / accepted / tokens of
+        the call. A call outside the path's scope (`_lookup_fallback`) runs the plain steps and says why in
+        `lookup_stats["fallback"]`; `lookup_stats` is None after a call without the keyword."""
         input_ids = input_ids.to(self.dev)
         n = int(num_return_sequences or 1)
         if n > 1 and not do_sample:
             raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True")
+        eos = None if eos_token_id is None else sorted(set(eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id]))
+        self.lookup_stats = None
+        K = int(prompt_lookup_num_tokens or 0)
+        if K:
+            why = self._lookup_fallback(K, input_ids.shape[1], max_new_tokens, do_sample or n > 1, attention_mask, eos)
+            if why is None and max_new_tokens < 1:
+                why = "no new tokens"
+            if why is None:
+                logits = self.prefill(input_ids, attention_mask)
+                self.sampling()
+                return self._generate_lookup(input_ids, logits, int(max_new_tokens), eos, K, max(1, int(max_matching_ngram_size or 2)))
+            self.lookup_stats = dict(steps=0, drafted=0, accepted=0, tokens=0, fallback=why)
         logits = self.prefill(input_ids, attention_mask, repeat=n)
         if n > 1:
             input_ids = input_ids.repeat_interleave(n, 0)
@@ -523,7 +673,6 @@ class DecodeEngine:
         else:
             self.sampling()
         out = [input_ids]
-        eos = None if eos_token_id is None else sorted(set(eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id]))
         eos_t = None if eos is None else torch.tensor(eos, device=self.dev)
         pad = pad_token_id if pad_token_id is not None else (eos[0] if eos else 0)
         done = torch.zeros(self.B, dtype=torch.bool, device=self.dev)
@@ -587,12 +736,13 @@ def _eps(norm):
 # silently ignored
 _ENGINE_KWARGS = {"max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "do_sample", "temperature", "top_k", "top_p",
                   "min_p", "attention_mask", "use_cache", "generator", "max_seq_len", "return_dict_in_generate", "output_scores",
-                  "generation_config", "tokenizer", "num_return_sequences", "kv_cache_dtype", "share_prompt_cache"}
+                  "generation_config", "tokenizer", "num_return_sequences", "kv_cache_dtype", "share_prompt_cache",
+                  "prompt_lookup_num_tokens", "max_matching_ngram_size"}
 
 
 # generation_config fields the engine reads (below the explicit keywords, above the model's own generation config)
 _CONFIG_FIELDS = ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "do_sample", "temperature", "top_k", "top_p",
-                  "min_p", "num_return_sequences")
+                  "min_p", "num_return_sequences", "prompt_lookup_num_tokens", "max_matching_ngram_size")
 _NEUTRAL = {"repetition_penalty": (None, 1.0), "num_beams": (None, 1), "streamer": (None,), "num_return_sequences": (None, 1),
             "min_new_tokens": (None, 0), "return_dict_in_generate": (None, False), "output_scores": (None, False),
             "generation_config": (None,)}
@@ -673,13 +823,22 @@ def route_generate(model, input_ids, max_new_tokens, kwargs):
     n = int(kwargs.get("num_return_sequences", None) or call_cfg.get("num_return_sequences", None) or 1)
     if n > 1 and not do_sample:
         raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True")
+    # prompt-lookup drafts (HF's two keywords / generation_config fields; None / 0: off): the engine verifies them for ONE greedy
+    # sequence; anything else keeps HF's own assisted generation
+    lookup = {}
+    K = int(gen_default("prompt_lookup_num_tokens", 0) or 0)
+    if K:
+        if do_sample or input_ids.shape[0] * n > 1:
+            return "old", ["prompt_lookup_num_tokens with " + ("do_sample" if do_sample else "more than one sequence")]
+        lookup = dict(prompt_lookup_num_tokens=K, max_matching_ngram_size=int(gen_default("max_matching_ngram_size", 2) or 2))
     return "engine", dict(max_new_tokens=int(max_new_tokens), eos_token_id=eos, pad_token_id=pad, do_sample=do_sample,
                           temperature=float(gen_default("temperature", 1.0)),
                           top_k=int(gen_default("top_k", 0) or 0) if do_sample else 0,
                           top_p=float(gen_default("top_p", 1.0)) if do_sample else 1.0,
                           min_p=float(gen_default("min_p", 0.0) or 0.0) if do_sample else 0.0,
                           generator=kwargs.get("generator", None), attention_mask=attention_mask if lens is not None else None,
-                          num_return_sequences=n, batch=input_ids.shape[0] * n, need=input_ids.shape[1] + int(max_new_tokens))
+                          num_return_sequences=n, batch=input_ids.shape[0] * n,
+                          need=input_ids.shape[1] + int(max_new_tokens) + K, **lookup)
 
 
 def wanted_kv_cache(model, kv_cache_dtype=None):
@@ -711,8 +870,9 @@ def wanted_share_prompt(model, share_prompt_cache=None):
 def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_len=None, **kwargs):
     """llama.py:2167-2259 counterpart: `model.generate(...)` after `FastLanguageModel.for_inference(model)`.
     The reference forwards every keyword to HF's generate; the engine covers greedy / temperature / top-k / top-p / min-p
-    decoding of unpadded and LEFT-padded batches (pad tokens under the mask's zeros), `num_return_sequences` when sampling and a `generation_config=` object
-    whose other fields are at their defaults. Calls outside that (repetition_penalty, beams, streamers, logits processors, a
+    decoding of unpadded and LEFT-padded batches (pad tokens under the mask's zeros), `num_return_sequences` when sampling, a `generation_config=` object
+    whose other fields are at their defaults, and `prompt_lookup_num_tokens` / `max_matching_ngram_size` for one greedy sequence
+    (DecodeEngine.generate; the engine's capacity grows by the K draft slots). Calls outside that (repetition_penalty, beams, streamers, logits processors, a
     right-padded or holey attention_mask, ...) are handed to HF's own generate (`model._old_generate`) -- or raise when it is
     unavailable. `share_prompt_cache=True` (the keyword, or the model's record: `wanted_share_prompt`) with
     num_return_sequences = n > 1: the engine is built with share_prompt = n -- one prompt cache for the n samples of a prompt;
