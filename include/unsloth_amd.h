@@ -584,6 +584,26 @@ int uamd_rope_kv_append_span(void* qkv, int64_t ld_qkv, const void* cos_t, const
 int uamd_attn_decode_span(const void* q, int64_t q_sb, const void* k_cache, const void* v_cache, int64_t cache_sb,
                           int64_t cache_sh, const int* kv_len, int R, float* partials, void* out, int64_t out_sb, int B, int Hq,
                           int Hk, int D, int nsplit, int split_keys, int window, float scale, int dtype, void* stream);
+/* ---- a chunk of T_c new tokens per sequence appended to a LIVE cache: the next chat turn, a tool result, a piece of a chunked
+ * prefill (DecodeEngine.extend). The append is uamd_rope_kv_append_span with R = T_c: its contract does not depend on R (one
+ * grid row per token row, B * R <= 65535, refused with UAMD_ERR_ARG beyond); a row whose slot would pass s_max writes nothing.
+ *
+ * uamd_attn_extend: attention of the T_c tokens just appended at slots kv_len[b] .. kv_len[b] + T_c - 1 (kv_len: DEVICE, never
+ * read by the host, not advanced here). q [B * T_c, Hq * D] (row stride q_sb, row b * T_c + j = token j of sequence b; a view
+ * into the fused q|k|v rows is fine), out [B * T_c, Hq * D] (row stride out_sb) in `dtype`, NORMALISED in the kernel: no
+ * workspace, no combine launch. Row (b, j, head h) attends keys [max(0, t_j - window), t_j) of cache b, KV head h / (Hq / Hk),
+ * t_j = kv_len[b] + j + 1 (window 0: all): the old cache in full and a causal triangle over the chunk. The caller guarantees
+ * kv_len[b] + T_c <= s_max (the kernel clamps every range to s_max and reads nothing beyond). Slots at or past kv_len[b] + T_c
+ * are never loaded. bf16 / fp16, D 64 or 128, Hq / Hk 1 .. 8; anything else UAMD_ERR_ARG before the launch.
+ * One launch, grid (ceil(T_c / floor(128 / G)), Hk, B) x 256 threads: a workgroup owns 128 query rows of one KV head,
+ * token-major, as 16-row tiles (wave w: tiles w and w + 4), and walks all keys of their ranges in fills of 128 through LDS with
+ * the next fill's global loads in flight under the current fill's v_mfma_f32_16x16x32. Roundings: fp32 accumulation of the exact
+ * 16-bit products q_j k_j, times scale * log2 e in fp32; running max and sum in fp32 (exp2 domain); P = exp2(s - m) rounded ONCE
+ * to `dtype` and the sum taken over the rounded P; P V accumulated in fp32; o / l rounded once. Row j's output is bitwise the
+ * same for every T_c > j (finite chunk values): later tokens never enter it. */
+int uamd_attn_extend(const void* q, int64_t q_sb, const void* k_cache, const void* v_cache, int64_t cache_sb, int64_t cache_sh,
+                     const int* kv_len, int T_c, void* out, int64_t out_sb, int B, int Hq, int Hk, int D, int s_max, int window,
+                     float scale, int dtype, void* stream);
 /* The draft: K tokens that followed an earlier occurrence of the sequence's last n-gram in its own context (what HF's
  * `prompt_lookup_num_tokens` proposes). hist: int64 [cap] and hist_len: int32 [1], both on the DEVICE; len = min(*hist_len, cap).
  * For n = min(n_max, len - 1) .. 1, with suffix = hist[len - n, len): among the starts i with i + n <= len - 1 and

@@ -5,6 +5,7 @@
     python tools/decode_bench.py [--shape llama3-8b] [--layers 32] [--context 2048] [--new 64] [--out decode.jsonl]
     python tools/decode_bench.py --sampler [--out sampler.jsonl]     the device sampler: launch and sampled step
     python tools/decode_bench.py --lookup [--out lookup.jsonl]       prompt-lookup verify replays (K = 2, 4, 8, 15) against the plain step
+    python tools/decode_bench.py --extend [--out extend.jsonl]       extend a live cache / chunked prefill against (re-)prefilling
 """
 import argparse
 import json
@@ -169,6 +170,83 @@ def lookup_ab(eng, emit, context, steps, rounds=5, Ks=(2, 4, 8, 15), n_max=2):
                   accepted_while_timing=accepted[K], acceptance_on_real_text="not measured"))
 
 
+def _wall_ms(fn):
+    torch.cuda.synchronize()
+    t0 = time.time()
+    fn()
+    torch.cuda.synchronize()
+    return (time.time() - t0) * 1e3
+
+
+def extend_ab(a, emit, rounds=3):
+    """DecodeEngine.extend against what the engine could do before it, rounds interleaved in one process (round 0 warms):
+      * a cache of 2048 / 8192 keys extended by 128 / 512 / 2048 tokens, batch 1 and 8, against re-prefilling context + chunk;
+      * a 2048-token prompt prefilled in chunks of 512 against the one-shot prefill, with the peak of allocated bytes above the
+        engine's own for both;
+      * uamd_attn_extend alone on a 2048-token chunk into an empty cache against the training flash forward on that shape."""
+    from unsloth_amd.kernels import decode as D
+    from unsloth_amd.models import llama as LL
+    from unsloth_amd.models.decode import DecodeEngine
+    H, I, L0, Hq, Hk, Dh, V = SHAPES[a.shape]
+    dev, bf = "cuda", torch.bfloat16
+    for B in (1, 8):
+        T = 2048
+        q = torch.randn(B, T, Hq, Dh, device=dev, dtype=bf)
+        k = torch.randn(B, T, Hk, Dh, device=dev, dtype=bf)
+        v = torch.randn(B, T, Hk, Dh, device=dev, dtype=bf)
+        kc, vc = k.transpose(1, 2).contiguous(), v.transpose(1, 2).contiguous()
+        kvl = torch.zeros(B, dtype=torch.int32, device=dev)
+        out = torch.empty(B * T, Hq * Dh, device=dev, dtype=bf)
+        fns = dict(extend=lambda: D.attn_extend(q.view(B * T, -1), kc, vc, kvl, T, out, Dh ** -0.5),
+                   flash=lambda: LL._attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), None, None, None))
+        us = {n: [] for n in fns}
+        for _ in range(5):
+            for n, fn in fns.items():
+                us[n].append(timeit(fn, n=10))
+        flops = 4 * B * Hq * Dh * T * (T + 1) / 2
+        emit(dict(kernel="uamd_attn_extend against the training flash forward, chunk 2048 into an empty cache", batch=B, q_heads=Hq,
+                  kv_heads=Hk, head_dim=Dh, extend_us=_spread(us["extend"]), flash_us=_spread(us["flash"]),
+                  extend_tflops=round(flops / sorted(us["extend"])[2] / 1e6, 1), flash_tflops=round(flops / sorted(us["flash"])[2] / 1e6, 1)))
+    model = whole_model(a, dev)
+    for B in (1, 8):
+        for ctx in (2048, 8192):
+            eng = DecodeEngine(model, max_seq_len=ctx + 2048, batch=B)
+            ids = torch.randint(0, 32000, (B, ctx + 2048), device=dev)
+            for Tc in (128, 512, 2048):
+                def ext():
+                    eng.kv_len.fill_(ctx)               # the cache of the last re-prefill, cut back to the context
+                    eng._fed = ctx
+                    eng.extend(ids[:, ctx:ctx + Tc])
+                ms = dict(extend=[], reprefill=[])
+                for r in range(rounds + 1):
+                    t = _wall_ms(lambda: eng.prefill(ids[:, :ctx + Tc]))
+                    e = _wall_ms(ext)
+                    if r:
+                        ms["reprefill"].append(t)
+                        ms["extend"].append(e)
+                e, t = _spread(ms["extend"]), _spread(ms["reprefill"])
+                emit(dict(metric="extend a live cache against re-prefilling context + chunk, ms", batch=B, context=ctx, chunk=Tc,
+                          layers=a.layers, rounds=rounds, extend_ms=e, reprefill_ms=t, speedup=round(t["median"] / e["median"], 2)))
+            del eng
+        eng = DecodeEngine(model, max_seq_len=2048, batch=B)
+        ids = torch.randint(0, 32000, (B, 2048), device=dev)
+        ms, peak = dict(chunked=[], oneshot=[]), {}
+        for r in range(rounds + 1):
+            for n, kw in (("oneshot", {}), ("chunked", dict(chunk=512))):
+                torch.cuda.synchronize()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                t = _wall_ms(lambda: eng.prefill(ids, **kw))
+                peak[n] = torch.cuda.max_memory_allocated() - base
+                if r:
+                    ms[n].append(t)
+        c, o = _spread(ms["chunked"]), _spread(ms["oneshot"])
+        emit(dict(metric="prefill of 2048 tokens in chunks of 512 against one shot, ms", batch=B, layers=a.layers, rounds=rounds,
+                  chunked_ms=c, oneshot_ms=o, chunked_over_oneshot=round(c["median"] / o["median"], 3),
+                  peak_bytes_chunked=peak["chunked"], peak_bytes_oneshot=peak["oneshot"]))
+        del eng
+
+
 def whole_model(a, dev):
     """The benchmark's synthetic Llama-shaped QLoRA model (NF4, r = 16 on every projection, random B factors)."""
     import bench as B                                   # the benchmark's synthetic Llama-3-8B-shaped config
@@ -199,6 +277,8 @@ def main():
                     help="only the sampler: its launch against the torch chain, and the sampled against the greedy hipGraph step")
     ap.add_argument("--lookup", action="store_true",
                     help="only prompt-lookup decoding: ms per verify replay at K = 2, 4, 8, 15 against the plain fused step")
+    ap.add_argument("--extend", action="store_true",
+                    help="only DecodeEngine.extend: against re-prefilling, chunked against one-shot prefill, the kernel against flash")
     a = ap.parse_args()
     H, I, L0, Hq, Hk, Dh, V = SHAPES[a.shape]
     if a.layers is None:
@@ -213,6 +293,9 @@ def main():
 
     if a.attn_ab:
         return attn_head_dim_ab(a.context, emit)
+    if a.extend:
+        a.context = 8192 + 2048                         # (the model's max_seq_length)
+        return extend_ab(a, emit)
     if a.sampler:
         from unsloth_amd.models.decode import DecodeEngine
         sampler_ab(V, emit)

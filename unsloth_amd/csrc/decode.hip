@@ -1651,6 +1651,224 @@ __global__ void __launch_bounds__(256) attn_decode_span_kernel(const T* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Chunk attention (uamd_attn_extend): sequence b has just appended T_c tokens at cache slots kv_len[b] .. kv_len[b] + T_c - 1
+// (a next chat turn, a piece of a chunked prefill); query row (token j, head h) attends keys [max(0, t_j - window), t_j) of
+// KV head h / G, t_j = kv_len[b] + j + 1. Block (query tile, kvh, b) = 4 waves owns 128 query rows of one KV head, token-major
+// (row = jj * G + g over the tile's floor(128 / G) tokens), in the 16-row tiles of the prefix / span scans -- wave w owns
+// tiles w and w + 4 -- and walks ALL keys [first_min, end_max) of its rows in fills of SH_CK, so a row's (m, l, o) never
+// leaves its registers: the output is normalised and rounded here, no partials, no combine.
+//   * A workgroup runs tens of fills (64 at 8192 keys), so the loop is software-pipelined over ONE LDS buffer: the next
+//     fill's 16-byte global loads are issued into registers (ExtFill) right after the barrier that publishes the current
+//     fill, stay in flight under its MFMAs, and are written to LDS -- K row-major, V transposed with two keys per word,
+//     SharedGeo's layout -- behind the barrier that ends its reads. Keys outside [first_min, end_max) are not loaded and enter
+//     as zeros: a slot at or past kv_len[b] + T_c is never read.
+//   * A 32-key group that lies inside the range of every row of a 16-row tile runs without the per-row select (all of the
+//     old cache but a window's start); a group past every row's end or before every row's start is skipped; the others (the
+//     diagonal, a window's start, the last partial group) select the score to -inf outside the row's [first, end).
+//   * Roundings, the prefix scan's: q . k is the MFMA's fp32 sum of exact 16-bit products, times scale * log2 e in fp32; max and
+//     sum in fp32 in the exp2 domain (softmax_merge); P rounded ONCE to T and the sum taken over the rounded P; P V in fp32;
+//     o / l rounded once. A row without a key in a group leaves (m, l, o) unchanged in value (alpha = exp2(0), P = 0; with an
+//     empty history exp2(-inf - 0) = 0, never exp2(-inf + inf)). A chunk key past a row's own token enters the row's P V as
+//     0 * v: the keys of a chunk are finite values the append has just written.
+#define UAMD_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+// (A function compiled without the packed fp32 instructions cannot inline the runtime headers' helpers, which are compiled with
+// them: plain vector types instead of uint4 / uint2, and the shuffle and the barrier restated on the builtins.)
+typedef uint32_t ext_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t ext_u32x2 __attribute__((ext_vector_type(2)));
+template <typename T> union ExtFrag { ext_u32x4 u; ext_u32x2 h[2]; uint32_t w[4]; typename RowsMfma<T>::frag f; };
+__device__ __forceinline__ UAMD_NO_PK_F32 float ext_shfl_xor(float v, int mask, int) {
+    const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ mask) << 2, __builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ UAMD_NO_PK_F32 void ext_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// The global loads of one fill, in registers from the issue (before the current fill's MFMAs) to the LDS stores (after them).
+template <typename T, int DD> struct ExtFill {
+    static constexpr int LPK = DecGeo<DD>::LPK, KROW = SharedGeo<DD>::KROW, VROW = SharedGeo<DD>::VROW;
+    static constexpr int KIT = SH_CK * LPK / 256, VIT = KIT / 2;      // 16-byte K loads / V key pairs of a thread per fill
+    ext_u32x4 kr[KIT], vr[VIT][2];
+    __device__ __forceinline__ void load(const T* const kb, const T* const vb, int c0, int live0, int s1, int tid) {
+#pragma unroll
+        for (int it = 0; it < KIT; ++it) {
+            const int i = tid + 256 * it, key = c0 + i / LPK, lc = i % LPK;
+            kr[it] = (key >= live0 && key < s1) ? *reinterpret_cast<const ext_u32x4*>(kb + (int64_t)key * DD + lc * 8)
+                                                : ext_u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int it = 0; it < VIT; ++it) {
+            const int i = tid + 256 * it, key = c0 + 2 * (i / LPK), lc = i % LPK;
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                vr[it][e] = (key + e >= live0 && key + e < s1)
+                                ? *reinterpret_cast<const ext_u32x4*>(vb + (int64_t)(key + e) * DD + lc * 8) : ext_u32x4{0u, 0u, 0u, 0u};
+        }
+    }
+    __device__ __forceinline__ void store(T* const Ks, uint32_t* const Vt, int tid) const {
+#pragma unroll
+        for (int it = 0; it < KIT; ++it) {
+            const int i = tid + 256 * it;
+            *reinterpret_cast<ext_u32x4*>(Ks + (i / LPK) * KROW + (i % LPK) * 8) = kr[it];
+        }
+#pragma unroll
+        for (int it = 0; it < VIT; ++it) {
+            const int i = tid + 256 * it, kp = i / LPK, lc = i % LPK;
+            const uint32_t a[4] = {vr[it][0].x, vr[it][0].y, vr[it][0].z, vr[it][0].w};
+            const uint32_t b[4] = {vr[it][1].x, vr[it][1].y, vr[it][1].z, vr[it][1].w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                  // columns lc * 8 + 2 j, + 1: (even key, odd key) per word
+                Vt[(lc * 8 + 2 * j) * VROW + kp] = (a[j] & 0xffffu) | (b[j] << 16);
+                Vt[(lc * 8 + 2 * j + 1) * VROW + kp] = (a[j] >> 16) | (b[j] & 0xffff0000u);
+            }
+        }
+    }
+};
+
+// One 32-key group (keys k0 .. k0 + 31 = LDS rows kg * 32 ..) against one 16-row tile: S^T = K Q^T, the online-softmax update of
+// the lane's row, O^T += V^T P^T. MASK: the per-row select of [first, end); without it every key of the group is the row's.
+template <typename T, int DD, bool MASK>
+__device__ __forceinline__ UAMD_NO_PK_F32 void extend_group(const T* const Ks, const uint32_t* const Vt, int kg, int k0, int r, int qq,
+                                             const ExtFrag<T> (&qf)[DD / 32], int first, int end, float scale_log2, float& m,
+                                             float& l, rows_f32x4 (&o)[DD / 16]) {
+    constexpr int KROW = SharedGeo<DD>::KROW, VROW = SharedGeo<DD>::VROW, QF = DD / 32, OT = DD / 16;
+    rows_f32x4 sc[2];
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+        sc[hf] = rows_f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int jf = 0; jf < QF; ++jf) {
+            ExtFrag<T> a;
+            a.u = *reinterpret_cast<const ext_u32x4*>(Ks + (kg * 32 + hf * 16 + r) * KROW + jf * 32 + qq * 8);
+            sc[hf] = RowsMfma<T>::run(a.f, qf[jf].f, sc[hf]);
+        }
+    }
+    // lane (row r, qq): keys k0 + 16 hf + 4 qq + e
+    float s[8], mx = -INFINITY;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int key = k0 + hf * 16 + qq * 4 + e;
+            s[hf * 4 + e] = (!MASK || (key >= first && key < end)) ? sc[hf][e] * scale_log2 : -INFINITY;
+            mx = fmaxf(mx, s[hf * 4 + e]);
+        }
+    mx = fmaxf(mx, ext_shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, ext_shfl_xor(mx, 32, 64));
+    float alpha, unused;
+    softmax_merge(m, l, mx, 0.f, alpha, unused);           // l: the lane's own keys, summed over qq at the end
+    const float mr = m == -INFINITY ? 0.f : m;
+    float pr[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        pr[e] = round_to<T>(__builtin_amdgcn_exp2f(s[e] - mr));
+        l += pr[e];
+    }
+    ExtFrag<T> pf;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pf.w[e] = pack2<T>(pr[2 * e], pr[2 * e + 1]);
+#pragma unroll
+    for (int dt = 0; dt < OT; ++dt) {
+        ExtFrag<T> a;                                      // V^T[column 16 dt + r][the lane's 8 keys]
+        const uint32_t* vp = Vt + (dt * 16 + r) * VROW + kg * 16 + qq * 2;
+        a.h[0] = *reinterpret_cast<const ext_u32x2*>(vp);
+        a.h[1] = *reinterpret_cast<const ext_u32x2*>(vp + 8);
+        o[dt] = RowsMfma<T>::run(a.f, pf.f, o[dt] * alpha);
+    }
+}
+
+template <typename T, int DD>
+__global__ UAMD_NO_PK_F32 void __launch_bounds__(256) attn_extend_kernel(const T* __restrict__ q, int64_t q_sb, const T* __restrict__ kc,
+                                                          const T* __restrict__ vc, int64_t c_sb, int64_t c_sh,
+                                                          const int* __restrict__ kv_len, T* __restrict__ out, int64_t out_sb,
+                                                          int Tc, int G, int s_max, int window, float scale_log2) {
+    constexpr int KROW = SharedGeo<DD>::KROW;
+    constexpr int QF = DD / 32, OT = DD / 16;              // Q fragments of a row; 16-column tiles of O^T
+    extern __shared__ __attribute__((aligned(16))) unsigned char sh_smem[];
+    T* const Ks = reinterpret_cast<T*>(sh_smem);
+    uint32_t* const Vt = reinterpret_cast<uint32_t*>(sh_smem + SH_CK * KROW * 2);
+    const int qt = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, qq = lane >> 4;
+    const int TPT = 128 / G;                               // tokens of a query tile
+    const int j0 = qt * TPT, nj = min(TPT, Tc - j0), NR = nj * G;
+    const int len0 = max(0, kv_len[b]);
+    const int s1 = min(len0 + j0 + nj, s_max);             // end_max: the last row's end (a chunk past s_max was refused by the host)
+    const int live0 = window > 0 ? max(0, len0 + j0 + 1 - window) : 0;      // first_min: the first row's start
+    // the wave's two tiles: lane (r, qq) works for row 16 t + r
+    bool rok[2];
+    int jrow[2], grow[2], first[2], end[2], t_lo[2], t_hi[2], f_lo[2], f_hi[2];
+    ExtFrag<T> qf[2][QF];
+    float m[2], l[2];
+    rows_f32x4 o[2][OT];
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti) {
+        const int row0 = (wave + 4 * ti) * 16, row = row0 + r;
+        rok[ti] = row < NR;
+        const int jj = rok[ti] ? row / G : 0;
+        grow[ti] = rok[ti] ? row - jj * G : 0;
+        jrow[ti] = j0 + jj;
+        const int jlo = j0 + min(nj - 1, row0 / G), jhi = j0 + min(nj - 1, (row0 + 15) / G);      // (wave-uniform)
+        first[ti] = window > 0 ? max(0, len0 + jrow[ti] + 1 - window) : 0;
+        end[ti] = min(len0 + jrow[ti] + 1, s1);
+        t_lo[ti] = min(len0 + jlo + 1, s1);                // the shortest / longest range's end of the tile
+        t_hi[ti] = min(len0 + jhi + 1, s1);
+        f_lo[ti] = window > 0 ? max(0, len0 + jlo + 1 - window) : 0;       // the earliest / latest range's start
+        f_hi[ti] = window > 0 ? max(0, len0 + jhi + 1 - window) : 0;
+        const T* qp = q + ((int64_t)b * Tc + jrow[ti]) * q_sb + (int64_t)(kvh * G + grow[ti]) * DD + qq * 8;
+#pragma unroll
+        for (int jf = 0; jf < QF; ++jf)
+            qf[ti][jf].u = rok[ti] ? *reinterpret_cast<const ext_u32x4*>(qp + jf * 32) : ext_u32x4{0u, 0u, 0u, 0u};
+        m[ti] = -INFINITY; l[ti] = 0.f;
+#pragma unroll
+        for (int dt = 0; dt < OT; ++dt) o[ti][dt] = rows_f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const T* const kb = kc + (int64_t)b * c_sb + (int64_t)kvh * c_sh;
+    const T* const vb = vc + (int64_t)b * c_sb + (int64_t)kvh * c_sh;
+    const int c_first = live0 / SH_CK * SH_CK;             // the first fill with a live key
+    ExtFill<T, DD> nx;
+    nx.load(kb, vb, c_first, live0, s1, tid);
+    for (int c0 = c_first; c0 < s1; c0 += SH_CK) {
+        if (c0 != c_first) ext_barrier();                // the previous fill is still being read
+        nx.store(Ks, Vt, tid);
+        ext_barrier();
+        if (c0 + SH_CK < s1) nx.load(kb, vb, c0 + SH_CK, live0, s1, tid);      // in flight under this fill's MFMAs
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti) {
+            if ((wave + 4 * ti) * 16 >= NR) continue;      // (wave-uniform, as everything that steers the loops below)
+            if (c0 >= t_hi[ti] || c0 + SH_CK <= f_lo[ti]) continue;
+            for (int kg = 0; kg < SH_CK / 32; ++kg) {
+                const int k0 = c0 + kg * 32;
+                if (k0 >= t_hi[ti] || k0 + 32 <= f_lo[ti]) continue;
+                if (k0 >= f_hi[ti] && k0 + 32 <= t_lo[ti])
+                    extend_group<T, DD, false>(Ks, Vt, kg, k0, r, qq, qf[ti], 0, 0, scale_log2, m[ti], l[ti], o[ti]);
+                else
+                    extend_group<T, DD, true>(Ks, Vt, kg, k0, r, qq, qf[ti], first[ti], end[ti], scale_log2, m[ti], l[ti], o[ti]);
+            }
+        }
+    }
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti) {
+        float ll = l[ti];                                  // fixed order: (qq, qq ^ 1), then (.., .. ^ 2)
+        ll += ext_shfl_xor(ll, 16, 64);
+        ll += ext_shfl_xor(ll, 32, 64);
+        if (!rok[ti]) continue;
+        const float inv = ll > 0.f ? 1.f / ll : 0.f;
+        T* op = out + ((int64_t)b * Tc + jrow[ti]) * out_sb + (int64_t)(kvh * G + grow[ti]) * DD + qq * 4;
+#pragma unroll
+        for (int dt = 0; dt < OT; ++dt) {
+            ext_u32x2 w;
+            w.x = pack2<T>(o[ti][dt][0] * inv, o[ti][dt][1] * inv);
+            w.y = pack2<T>(o[ti][dt][2] * inv, o[ti][dt][3] * inv);
+            *reinterpret_cast<ext_u32x2*>(op + dt * 16) = w;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Prompt-lookup drafts (uamd_ngram_draft, uamd_accept_greedy): the two tiny kernels that turn the span step into speculative
 // decoding of ONE sequence from its own context. Plain C++; every input and counter lives on the device, so draft -> R-row
 // step -> argmax -> accept replays as one hipGraph.
@@ -2529,6 +2747,7 @@ extern "C" int uamd_rope_kv_append_span(void* qkv, int64_t ld_qkv, const void* c
                                         int B, int R, int Hq, int Hk, int D, int s_max, int dtype, void* stream) {
     if (!qkv || !cos_t || !sin_t || !kv_len || !k_cache || !v_cache || B <= 0 || R <= 0 || Hq <= 0 || Hk <= 0 || D <= 0 || (D & 1))
         return UAMD_ERR_ARG;
+    if ((int64_t)B * R > 65535) return UAMD_ERR_ARG;      // one grid row per token row (a chunk of uamd_attn_extend: any R below that)
     hipStream_t st = (hipStream_t)stream;
     UAMD_DISPATCH_HALF(dtype, hipLaunchKernelGGL((rope_append_span_kernel<T>), dim3(Hq + 2 * Hk, B * R), dim3(64), 0, st, (T*)qkv,
                                                  ld_qkv, (const T*)cos_t, (const T*)sin_t, ld_cs, kv_len, (T*)k_cache,
@@ -2559,6 +2778,32 @@ extern "C" int uamd_attn_decode_span(const void* q, int64_t q_sb, const void* k_
             hipLaunchKernelGGL((attn_decode_combine_kernel<T, DD>), dim3(Hq, B * R), dim3(DD), 0, st, partials, (T*)out, out_sb, Hq,
                                nsplit);
             return uamd_launch_status();
+        };
+        return D == 128 ? launch(IntC<128>()) : launch(IntC<64>());
+    })
+}
+
+// ---- a chunk of T_c new tokens per sequence appended to a live cache (include/unsloth_amd.h): uamd_rope_kv_append_span with
+//      R = T_c is the append; one launch of attn_extend_kernel, grid (query tiles of floor(128 / G) tokens, Hk, B), is the attention.
+extern "C" int uamd_attn_extend(const void* q, int64_t q_sb, const void* k_cache, const void* v_cache, int64_t cache_sb,
+                                int64_t cache_sh, const int* kv_len, int T_c, void* out, int64_t out_sb, int B, int Hq, int Hk,
+                                int D, int s_max, int window, float scale, int dtype, void* stream) {
+    if (!q || !k_cache || !v_cache || !kv_len || !out || B <= 0 || Hq <= 0 || Hk <= 0 || T_c < 1 || s_max < 1 || window < 0)
+        return UAMD_ERR_ARG;
+    if (Hq % Hk || Hq / Hk > 8 || (D != 64 && D != 128) || B > 65535) return UAMD_ERR_ARG;
+    if ((int64_t)s_max * D > cache_sh || (int64_t)Hk * cache_sh > cache_sb) return UAMD_ERR_ARG;      // slots [0, s_max) of every head
+    if (!aligned16(k_cache) || !aligned16(v_cache) || (cache_sb & 7) || (cache_sh & 7)) return UAMD_ERR_ALIGN;
+    if (!aligned16(q) || (q_sb & 7) || !aligned16(out) || (out_sb & 7)) return UAMD_ERR_ALIGN;
+    const int G = Hq / Hk, tiles = (T_c + 128 / G - 1) / (128 / G);
+    const float sl2 = scale * 1.4426950408889634f;
+    hipStream_t st = (hipStream_t)stream;
+    UAMD_DISPATCH_HALF(dtype, {
+        auto launch = [&](auto dd) -> int {
+            constexpr int DD = decltype(dd)::value;
+            return uamd_launch_lds<&attn_extend_kernel<T, DD>>(dim3((unsigned)tiles, (unsigned)Hk, (unsigned)B), dim3(256),
+                                                               SharedGeo<DD>::LDS, st, (const T*)q, q_sb, (const T*)k_cache,
+                                                               (const T*)v_cache, cache_sb, cache_sh, kv_len, (T*)out, out_sb, T_c, G,
+                                                               s_max, window, sl2);
         };
         return D == 128 ? launch(IntC<128>()) : launch(IntC<64>());
     })

@@ -462,6 +462,26 @@ def attn_decode_span(q, k_cache, v_cache, kv_len, R, out, partials, split_keys, 
     return out
 
 
+def attn_extend(q, k_cache, v_cache, kv_len, T_c, out, scale, window=0):
+    """Attention of the T_c tokens per sequence that `rope_kv_append_span(..., R=T_c, ...)` has just appended to a live cache
+    (uamd_attn_extend): q, out [B * T_c, Hq*D] (q may be a view into the fused qkv rows). Row (b, j) attends keys
+    [max(0, t - window), t), t = kv_len[b] + j + 1: the old cache in full and a causal triangle over the chunk. One launch, the
+    output normalised inside; kv_len [B] int32 stays on the device and is not advanced. The caller keeps kv_len[b] + T_c within
+    the cache's S_max (host-known bound: the kernel clamps, it does not report)."""
+    _lib.require_gpu(q)
+    B, Hk, S_max, D = k_cache.shape
+    T_c = int(T_c)
+    Hq = q.shape[1] // D
+    assert q.shape == out.shape == (B * T_c, Hq * D) and q.stride(1) == 1 and out.stride(1) == 1
+    assert k_cache.stride()[2:] == (D, 1) and v_cache.stride() == k_cache.stride() and v_cache.shape == k_cache.shape
+    assert k_cache.dtype == v_cache.dtype == q.dtype == out.dtype and kv_len.dtype == torch.int32 and kv_len.numel() >= B
+    assert kv_len.is_contiguous()
+    _lib.call("uamd_attn_extend", q, _lib.ptr(q), q.stride(0), _lib.ptr(k_cache), _lib.ptr(v_cache), k_cache.stride(0),
+              k_cache.stride(1), _lib.ptr(kv_len), T_c, _lib.ptr(out), out.stride(0), B, Hq, Hk, D, S_max, int(window),
+              float(scale), _lib.dtype_code(q.dtype), _lib.stream_of(q))
+    return out
+
+
 def ngram_draft(hist, hist_len, K, n_max, tok, n_draft):
     """The prompt-lookup draft of one sequence (uamd_ngram_draft; the rule is stated in include/unsloth_amd.h): hist int64 [cap],
     hist_len int32 [1] -> tok int64 [K + 1] = (last token, the draft, zeros), n_draft int32 [1]. Everything on the device."""

@@ -30,6 +30,10 @@ attention (uamd_attn_decode_shared) scores the n x G query rows of a (prompt, KV
 `generate(..., prompt_lookup_num_tokens=K)` (opt-in, one greedy sequence, 16-bit cache): every step verifies the last token and K
 drafts found in the sequence's own context as K + 1 token rows on one pass over the weights (uamd_ngram_draft, uamd_gemv_rows,
 uamd_rope_kv_append_span, uamd_attn_decode_span, uamd_accept_greedy), a third captured graph beside the greedy and the sampled step.
+`extend(ids[B, T_c])` (16-bit cache, no shared prompt): T_c more tokens per row behind what the cache holds -- the next chat turn,
+a tool result, a piece of `prefill(chunk=N)` -- through the training-path linears, uamd_rope_kv_append_span with R = T_c and
+uamd_attn_extend (the old cache and the chunk's causal triangle in one launch, every length from device memory); eager, and the
+captured steps go on from the new kv_len. `generate(..., append=True)` extends instead of prefilling.
 """
 import math
 import os
@@ -191,6 +195,9 @@ class DecodeEngine:
         self._graph_l = {}
         self._lk = None
         self.lookup_stats = None
+        # host mirror of the LARGEST kv_len (no sync): the prompt's width plus the tokens fed since. `extend` checks its
+        # capacity against it
+        self._fed = 0
 
     # ---- per-layer parameter tuples, read once (adapters must not be switched under a live engine) -------------------
     @staticmethod
@@ -204,15 +211,20 @@ class DecodeEngine:
 
     # ---- prefill: prompt through the training-path kernels, K / V into the cache -----------------------------------------
     @torch.no_grad()
-    def prefill(self, input_ids, attention_mask=None, repeat=1):
+    def prefill(self, input_ids, attention_mask=None, repeat=1, chunk=None):
         """The prompt(s) [B, T] through the training-path kernels; K / V into the cache, next-token logits out.
         `attention_mask`: a LEFT-padded key mask (`left_pad_lengths`); row b's L_b real tokens get RoPE positions 0 .. L_b - 1
         and cache positions [0, L_b), pad positions never enter the cache, kv_len[b] = L_b. `repeat` = n: the engine's batch is
-        B * n and every prompt's cache rows and logits are replicated to n adjacent rows (num_return_sequences)."""
+        B * n and every prompt's cache rows and logits are replicated to n adjacent rows (num_return_sequences).
+        `chunk` = N: the first N columns as above, the rest through `extend` in pieces of N -- the activations of a pass are
+        those of N tokens, not of T. The first piece must cover the longest padding."""
+        if chunk is not None:
+            return self._prefill_chunked(input_ids, attention_mask, repeat, int(chunk))
         from . import llama as _ll
         from ..kernels import attention as _flash
         B, T = input_ids.shape
         assert B * repeat == self.B and T <= self.S
+        self._fed = T
         assert self.share_prompt is None or repeat == self.share_prompt, "an engine with share_prompt = n prefills with repeat = n"
         lens = pad = seq_info = rope_pos = None
         if attention_mask is not None and not bool((attention_mask != 0).all()):
@@ -302,6 +314,69 @@ class DecodeEngine:
         xn = xn.view(B, -1)
         self.logits = self._lm_head(xn if repeat == 1 else xn.repeat_interleave(repeat, 0))
         return self.logits
+
+    # ---- extend: a chunk of tokens appended to the LIVE cache (the next turn, a piece of a chunked prefill) ---------------------
+    def _extend_scope(self, what):
+        if self.kv_cache_dtype is not None:
+            raise NotImplementedError(f"DecodeEngine.{what}: uamd_attn_extend reads a 16-bit cache (this engine's is FP8)")
+        if self.share_prompt is not None:
+            raise NotImplementedError(f"DecodeEngine.{what}: not built for an engine with share_prompt")
+
+    @torch.no_grad()
+    def extend(self, input_ids):
+        """T_c more tokens per sequence ([B, T_c]) behind what the cache holds; fp32 logits [B, V] of each row's last new
+        token. The linears are the training path's, as in `prefill`; per layer uamd_rope_kv_append_span puts token j of row b
+        at RoPE position and slot kv_len[b] + j and uamd_attn_extend attends the old cache and the chunk's causal triangle;
+        then kv_len += T_c. Every length stays on the device (eager: T_c varies); the captured steps read kv_len from there
+        and go on from the new length. Capacity is checked against the host-known bound on kv_len, before any launch."""
+        self._extend_scope("extend")
+        B, Tc = input_ids.shape
+        if B != self.B or Tc < 1:
+            raise ValueError(f"DecodeEngine.extend: input_ids [{self.B}, T_c >= 1] (got {tuple(input_ids.shape)})")
+        if self._fed + Tc > self.S:
+            raise ValueError(f"DecodeEngine.extend: {Tc} more tokens behind up to {self._fed} exceed the cache's {self.S} slots")
+        core = self.core
+        kw = dict(dtype=self.dtype, device=self.dev)
+        nq = self.Hq * self.D
+        resid, delta = core.embed_tokens(input_ids.to(self.dev)).to(self.dtype), None
+        for li, layer in enumerate(core.layers):
+            w1, e1 = self._params[li]["ln1"]
+            if delta is None:
+                x = rms_fwd(resid, w1, e1)[0].view(B, Tc, -1)
+            else:
+                resid, x, _ = add_rms_fwd(delta, resid, w1, e1)
+                resid, x = resid.view(B, Tc, -1), x.view(B, Tc, -1)
+            attn = layer.self_attn
+            qkv = torch.cat([t.reshape(B * Tc, -1) for t in attn.apply_qkv(attn, x)], dim=1)       # the fused q|k|v rows
+            _dk.rope_kv_append_span(qkv, self.cos, self.sin, self.kv_len, self.k_cache[li], self.v_cache[li], Tc,
+                                    self.Hq, self.Hk, self.D)
+            A = torch.empty(B * Tc, nq, **kw)
+            _dk.attn_extend(qkv[:, :nq], self.k_cache[li], self.v_cache[li], self.kv_len, Tc, A, self.scale, window=self.window)
+            o = attn.apply_o(attn, A.view(B, Tc, nq))
+            w2, e2 = self._params[li]["ln2"]
+            resid, x, _ = add_rms_fwd(o, resid, w2, e2)
+            resid, x = resid.view(B, Tc, -1), x.view(B, Tc, -1)
+            delta = layer.mlp(x)
+        _, xn, _ = add_rms_fwd(delta[:, -1:], resid[:, -1:], core.norm.weight, _eps(core.norm))
+        self.kv_len.add_(Tc)
+        self._fed += Tc
+        self.logits = self._lm_head(xn.view(B, -1))
+        return self.logits
+
+    def _prefill_chunked(self, input_ids, attention_mask, repeat, N):
+        self._extend_scope("prefill(chunk=N)")
+        T = input_ids.shape[1]
+        if N < 1:
+            raise ValueError(f"DecodeEngine.prefill: chunk >= 1 (got {N})")
+        assert T <= self.S
+        if attention_mask is not None and T > N and not bool((attention_mask[:, N - 1:] != 0).all()):
+            raise ValueError(f"DecodeEngine.prefill(chunk={N}): the first piece must cover the longest padding -- every row "
+                             "needs a real token among its first `chunk` columns")
+        logits = self.prefill(input_ids[:, :N], None if attention_mask is None else attention_mask[:, :N], repeat)
+        for s in range(N, T, N):
+            piece = input_ids[:, s:s + N]
+            logits = self.extend(piece if repeat == 1 else piece.repeat_interleave(repeat, 0))
+        return logits
 
     def _greedy(self):
         """next_tok = argmax of the step's logits, inside the captured step."""
@@ -477,6 +552,7 @@ class DecodeEngine:
         """Feed one token per sequence ([B] or [B, 1]); returns fp32 logits [B, V] for the next position."""
         self.tok.copy_(token_ids.view(self.B, 1))
         self._steps += 1
+        self._fed += 1
         if self._steps >= (1 << 22) - 8:                     # step * TAG_STRIDE would wrap: start the tags over on clean workspaces
             self.sync.ws.zero_()
             self.fpartials.ws.zero_()
@@ -621,6 +697,7 @@ class DecodeEngine:
             if done:
                 break
             self._lookup_step(K + 1, n_max)
+        self._fed = hist_len                                         # (kv_len is at most this)
         steps, drafted, accepted, tokens = lk["stats"].tolist()
         self.lookup_stats = dict(steps=steps, drafted=drafted, accepted=accepted, tokens=tokens, fallback=None)
         return hist[:hist_len].clone().view(1, -1)
@@ -628,7 +705,7 @@ class DecodeEngine:
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens=32, eos_token_id=None, do_sample=False, temperature=1.0, top_k=0,
                  generator=None, pad_token_id=None, top_p=1.0, min_p=0.0, attention_mask=None, num_return_sequences=1,
-                 prompt_lookup_num_tokens=None, max_matching_ngram_size=2):
+                 prompt_lookup_num_tokens=None, max_matching_ngram_size=2, append=False, prefill_chunk_size=None):
         """Greedy (default) or temperature / top-k / top-p / min-p sampling. Returns [B, T + new] token ids. Rows that have
         produced an end-of-sequence token keep emitting `pad_token_id` (default: the first eos id), like HF's generate.
         `attention_mask`: left-padded prompts (see `prefill`); the padded prompt is returned in front of the new tokens.
@@ -645,24 +722,36 @@ class DecodeEngine:
         agrees with is kept (uamd_ngram_draft, uamd_attn_decode_span, uamd_accept_greedy). The tokens are those of the plain
         steps up to the rounding of a batched step against a single one; `lookup_stats` = steps / drafted / accepted / tokens of
         the call. A call outside the path's scope (`_lookup_fallback`) runs the plain steps and says why in
-        `lookup_stats["fallback"]`; `lookup_stats` is None after a call without the keyword."""
+        `lookup_stats["fallback"]`; `lookup_stats` is None after a call without the keyword.
+        `append=True`: `input_ids` [B, T_c] are the tokens that FOLLOW what the cache holds (the next turn of a chat, a tool
+        result): the engine extends the live cache by them (`extend`) instead of prefilling and decodes as usual; returns
+        [B, T_c + new]. `prefill_chunk_size` = N: the prompt is prefilled in pieces of N (`prefill(chunk=N)`)."""
         input_ids = input_ids.to(self.dev)
         n = int(num_return_sequences or 1)
         if n > 1 and not do_sample:
             raise ValueError("greedy decoding returns one sequence per prompt: num_return_sequences > 1 needs do_sample=True")
+        if append:
+            self._extend_scope("generate(append=True)")
+            if n > 1 or (attention_mask is not None and not bool((attention_mask != 0).all())):
+                raise ValueError("generate(append=True): the rows of the live cache continue, one each, with unpadded tokens")
+        if prefill_chunk_size is not None:
+            self._extend_scope("generate(prefill_chunk_size=N)")
+        chunked = {} if prefill_chunk_size is None else dict(chunk=int(prefill_chunk_size))
         eos = None if eos_token_id is None else sorted(set(eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id]))
         self.lookup_stats = None
         K = int(prompt_lookup_num_tokens or 0)
         if K:
             why = self._lookup_fallback(K, input_ids.shape[1], max_new_tokens, do_sample or n > 1, attention_mask, eos)
+            if append:
+                why = "append=True"
             if why is None and max_new_tokens < 1:
                 why = "no new tokens"
             if why is None:
-                logits = self.prefill(input_ids, attention_mask)
+                logits = self.prefill(input_ids, attention_mask, **chunked)
                 self.sampling()
                 return self._generate_lookup(input_ids, logits, int(max_new_tokens), eos, K, max(1, int(max_matching_ngram_size or 2)))
             self.lookup_stats = dict(steps=0, drafted=0, accepted=0, tokens=0, fallback=why)
-        logits = self.prefill(input_ids, attention_mask, repeat=n)
+        logits = self.extend(input_ids) if append else self.prefill(input_ids, attention_mask, repeat=n, **chunked)
         if n > 1:
             input_ids = input_ids.repeat_interleave(n, 0)
         if do_sample:
@@ -677,6 +766,8 @@ class DecodeEngine:
         pad = pad_token_id if pad_token_id is not None else (eos[0] if eos else 0)
         done = torch.zeros(self.B, dtype=torch.bool, device=self.dev)
         room = self.S_n if self.share_prompt else self.S - input_ids.shape[1]      # (a shared prompt: the suffix caches' slots)
+        if append:
+            room = self.S - self._fed                # (what the earlier turns left)
         # a hand-off inside the fused decode launches that times out (csrc/decode.hip: a workgroup polled 2^18 times for a granule
         # that never came) poisons its output with NaN on purpose; NaN logits would otherwise turn into plausible-looking token ids
         # through argmax / multinomial. One element per row and token is accumulated (NaN * 0 = NaN) and looked at ONCE, after
@@ -737,7 +828,7 @@ def _eps(norm):
 _ENGINE_KWARGS = {"max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "do_sample", "temperature", "top_k", "top_p",
                   "min_p", "attention_mask", "use_cache", "generator", "max_seq_len", "return_dict_in_generate", "output_scores",
                   "generation_config", "tokenizer", "num_return_sequences", "kv_cache_dtype", "share_prompt_cache",
-                  "prompt_lookup_num_tokens", "max_matching_ngram_size"}
+                  "prompt_lookup_num_tokens", "max_matching_ngram_size", "prefill_chunk_size"}
 
 
 # generation_config fields the engine reads (below the explicit keywords, above the model's own generation config)
@@ -831,6 +922,8 @@ def route_generate(model, input_ids, max_new_tokens, kwargs):
         if do_sample or input_ids.shape[0] * n > 1:
             return "old", ["prompt_lookup_num_tokens with " + ("do_sample" if do_sample else "more than one sequence")]
         lookup = dict(prompt_lookup_num_tokens=K, max_matching_ngram_size=int(gen_default("max_matching_ngram_size", 2) or 2))
+    if kwargs.get("prefill_chunk_size", None):       # (the engine's own keyword; without it the settings are what they were)
+        lookup["prefill_chunk_size"] = int(kwargs["prefill_chunk_size"])
     return "engine", dict(max_new_tokens=int(max_new_tokens), eos_token_id=eos, pad_token_id=pad, do_sample=do_sample,
                           temperature=float(gen_default("temperature", 1.0)),
                           top_k=int(gen_default("top_k", 0) or 0) if do_sample else 0,
@@ -867,6 +960,18 @@ def wanted_share_prompt(model, share_prompt_cache=None):
     return False
 
 
+def wanted_prefill_chunk(model, prefill_chunk_size=None):
+    """The piece size a `generate` call prefills its prompt in (DecodeEngine.prefill(chunk=N)): its `prefill_chunk_size=`
+    keyword, else what `for_inference(model, prefill_chunk_size=N)` recorded on the model, else None (one pass)."""
+    if prefill_chunk_size is not None:
+        return int(prefill_chunk_size) or None
+    for m in (model, _base(model)):
+        mark = getattr(m, "_uamd_prefill_chunk_size", None)
+        if mark is not None:
+            return int(mark) or None
+    return None
+
+
 def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_len=None, **kwargs):
     """llama.py:2167-2259 counterpart: `model.generate(...)` after `FastLanguageModel.for_inference(model)`.
     The reference forwards every keyword to HF's generate; the engine covers greedy / temperature / top-k / top-p / min-p
@@ -880,7 +985,10 @@ def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_le
     input_ids = kwargs.pop("inputs", input_ids)
     kind = wanted_kv_cache(model, kwargs.pop("kv_cache_dtype", None))       # (the engine's own keyword: HF's generate has none)
     share = wanted_share_prompt(model, kwargs.pop("share_prompt_cache", None))      # (likewise)
+    chunk = wanted_prefill_chunk(model, kwargs.pop("prefill_chunk_size", None))     # (likewise)
     where, what = route_generate(model, input_ids, max_new_tokens, kwargs)
+    if where == "engine" and chunk:
+        what["prefill_chunk_size"] = chunk
     if where == "old":
         old = getattr(model, "_old_generate", None)
         if old is None:

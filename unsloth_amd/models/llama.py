@@ -784,13 +784,14 @@ class FastLlamaModel:
         return model
 
     @staticmethod
-    def for_inference(model, float8_kv_cache=None, share_prompt_cache=None):
+    def for_inference(model, float8_kv_cache=None, share_prompt_cache=None, prefill_chunk_size=None):
         """llama.py:3888-3929: eval mode, no checkpointing, and `model.generate` = the KV-cache decode engine
         (models/decode.py: unsloth_fast_generate, the counterpart of llama.py:2167-2259) for the architectures it covers
         (head_dim 64 or 128, SwiGLU); the HF `generate` stays reachable as `model._old_generate`, as in the reference.
         `float8_kv_cache` True / False: the engine's KV cache as e4m3 codes + per-key scales, or not (recorded on the model;
         None leaves what `from_pretrained(..., float8_kv_cache=)` recorded). `share_prompt_cache` True / False, recorded the
-        same way: `generate(..., num_return_sequences=n)` stores each prompt's K / V once for its n samples, or n times."""
+        same way: `generate(..., num_return_sequences=n)` stores each prompt's K / V once for its n samples, or n times.
+        `prefill_chunk_size` = N (0: off), recorded the same way: `generate` prefills its prompts in pieces of N tokens."""
         from types import MethodType
         from . import decode as _decode
         base = model.get_base_model() if hasattr(model, "get_base_model") else model
@@ -802,6 +803,8 @@ class FastLlamaModel:
             model._uamd_float8_kv_cache = bool(float8_kv_cache)
         if share_prompt_cache is not None:
             model._uamd_share_prompt_cache = bool(share_prompt_cache)
+        if prefill_chunk_size is not None:
+            model._uamd_prefill_chunk_size = int(prefill_chunk_size)
         cfg = base.config
         head_dim = getattr(cfg, "head_dim", None) or cfg.hidden_size // cfg.num_attention_heads
         if head_dim in _decode._dk.HEAD_DIMS and getattr(cfg, "hidden_act", "silu") == "silu" and not hasattr(model, "_old_generate"):

@@ -151,8 +151,8 @@ class FastLanguageModel:
         return FastLlamaModel.for_training(model, use_gradient_checkpointing)
 
     @staticmethod
-    def for_inference(model, float8_kv_cache=None, share_prompt_cache=None):
-        return FastLlamaModel.for_inference(model, float8_kv_cache, share_prompt_cache)
+    def for_inference(model, float8_kv_cache=None, share_prompt_cache=None, prefill_chunk_size=None):
+        return FastLlamaModel.for_inference(model, float8_kv_cache, share_prompt_cache, prefill_chunk_size)
 
 
 # VLM configs whose language tower is a Llama-family decoder the hand-kernel path covers (text_config.model_type -> the
