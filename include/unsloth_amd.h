@@ -112,6 +112,36 @@ int uamd_rope_embedding_qk(void* Q, int64_t q_batch_stride, int64_t q_head_strid
                            int n_heads_k, int head_dim, int backward, int q_dtype,
                            int table_dtype, void* stream);
 
+/* Per-head RMSNorm of q and k fused with RoPE (Qwen3: q_norm / k_norm, one weight of head_dim each, applied to every
+ * (token, head) row before the rotation), IN PLACE on the strided views of uamd_rope_embedding_qk (same strides, tables and
+ * rope_indices). head_dim 64 or 128; Q, K, the weights and the tables share one 16-bit `dtype`; pointers 8-byte aligned and
+ * strides multiples of 4 elements (UAMD_ERR_ALIGN otherwise). Per row, at the rounding points of transformers' Qwen3RMSNorm
+ * followed by apply_rotary_pos_emb:
+ *     r = rsqrt(mean(x^2) + eps) in fp32;  y = rn(x r);  z = rn(y w);  out = the rotation of z with every product and the
+ *     sum rounded to `dtype` (uamd_rope_embedding_qk's 16-bit arithmetic).
+ * fwd: r (fp32 [batch*seqlen, n_heads_q + n_heads_k], q heads first) and x_save (`dtype` [batch*seqlen, n_heads_q + n_heads_k,
+ *      head_dim] contiguous, the pre-norm rows) are what the backward needs; either may be NULL (inference).
+ * bwd: dQ, dK hold the gradients of the rotated outputs and receive the gradients of the pre-norm rows:
+ *      g = the rotation of dY with -sin;  dx = r (w g - xh mean(w g xh)),  xh = x r;  fp32 throughout, one rounding at the
+ *      store. The norm weights get no gradient (they are frozen under LoRA). */
+int uamd_qk_norm_rope_fwd(void* Q, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_seq_stride, void* K,
+                          int64_t k_batch_stride, int64_t k_head_stride, int64_t k_seq_stride, const void* q_weight,
+                          const void* k_weight, float eps, const void* cos, int64_t cos_row_stride, const void* sin,
+                          int64_t sin_row_stride, const int32_t* rope_indices, float* r, void* x_save, int batch,
+                          int seqlen, int n_heads_q, int n_heads_k, int head_dim, int dtype, void* stream);
+int uamd_qk_norm_rope_bwd(void* dQ, int64_t q_batch_stride, int64_t q_head_stride, int64_t q_seq_stride, void* dK,
+                          int64_t k_batch_stride, int64_t k_head_stride, int64_t k_seq_stride, const void* q_weight,
+                          const void* k_weight, const void* cos, int64_t cos_row_stride, const void* sin,
+                          int64_t sin_row_stride, const int32_t* rope_indices, const float* r, const void* x_saved,
+                          int batch, int seqlen, int n_heads_q, int n_heads_k, int head_dim, int dtype, void* stream);
+/* uamd_rope_kv_append (same qkv row, kv_len, rope_pos, s_max and 16-bit cache) with the per-head norm of uamd_qk_norm_rope_fwd
+ * applied to q and k before the rotation, through the same device function: the q it leaves in the row and the key it
+ * appends are bit-equal to that kernel's on the same token. D = 64 or 128. */
+int uamd_qk_norm_rope_kv_append(void* qkv, int64_t ld_qkv, const void* q_weight, const void* k_weight, float eps,
+                                const void* cos_t, const void* sin_t, int64_t ld_cs, const int* kv_len, const int* rope_pos,
+                                void* k_cache, void* v_cache, int64_t cache_sb, int64_t cache_sh, int B, int Hq, int Hk, int D,
+                                int s_max, int dtype, void* stream);
+
 /* Multimodal RoPE ("mrope", Qwen2-VL text tower; SURVEY 8 f4 / BASELINE config 4). The reference has no kernel for it
  * (its VLM path is the unsloth_zoo compiler); semantics = transformers' apply_multimodal_rotary_pos_emb:
  * positions3 = int32 [3, batch*seqlen] (temporal, height, width position per token); rotary pair j uses the temporal

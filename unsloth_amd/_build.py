@@ -21,6 +21,7 @@ SOURCES = [
     "rms_layernorm.hip",
     "layernorm.hip",
     "rope_embedding.hip",
+    "qk_norm_rope.hip",
     "glu.hip",
     "cross_entropy_loss.hip",
     "nf4.hip",
@@ -48,7 +49,12 @@ FILE_FLAGS = {"attention.hip": os.environ.get("UAMD_ATTN_CFLAGS", "-fno-slp-vect
               # glu.hip: no v_fma_mix* -- hipcc otherwise folds an fp32 multiply into the fp16 conversion (one rounding, and the sign
               # of a zero lost) for the elements its vectoriser did not pair, so a result depended on its position (the note in
               # front of fwd_one). A device feature: the host pass says it ignores it.
-              "glu.hip": ["-Xclang", "-target-feature", "-Xclang", "-fma-mix-insts"]}
+              "glu.hip": ["-Xclang", "-target-feature", "-Xclang", "-fma-mix-insts"],
+              # qk_norm_rope.hip: a row's bits must not depend on which of its kernels (training, decode append) computed it or on
+              # the element's position -- no packed fp32 instructions (the vectoriser pairs a lane's adjacent multiplies and adds)
+              # and, as in glu.hip, no v_fma_mix* (an fp32 multiply folded into the 16-bit conversion rounds once, not twice)
+              "qk_norm_rope.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
+                                   "-Xclang", "-target-feature", "-Xclang", "-fma-mix-insts"]}
 
 
 def _flags(source=None):

@@ -87,6 +87,15 @@ SIGNATURES = {
     "uamd_rope_embedding_qk_mrope": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                              c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int,
                                              c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "uamd_qk_norm_rope_fwd": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                      c_void_p, c_float, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                      c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "uamd_qk_norm_rope_bwd": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                      c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                      c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "uamd_qk_norm_rope_kv_append": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int,
+                                            c_int, c_int, c_void_p]),
     "uamd_swiglu_fg": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "uamd_swiglu_DWf_DW_dfg": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "uamd_geglu_exact_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),

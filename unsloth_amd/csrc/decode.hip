@@ -58,20 +58,7 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
     return v.u;
 }
 
-// Reductions on the VALU only (DPP), no LDS round trips: a ds_bpermute-based __shfl_xor costs ~100+ cycles of latency per
-// step, and a decode step is nothing but latency. lanes_sum<16>: every lane ends with the sum over its 16-lane row
-// (quad swaps, then the two mirror patterns pair each lane with the partial sum it is missing); lanes_sum<8> stops after
-// row_half_mirror, where every lane holds the sum of its 8-lane half row.
-#define UAMD_DPP_ADD(v, CTRL) ((v) + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, (v)), (CTRL), 0xf, 0xf, true)))
-template <int LANES>
-__device__ __forceinline__ float lanes_sum(float v) {
-    static_assert(LANES == 8 || LANES == 16, "half a DPP row or a whole one");
-    v = UAMD_DPP_ADD(v, 0xb1);      // quad_perm [1,0,3,2]
-    v = UAMD_DPP_ADD(v, 0x4e);      // quad_perm [2,3,0,1]
-    v = UAMD_DPP_ADD(v, 0x141);     // row_half_mirror
-    if constexpr (LANES == 16) v = UAMD_DPP_ADD(v, 0x140);     // row_mirror
-    return v;
-}
+// (lanes_sum, the DPP reduction over 8 or 16 lanes: common.h)
 __device__ __forceinline__ float row16_sum(float v) { return lanes_sum<16>(v); }
 __device__ __forceinline__ float wave_sum_dpp(float v) {            // wave-uniform total of all 64 lanes
     v = row16_sum(v);
@@ -1035,14 +1022,7 @@ int launch_gemv_rows_wide(const GemvRowsArgs& a, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------------------------
 // RoPE (rotate-half, the training kernel's arithmetic and rounding points) on the new token's q and k, and the
 // append of k, v to the cache at position kv_len[b]. qkv: [B, (Hq + 2 Hk) D] as the fused q|k|v GEMV wrote it.
-//
-// One rotated pair. Rounding points of the training kernel for 16-bit tables (csrc/rope_embedding.hip rotate<T, NATIVE>, i.e.
-// the reference's Triton arithmetic in the cos / sin dtype): every product and the sum are rounded to T.
-template <typename T>
-__device__ __forceinline__ void rope_pair(float x1, float x2, float c, float s, T& r1, T& r2) {
-    r1 = from_f32<T>(round_to<T>(x1 * c) - round_to<T>(x2 * s));
-    r2 = from_f32<T>(round_to<T>(x2 * c) + round_to<T>(x1 * s));
-}
+// (rope_pair, one rotated pair with the training kernel's rounding points: common.h)
 template <typename T>
 __global__ void __launch_bounds__(64) rope_append_kernel(T* __restrict__ qkv, int64_t ld_qkv, const T* __restrict__ cos_t,
                                                          const T* __restrict__ sin_t, int64_t ld_cs,

@@ -17,6 +17,8 @@ from .rope_embedding import (
     fast_rope_embedding,
     inplace_rope_embedding,
     fast_mrope_embedding,
+    fast_qk_norm_rope_embedding,
+    Fast_QKNorm_RoPE_Embedding,
     Fast_MRoPE_Embedding_QK,
     Fast_RoPE_Embedding,
     Fast_RoPE_Embedding_QK,

@@ -388,6 +388,18 @@ def rope_kv_append(qkv, cos, sin, kv_len, k_cache, v_cache, Hq, Hk, D, rope_pos=
               _lib.stream_of(qkv))
 
 
+def qk_norm_rope_kv_append(qkv, q_w, k_w, eps, cos, sin, kv_len, k_cache, v_cache, Hq, Hk, D, rope_pos=None):
+    """`rope_kv_append` for a model with per-head q_norm / k_norm (Qwen3; weights q_w, k_w [D] in qkv's dtype): the norm, then
+    the rotation, the training kernel's bits."""
+    B = qkv.shape[0]
+    assert qkv.stride(1) == 1 and k_cache.is_contiguous() and v_cache.is_contiguous() and kv_len.dtype == torch.int32
+    assert cos.stride(1) == 1 and sin.stride() == cos.stride() and cos.dtype == qkv.dtype == q_w.dtype == k_w.dtype
+    _lib.call("uamd_qk_norm_rope_kv_append", qkv, _lib.ptr(qkv), qkv.stride(0), _lib.ptr(q_w), _lib.ptr(k_w), float(eps),
+              _lib.ptr(cos), _lib.ptr(sin), cos.stride(0), _lib.ptr(kv_len), _lib.ptr(rope_pos) if rope_pos is not None else None,
+              _lib.ptr(k_cache), _lib.ptr(v_cache), k_cache.stride(0), k_cache.stride(1), B, Hq, Hk, D, k_cache.shape[2],
+              _lib.dtype_code(qkv.dtype), _lib.stream_of(qkv))
+
+
 def attn_decode(q, k_cache, v_cache, kv_len, out, partials, split_keys, scale, len_add=1, window=0):
     """q [B, Hq*D] (a view into the fused qkv row is fine), out [B, Hq*D]; partials fp32 [B, Hq, nsplit, D + 2]."""
     B, Hk, S_max, D = k_cache.shape

@@ -151,6 +151,85 @@ def fast_mrope_embedding(Q, K, cos, sin, positions3, mrope_section):
     return Fast_MRoPE_Embedding_QK.apply(Q, K, cos, sin, positions3, tuple(mrope_section))
 
 
+def qk_norm_rope_fwd_(Q, K, q_w, k_w, eps, cos, sin, idx, keep):
+    """Per-head RMSNorm (weights q_w / k_w [D]) + RoPE in place on Q [B,Hq,T,D], K [B,Hk,T,D] (strided views; `cos` / `sin`
+    through `_tables`, `idx` int32 [B*T] or None). `keep`: returns what the backward needs -- (r fp32 [B*T, Hq+Hk], the
+    pre-norm rows [B*T, Hq+Hk, D]), written by the same launch -- else (None, None)."""
+    B, Hq, T, D = Q.shape
+    Hk = K.shape[1]
+    if Q.stride(3) != 1 or K.stride(3) != 1:
+        raise ValueError("head_dim must be the contiguous dimension")
+    assert idx is not None or T <= cos.shape[0]
+    r = x = None
+    if keep:
+        r = torch.empty(B * T, Hq + Hk, dtype=torch.float32, device=Q.device)
+        x = torch.empty(B * T, Hq + Hk, D, dtype=Q.dtype, device=Q.device)
+    _lib.call("uamd_qk_norm_rope_fwd", Q, _lib.ptr(Q), Q.stride(0), Q.stride(1), Q.stride(2), _lib.ptr(K), K.stride(0),
+              K.stride(1), K.stride(2), _lib.ptr(q_w), _lib.ptr(k_w), float(eps), _lib.ptr(cos), cos.stride(0), _lib.ptr(sin),
+              sin.stride(0), _lib.ptr(idx), _lib.ptr(r), _lib.ptr(x), B, T, Hq, Hk, D, _lib.dtype_code(Q.dtype),
+              _lib.stream_of(Q))
+    return r, x
+
+
+def qk_norm_rope_bwd_(dQ, dK, q_w, k_w, cos, sin, idx, r, x):
+    """dQ, dK [B,H,T,D] (gradients of the rotated outputs) become the gradients of the pre-norm projections, in place."""
+    B, Hq, T, D = dQ.shape
+    _lib.call("uamd_qk_norm_rope_bwd", dQ, _lib.ptr(dQ), dQ.stride(0), dQ.stride(1), dQ.stride(2), _lib.ptr(dK), dK.stride(0),
+              dK.stride(1), dK.stride(2), _lib.ptr(q_w), _lib.ptr(k_w), _lib.ptr(cos), cos.stride(0), _lib.ptr(sin),
+              sin.stride(0), _lib.ptr(idx), _lib.ptr(r), _lib.ptr(x), B, T, Hq, dK.shape[1], D, _lib.dtype_code(dQ.dtype),
+              _lib.stream_of(dQ))
+
+
+def qk_norm_args(attn, dtype):
+    """(q_norm weight, k_norm weight, eps) of a Qwen3 attention module, the weights detached and in the activation dtype."""
+    if attn.q_norm.weight.requires_grad or attn.k_norm.weight.requires_grad:
+        raise NotImplementedError("q_norm / k_norm weights that require grad: uamd_qk_norm_rope_bwd forms no weight gradient (dW)")
+    q_w, k_w = attn.q_norm.weight.detach(), attn.k_norm.weight.detach()
+    if q_w.dtype != dtype:
+        q_w, k_w = q_w.to(dtype), k_w.to(dtype)
+    return q_w.contiguous(), k_w.contiguous(), float(attn.q_norm.variance_epsilon)
+
+
+class Fast_QKNorm_RoPE_Embedding(torch.autograd.Function):
+    """Qwen3: per-head RMSNorm of Q [B,Hq,T,D] and K [B,Hk,T,D] (frozen weights q_w, k_w [D]) and RoPE, one launch, in place
+    on the strided views like Fast_RoPE_Embedding_QK. Kept for the backward when an input needs a gradient: the pre-norm q|k
+    rows (written by the forward launch, no clone) and r -- B T (Hq + Hk) (2 D + 4) bytes."""
+
+    @staticmethod
+    def forward(ctx, Q, K, q_w, k_w, eps, cos, sin, rope_indices):
+        _lib.require_gpu(Q, K, q_w, k_w, cos, sin)
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            raise NotImplementedError("Fast_QKNorm_RoPE_Embedding: no gradient for the norm weights (dW)")
+        cos, sin = _tables(cos, sin)
+        if cos.dtype != Q.dtype:
+            cos, sin = cos.to(Q.dtype), sin.to(Q.dtype)
+        Q_out = Q if Q.stride(-1) == 1 else Q.contiguous()
+        K_out = K if K.stride(-1) == 1 else K.contiguous()
+        idx = None
+        if rope_indices is not None:
+            idx = rope_indices.reshape(-1).to(dtype=torch.int32, device=Q.device).contiguous()
+            assert idx.numel() == Q.shape[0] * Q.shape[2]
+        q_w, k_w = q_w.detach().to(Q.dtype).contiguous(), k_w.detach().to(Q.dtype).contiguous()
+        r, x = qk_norm_rope_fwd_(Q_out, K_out, q_w, k_w, eps, cos, sin, idx, ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        ctx.args = (q_w, k_w, cos, sin, idx, r, x)
+        return Q_out, K_out
+
+    @staticmethod
+    def backward(ctx, dQ, dK):
+        q_w, k_w, cos, sin, idx, r, x = ctx.args
+        ok = lambda g: g.stride(-1) == 1 and all(s % 4 == 0 for s in g.stride()[:3])
+        dQ = dQ if ok(dQ) else dQ.contiguous()
+        dK = dK if ok(dK) else dK.contiguous()
+        qk_norm_rope_bwd_(dQ, dK, q_w, k_w, cos, sin, idx, r, x)
+        return dQ, dK, None, None, None, None, None, None
+
+
+@torch.compiler.disable
+def fast_qk_norm_rope_embedding(Q, K, q_w, k_w, eps, cos, sin, rope_embedding_indices=None):
+    """Q [B,Hq,T,D], K [B,Hk,T,D] -> (Q, K) after Qwen3's q_norm / k_norm and RoPE; see Fast_QKNorm_RoPE_Embedding."""
+    return Fast_QKNorm_RoPE_Embedding.apply(Q, K, q_w, k_w, eps, cos, sin, rope_embedding_indices)
+
+
 def inplace_rope_embedding(Q, K, cos, sin, position_ids):
     """rope_embedding.py:435-439 (the reference's decode-time entry: rotate Q and K [B,H,T,D] in place at explicit
     `position_ids`). Here it is the SAME HIP kernel as training, with the positions as its per-token gather

@@ -34,6 +34,9 @@ uamd_rope_kv_append_span, uamd_attn_decode_span, uamd_accept_greedy), a third ca
 a tool result, a piece of `prefill(chunk=N)` -- through the training-path linears, uamd_rope_kv_append_span with R = T_c and
 uamd_attn_extend (the old cache and the chunk's causal triangle in one launch, every length from device memory); eager, and the
 captured steps go on from the new kv_len. `generate(..., append=True)` extends instead of prefilling.
+A model with per-head q_norm / k_norm (Qwen3): prefill through the fused norm + RoPE op, the plain and the batched step with
+uamd_qk_norm_rope_kv_append (the prefill's bits for a token's key), the 16-bit cache. The single-launch step, the FP8 cache,
+share_prompt, prompt-lookup and extend rotate inside kernels that know no norm: NotImplementedError before any launch.
 """
 import math
 import os
@@ -42,7 +45,7 @@ import torch
 
 from ..kernels import decode as _dk
 from ..kernels.rms_layernorm import add_rms_fwd, rms_fwd
-from ..kernels.rope_embedding import fast_rope_embedding
+from ..kernels.rope_embedding import fast_qk_norm_rope_embedding, fast_rope_embedding, qk_norm_args
 from ..kernels.swiglu import swiglu_fg_kernel
 from ..kernels.utils import get_lora_parameters_bias, matmul_lora
 
@@ -52,6 +55,12 @@ SPLIT_KEYS = 128
 def _base(model):
     m = model.get_base_model() if hasattr(model, "get_base_model") else model
     return m
+
+
+def has_qk_norm(model):
+    """Qwen3: the attention modules carry q_norm / k_norm, an RMSNorm over each head's vector of q and of k before RoPE."""
+    layers = getattr(getattr(_base(model), "model", None), "layers", None)
+    return bool(layers) and hasattr(layers[0].self_attn, "q_norm")
 
 
 # UNSLOTH_AMD_DECODE_FUSED=0: one token of one sequence as the 14 separate launches per layer of rounds 2-3 instead of 5.
@@ -113,6 +122,12 @@ class DecodeEngine:
             raise NotImplementedError(f"decode attention kernels: head_dim 64 or 128 only (got {self.D})")
         if getattr(cfg, "hidden_act", "silu") != "silu":
             raise NotImplementedError("decode path: SwiGLU MLP only")
+        # Qwen3 (q_norm / k_norm on every head before RoPE): the plain and the batched step with uamd_qk_norm_rope_kv_append and
+        # the 16-bit cache. Every other variant rotates inside a kernel that knows no norm and is refused before any launch.
+        self.qk_norm = has_qk_norm(model)
+        if self.qk_norm and (kv_cache_kind(kv_cache_dtype) is not None or share_prompt is not None):
+            raise NotImplementedError("decode of a model with q_norm / k_norm (Qwen3): the FP8 cache and share_prompt are not built "
+                                      "-- their kernels rotate q and k without the per-head norm")
         self.window = int(getattr(cfg, "sliding_window", None) or 0)
         self.scale = 1.0 / math.sqrt(self.D)
         self.rows = bool(BATCH_ROWS) and 2 <= batch <= _dk.MAX_ROWS_WIDE      # the batched step on uamd_gemv_rows / _rows64
@@ -181,6 +196,9 @@ class DecodeEngine:
         self._graph = None
         assert 5 * L + 1 < 1024, "hand-off tag sites: 5 per layer below UAMD_TAG_STRIDE"
         self._params = [self._layer_params(l) for l in self.core.layers]
+        if self.qk_norm:
+            for P, l in zip(self._params, self.core.layers):
+                P["qkn"] = qk_norm_args(l.self_attn, self.dtype)
         self._head = self.lm.lm_head.weight
         # sampling: None = the steps pick next_tok greedily; otherwise (`sampling()`) they draw it with uamd_sample_f32 from the
         # DEVICE parameter block and draw counter below -- settings, seed and counter change in place, so the captured sampled
@@ -275,7 +293,10 @@ class DecodeEngine:
             Q = Q.view(B, T, self.Hq, self.D).transpose(1, 2)
             K = K.view(B, T, self.Hk, self.D).transpose(1, 2)
             V = V.view(B, T, self.Hk, self.D).transpose(1, 2)
-            Q, K = fast_rope_embedding(Q, K, cos, sin, rope_pos)
+            if self.qk_norm:
+                Q, K = fast_qk_norm_rope_embedding(Q, K, *self._params[li]["qkn"], cos, sin, rope_pos)
+            else:
+                Q, K = fast_rope_embedding(Q, K, cos, sin, rope_pos)
             Kc, Vc = K, V
             if lens is not None:
                 zero = torch.zeros((), dtype=self.dtype, device=self.dev)
@@ -317,6 +338,8 @@ class DecodeEngine:
 
     # ---- extend: a chunk of tokens appended to the LIVE cache (the next turn, a piece of a chunked prefill) ---------------------
     def _extend_scope(self, what):
+        if self.qk_norm:
+            raise NotImplementedError(f"DecodeEngine.{what}: uamd_rope_kv_append_span knows no q_norm / k_norm (Qwen3)")
         if self.kv_cache_dtype is not None:
             raise NotImplementedError(f"DecodeEngine.{what}: uamd_attn_extend reads a 16-bit cache (this engine's is FP8)")
         if self.share_prompt is not None:
@@ -440,7 +463,8 @@ class DecodeEngine:
 
     @torch.no_grad()
     def _step_body(self):
-        if self.B == 1 and FUSED_STEP and self.kv_cache_dtype is None:       # (the single-launch attention reads a 16-bit cache)
+        # (the single-launch attention reads a 16-bit cache and rotates without a per-head norm)
+        if self.B == 1 and FUSED_STEP and self.kv_cache_dtype is None and not self.qk_norm:
             return self._step_body_fused()
         return self._step_body_plain()
 
@@ -449,6 +473,8 @@ class DecodeEngine:
         """One token of one sequence, 5 launches per decoder layer: q|k|v (residual add + RMSNorm inside), attention (RoPE,
         cache append and the split combine inside), o, gate|up (add + RMSNorm in, SwiGLU out), down; every LoRA `A x` inside
         the GEMV launch that consumes it."""
+        if self.qk_norm:
+            raise NotImplementedError("the single-launch decode step: uamd_attn_decode_fused knows no q_norm / k_norm (Qwen3)")
         H = self.cfg.hidden_size
         core = self.core
         resid = core.embed_tokens(self.tok).to(self.dtype).view(H)
@@ -530,8 +556,12 @@ class DecodeEngine:
                                        self.k_cache[li], self.v_cache[li], self.new_len, a_out, self.partials, SPLIT_KEYS,
                                        self.scale, len_add=1, window=self.window)
             else:
-                _dk.rope_kv_append(qkv, self.cos, self.sin, self.kv_len, self.k_cache[li], self.v_cache[li],
-                                   self.Hq, self.Hk, self.D)
+                if self.qk_norm:
+                    _dk.qk_norm_rope_kv_append(qkv, *P["qkn"], self.cos, self.sin, self.kv_len, self.k_cache[li], self.v_cache[li],
+                                               self.Hq, self.Hk, self.D)
+                else:
+                    _dk.rope_kv_append(qkv, self.cos, self.sin, self.kv_len, self.k_cache[li], self.v_cache[li],
+                                       self.Hq, self.Hk, self.D)
                 _dk.attn_decode(qkv[:, :self.Hq * self.D], self.k_cache[li], self.v_cache[li], self.kv_len, a_out,
                                 self.partials, SPLIT_KEYS, self.scale, len_add=1, window=self.window)
             (o,) = self._linear(a_out, P["o"])
@@ -740,6 +770,8 @@ class DecodeEngine:
         eos = None if eos_token_id is None else sorted(set(eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id]))
         self.lookup_stats = None
         K = int(prompt_lookup_num_tokens or 0)
+        if K and self.qk_norm:
+            raise NotImplementedError("prompt_lookup_num_tokens: uamd_rope_kv_append_span knows no q_norm / k_norm (Qwen3)")
         if K:
             why = self._lookup_fallback(K, input_ids.shape[1], max_new_tokens, do_sample or n > 1, attention_mask, eos)
             if append:
@@ -997,6 +1029,13 @@ def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_le
     batch, need = what.pop("batch"), what.pop("need")
     eng = getattr(model, "_uamd_decode_engine", None)
     n = what["num_return_sequences"]
+    if has_qk_norm(model):
+        # Qwen3: refused here, before an engine is built, rather than decoded by a kernel that rotates without the per-head norm
+        asked = [name for name, on in (("kv_cache_dtype='fp8'", kind == "fp8"), ("share_prompt_cache", share and n > 1),
+                                       ("prompt_lookup_num_tokens", what.get("prompt_lookup_num_tokens")),
+                                       ("prefill_chunk_size", what.get("prefill_chunk_size"))) if on]
+        if asked:
+            raise NotImplementedError(f"unsloth_fast_generate: {asked} not built for a model with q_norm / k_norm (Qwen3)")
     if share and n > 1:
         # one prompt cache for the n samples of a prompt: prompt capacity >= T, suffix capacity >= the call's new tokens
         if kind == "fp8":
@@ -1048,6 +1087,8 @@ def LlamaAttention_fast_forward_inference(self, hidden_states, past_key_value, p
     from ..kernels.utils import fast_linear_forward
     if attention_mask is not None:
         raise NotImplementedError("decode attention takes no padding mask; left-pad-free batches only")
+    if hasattr(self, "q_norm"):
+        raise NotImplementedError("LlamaAttention_fast_forward_inference: no q_norm / k_norm (Qwen3) here; DecodeEngine decodes it")
     cfg = self.config
     bsz = hidden_states.shape[0]
     Hq, Hk, D = cfg.num_attention_heads, cfg.num_key_value_heads, self.head_dim

@@ -36,7 +36,8 @@ from ..kernels.fast_lora import (
 )
 from ..kernels.rms_layernorm import add_rms_fwd, rms_bwd_, rms_fwd
 from ..kernels.utils import lora_linear_forward
-from ..kernels.rope_embedding import Fast_MRoPE_Embedding_QK, _launch_qk, _tables
+from ..kernels.rope_embedding import (Fast_MRoPE_Embedding_QK, _launch_qk, _tables, qk_norm_args, qk_norm_rope_bwd_,
+                                      qk_norm_rope_fwd_)
 from ..kernels.swiglu import swiglu_DWf_DW_dfg_kernel, swiglu_fg_kernel
 
 POLICIES = {"min": frozenset(), "attn": frozenset({"qkv", "h1"}), "all": frozenset({"x1", "qkv", "h1", "x2", "eg"})}
@@ -201,7 +202,7 @@ def _eps(norm):
 class _Static:
     """Non-tensor context of one layer call (weights, norm parameters, rope tables, band, shapes)."""
     __slots__ = ("projs", "biases", "w1", "w2", "eps1", "eps2", "cos", "sin", "idx", "band", "n_heads", "n_kv", "head_dim",
-                 "scale", "keep", "shape", "step_decode")
+                 "scale", "keep", "shape", "step_decode", "qk_norm")
 
 
 def _rope(st, q4, k4, backward):
@@ -213,6 +214,13 @@ def _rope(st, q4, k4, backward):
         Fast_MRoPE_Embedding_QK._run(q, k, st.cos, st.sin, pos3, int(sec[0]), int(sec[1]), backward)
     else:
         _launch_qk(q, k, st.cos, st.sin, st.idx, backward)
+
+
+def _qk_norm_rope(st, q4, k4, keep):
+    """Qwen3 (`st.qk_norm` = (q_norm weight, k_norm weight, eps)): per-head RMSNorm + RoPE in place on the [B, T, H, D]
+    projection outputs. `keep`: returns (r, pre-norm rows) for `_qk_norm_rope_bwd`."""
+    return qk_norm_rope_fwd_(q4.transpose(1, 2), k4.transpose(1, 2), st.qk_norm[0], st.qk_norm[1], st.qk_norm[2], st.cos, st.sin,
+                             st.idx, keep)
 
 
 def _with_bias(projs, biases, idx):
@@ -245,7 +253,10 @@ class DecoderLayerFunction(torch.autograd.Function):
         q4 = Q.view(B_, T_, st.n_heads, st.head_dim)
         k4 = K.view(B_, T_, st.n_kv, st.head_dim)
         v4 = V.view(B_, T_, st.n_kv, st.head_dim)
-        _rope(st, q4, k4, False)                                                                 # RoPE in place
+        if st.qk_norm is None:
+            _rope(st, q4, k4, False)                                                             # RoPE in place
+        else:
+            qk_kept = _qk_norm_rope(st, q4, k4, "qkv" in keep)                                   # q_norm / k_norm + RoPE in place
         O, lse = _flash.attn_forward(q4, k4, v4, st.scale, st.band)
         attn = O.view(-1, st.n_heads * st.head_dim)
         o, xa_o = w_forward(attn, projs[3] + (st.biases[3],))
@@ -259,6 +270,8 @@ class DecoderLayerFunction(torch.autograd.Function):
             saved.append(x1)
         if "qkv" in keep:
             saved += [Q, K, V, O, lse]
+            if st.qk_norm is not None:
+                saved += list(qk_kept)
         if "h1" in keep:
             saved.append(h1)
         if "x2" in keep:
@@ -291,6 +304,9 @@ class DecoderLayerFunction(torch.autograd.Function):
         if "qkv" in keep:
             Q, K, V, O, lse = rest[:5]
             del rest[:5]
+            if st.qk_norm is not None:
+                qk_kept = rest[:2]
+                del rest[:2]
         h1 = rest.pop(0) if "h1" in keep else None
         x2 = rest.pop(0) if "x2" in keep else None
         if "eg" in keep:
@@ -303,7 +319,10 @@ class DecoderLayerFunction(torch.autograd.Function):
                 Q, K, V = lora_linear_forward(x1, _with_bias(projs, st.biases, (0, 1, 2)))
                 q4 = Q.view(B_, T_, nh, hd)
                 k4 = K.view(B_, T_, nkv, hd)
-                _rope(st, q4, k4, False)
+                if st.qk_norm is None:
+                    _rope(st, q4, k4, False)
+                else:
+                    qk_kept = _qk_norm_rope(st, q4, k4, True)
                 O, lse = _flash.attn_forward(q4, k4, V.view(B_, T_, nkv, hd), st.scale, st.band)
             attn = O.view(-1, nh * hd)
             if h1 is None:
@@ -330,7 +349,11 @@ class DecoderLayerFunction(torch.autograd.Function):
             dq, dk, dv = _flash.attn_backward(d_attn.view(B_, T_, nh, hd), Q.view(B_, T_, nh, hd),
                                               K.view(B_, T_, nkv, hd), V.view(B_, T_, nkv, hd),
                                               O.view(B_, T_, nh, hd), lse, st.scale, st.band)
-            _rope(st, dq, dk, True)
+            if st.qk_norm is None:
+                _rope(st, dq, dk, True)
+            else:
+                qk_norm_rope_bwd_(dq.transpose(1, 2), dk.transpose(1, 2), st.qk_norm[0], st.qk_norm[1], st.cos, st.sin, st.idx,
+                                  *qk_kept)
             dx1, g_qkv = qkv_backward(dq.reshape(-1, nh * hd), dk.reshape(-1, nkv * hd), dv.reshape(-1, nkv * hd), x1,
                                       (xa_q, xa_k, xa_v), projs[0], projs[1], projs[2], True)
             # ---- norm1 backward + the residual path: d h0 = rms'(dx1) + d h1
@@ -363,6 +386,11 @@ def decoder_layer_forward(layer, residual, delta, cos, sin, rope_position_ids, b
         assert sum(st.idx[1]) == attn.head_dim // 2, "mrope_section must cover head_dim / 2 rotary pairs"
     else:
         st.idx = rope_position_ids
+    st.qk_norm = None
+    if hasattr(attn, "q_norm"):
+        if isinstance(st.idx, tuple):
+            raise NotImplementedError("multimodal RoPE together with q_norm / k_norm: uamd_qk_norm_rope_fwd takes one position stream")
+        st.qk_norm = qk_norm_args(attn, residual.dtype)
     st.band = band
     st.n_heads, st.n_kv, st.head_dim = cfg.num_attention_heads, cfg.num_key_value_heads, attn.head_dim
     st.scale = None

@@ -38,6 +38,7 @@ from ..kernels import (
     unsloth_fused_ce_loss,
 )
 from ..kernels.utils import invalidate_cast_cache, lora_linear_forward
+from ..kernels.rope_embedding import fast_qk_norm_rope_embedding, qk_norm_args
 from ..kernels.rms_layernorm import fast_add_rms_layernorm
 from ..utils.packing import (
     get_packed_info_from_kwargs,
@@ -213,7 +214,11 @@ def LlamaAttention_fast_forward(self, hidden_states, cos, sin, rope_position_ids
     Q = Q.view(bsz, q_len, n_heads, head_dim).transpose(1, 2)
     K = K.view(bsz, q_len, n_kv_heads, head_dim).transpose(1, 2)
     V = V.view(bsz, q_len, n_kv_heads, head_dim).transpose(1, 2)
-    if isinstance(rope_position_ids, tuple):                             # multimodal RoPE: (positions3, mrope_section)
+    if hasattr(self, "q_norm"):                                          # Qwen3: per-head RMSNorm of q and k, then RoPE, one launch
+        if isinstance(rope_position_ids, tuple):
+            raise NotImplementedError("multimodal RoPE together with q_norm / k_norm: uamd_qk_norm_rope_fwd takes one position stream")
+        Q, K = fast_qk_norm_rope_embedding(Q, K, *qk_norm_args(self, Q.dtype), cos, sin, rope_position_ids)
+    elif isinstance(rope_position_ids, tuple):                           # multimodal RoPE: (positions3, mrope_section)
         Q, K = fast_mrope_embedding(Q, K, cos, sin, rope_position_ids[0], rope_position_ids[1])
     else:
         Q, K = fast_rope_embedding(Q, K, cos, sin, rope_position_ids)    # in place on the strided views
@@ -587,7 +592,7 @@ class FastLlamaModel:
         """llama.py:2288-2320: class-level forward replacement + HF RMSNorm class swap + loss mapping."""
         import importlib
         from ..kernels import patch_loss_functions, patch_rms_layernorm
-        for modname, prefix in (("llama", "Llama"), ("mistral", "Mistral"), ("qwen2", "Qwen2")):
+        for modname, prefix in (("llama", "Llama"), ("mistral", "Mistral"), ("qwen2", "Qwen2"), ("qwen3", "Qwen3")):
             try:
                 mod = importlib.import_module(f"transformers.models.{modname}.modeling_{modname}")
             except Exception:

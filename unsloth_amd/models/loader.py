@@ -10,8 +10,8 @@ Differences forced by this image (no network, no bitsandbytes, no peft): `model_
 directory with HF weights, or a `config=` object for random-init (synthetic benchmarks, SURVEY 8(d));
 4-bit loading quantises on the GPU with our NF4 quantiser (unsloth_amd/nf4.py) or reads a local
 bitsandbytes-format checkpoint (`weight.absmax`, `weight.quant_map`, ... keys).
-Architectures: dispatch by config.model_type as loader.py:828-890; llama / mistral / qwen2 share the
-Llama patcher. Anything else raises (the reference sends it to the unsloth_zoo compiler path: out of scope).
+Architectures: dispatch by config.model_type as loader.py:828-890; llama / mistral / qwen2 / qwen3 share the
+Llama patcher (Qwen3: the per-head q_norm / k_norm run fused with RoPE, kernels/rope_embedding.py). Anything else raises (the reference sends it to the unsloth_zoo compiler path: out of scope).
 """
 import os
 
@@ -20,7 +20,7 @@ import torch
 from .llama import FastLlamaModel, quantize_model_nf4_
 from .. import nf4 as _nf4
 
-SUPPORTED = ("llama", "mistral", "qwen2")
+SUPPORTED = ("llama", "mistral", "qwen2", "qwen3")
 
 
 def _resolve_dtype(dtype):
@@ -75,6 +75,11 @@ class FastLanguageModel:
         if model_type not in SUPPORTED:
             raise NotImplementedError(
                 f"model_type={model_type!r}: the hand-kernel path covers {SUPPORTED} (loader.py:828-890).")
+        if model_type == "qwen3" and full_finetuning:
+            os.environ["UNSLOTH_ENABLE_FULL_FINETUNING"] = "0"          # (nothing was loaded: the switch set above goes back)
+            raise NotImplementedError(
+                "full_finetuning=True with a Qwen3 config: the fused per-head q_norm / k_norm + RoPE backward "
+                "(uamd_qk_norm_rope_bwd) forms no gradient for the norm weights (dW); LoRA / QLoRA freeze them.")
         if rope_scaling is not None:
             config.rope_scaling = rope_scaling
         FastLlamaModel.pre_patch()
