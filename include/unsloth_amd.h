@@ -731,6 +731,22 @@ int uamd_sample_f32(const float* logits, int64_t ld, int rows, int V, const uamd
                     const uint64_t* ctr, const float* u_in, int64_t* out, int* kept_out, float* thresh_out,
                     float* u_out, void* stream);
 
+/* Log-probability and entropy of the token a decode step chose, from the step's fp32 logits (csrc/token_logprob.hip): for each of
+ * `rows` (1 .. 64) rows b, with z = logits[b] * (1 / temperature),
+ *   out_lp[b * ld_out + *slot]  = z[tok[b]] - logsumexp(z)
+ *   out_ent[b * ld_out + *slot] = logsumexp(z) - sum softmax(z) z          (out_ent may be NULL)
+ * over the whole row of V logits: the temperature-scaled distribution BEFORE top-k / top-p / min-p, the one a teacher-forced
+ * forward scores the token under. logits: row stride `ld` elements (ld >= V, or 0), any 4-byte alignment; 1 <= V <= 2^30.
+ * tok: DEVICE int64 [rows]; a value outside [0, V) cannot be seen by the host: its read is clamped and its log-prob is NaN.
+ * sparams: the sampler's DEVICE parameter block, of which only the temperature is read (NULL: temperature 1, the greedy step);
+ * slot: DEVICE int32, the column to write (a value outside [0, ld_out) stores nothing). Both are read by the kernels, so a
+ * captured launch follows a change of settings and a column the caller advances.
+ * Two launches: min(64, ceil(V / 1024)) workgroups per row reduce contiguous slices to (max, sum exp, sum exp * (z - max)) in
+ * ws, one wave per row merges them in a fixed order: bit-reproducible. ws: rows * 64 * 3 floats. */
+int uamd_token_logprob_f32(const float* logits, int64_t ld, int rows, int V, const int64_t* tok,
+                           const uamd_sample_params* sparams, const int* slot, float* out_lp, float* out_ent,
+                           int64_t ld_out, float* ws, void* stream);
+
 /* uamd_lora_xa2: same contract as uamd_lora_xa for R <= 64, streaming version (csrc/lora_side.hip): 32 rows per
  * block, K split over 4 waves, X and W through a per-wave LDS-DMA ring, fixed-order reduction. */
 int uamd_lora_xa2(const void* X, int64_t ldx, const void* A, int64_t lda, float* out,

@@ -31,6 +31,7 @@ SOURCES = [
     "attention.hip",
     "decode.hip",
     "sampler.hip",
+    "token_logprob.hip",
     "adamw.hip",
 ]
 

@@ -664,3 +664,43 @@ def sample_f32(logits, params, ctr, out=None, ws=None, kept_out=None, thresh_out
     _lib.call("uamd_sample_f32", logits, _lib.ptr(logits), ld, rows, V, _lib.ptr(params), _lib.ptr(ctr), _lib.ptr(u_in),
               _lib.ptr(out), _lib.ptr(kept_out), _lib.ptr(thresh_out), _lib.ptr(u_out), _lib.stream_of(logits))
     return out
+
+
+TOKEN_LOGPROB_MAX_ROWS = 64
+
+
+def token_logprob_split(V):
+    """(parts, span) of uamd_token_logprob_f32 for a row of V logits: min(64, ceil(V / 1024)) contiguous slices of `span`
+    logits (a multiple of 4), the last one possibly short. The host statement of the C rule, for tests and byte counts."""
+    want = min(64, (V - 1) // 1024 + 1)
+    span = (-(-V // want) + 3) & ~3
+    return -(-V // span), span
+
+
+def token_logprob_f32(logits, tok, sparams, slot, out_lp, out_ent=None, ws=None):
+    """Log-prob (and entropy) of the chosen token of each row (uamd_token_logprob_f32, two launches): with z = logits *
+    (1 / temperature), out_lp[b, slot] = z[b, tok[b]] - logsumexp(z[b]) and out_ent[b, slot] = logsumexp(z[b]) - sum softmax(z[b])
+    z[b]. The distribution scored is the temperature-scaled, UNFILTERED one -- top-k, top-p and min-p are not applied -- which
+    is what get_per_token_logps_and_entropies computes for the same token.
+    logits fp32 [rows <= 64, V], unit stride along V, any row stride >= V and any 4-byte alignment; tok int64 [rows]; `sparams`
+    the block of `sample_params` (only its temperature is read) or None = temperature 1; `slot` int32 [1] on the device, the
+    column of out_lp / out_ent (contiguous fp32 [rows, cap]) to write. Block and slot are read on the device: a captured
+    launch follows `sample_params(out=...)` and `slot.add_(1)`. `ws`: fp32 [rows * 192] to reuse under a hipGraph."""
+    _lib.require_gpu(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and (logits.shape[1] == 1 or logits.stride(1) == 1)
+    rows, V = logits.shape
+    ld = logits.stride(0) if rows > 1 else V
+    dev = logits.device
+    assert tok.dtype == torch.long and tok.numel() == rows and tok.is_contiguous() and tok.device == dev
+    assert sparams is None or (sparams.dtype == torch.int32 and sparams.numel() >= 6 and sparams.is_contiguous() and sparams.device == dev)
+    assert slot.dtype == torch.int32 and slot.numel() == 1 and slot.device == dev
+    for t in (out_lp, out_ent):
+        assert t is None or (t.dtype == torch.float32 and t.dim() == 2 and t.shape == out_lp.shape and t.shape[0] == rows
+                             and t.is_contiguous() and t.device == dev)
+    if ws is None:
+        ws = torch.empty(rows * 64 * 3, dtype=torch.float32, device=dev)
+    assert ws.dtype == torch.float32 and ws.numel() >= rows * 64 * 3 and ws.is_contiguous() and ws.device == dev
+    _lib.call("uamd_token_logprob_f32", logits, _lib.ptr(logits), ld, rows, V, _lib.ptr(tok), _lib.ptr(sparams), _lib.ptr(slot),
+              _lib.ptr(out_lp), _lib.ptr(out_ent), out_lp.shape[1], _lib.ptr(ws),
+              _lib.stream_of(logits))
+    return out_lp

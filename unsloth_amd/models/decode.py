@@ -34,6 +34,9 @@ uamd_rope_kv_append_span, uamd_attn_decode_span, uamd_accept_greedy), a third ca
 a tool result, a piece of `prefill(chunk=N)` -- through the training-path linears, uamd_rope_kv_append_span with R = T_c and
 uamd_attn_extend (the old cache and the chunk's causal triangle in one launch, every length from device memory); eager, and the
 captured steps go on from the new kv_len. `generate(..., append=True)` extends instead of prefilling.
+`generate(..., output_logprobs=True, output_entropies=True)` / `track_logprobs()` (opt-in): every choice of next_tok, in any of the
+steps above, is followed by uamd_token_logprob_f32 on the same logits -- the token's log-prob and the distribution's entropy
+into [B, new] buffers at a device-side column, inside the captured step: a rollout's `old_per_token_logps` without a second forward.
 A model with per-head q_norm / k_norm (Qwen3): prefill through the fused norm + RoPE op, the plain and the batched step with
 uamd_qk_norm_rope_kv_append (the prefill's bits for a token's key), the 16-bit cache. The single-launch step, the FP8 cache,
 share_prompt, prompt-lookup and extend rotate inside kernels that know no norm: NotImplementedError before any launch.
@@ -208,6 +211,10 @@ class DecodeEngine:
         self._sparams = _dk.sample_params(self.dev)
         self._draw_ctr = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self._graph_s = None
+        # `track_logprobs()`: logprobs / entropies [B, new-token capacity] of the tokens the steps chose, written at column
+        # `_lp_slot` (device int32, advanced with every choice) by uamd_token_logprob_f32 right behind the argmax / the draw.
+        # None = off: the launch list and the buffers of an engine that never tracked
+        self.logprobs = self.entropies = self._lp_slot = self._lp_ws = None
         # prompt-lookup decoding (generate(prompt_lookup_num_tokens=K)): the verify step of R = K + 1 token rows, one capture
         # per (R, n-gram size); its device state (`_lookup_state`) is allocated by the first call that asks for it
         self._graph_l = {}
@@ -411,6 +418,43 @@ class DecodeEngine:
             _dk.argmax_f32(lg, out=self.next_tok, ws=self._amax_ws)
         else:
             self.next_tok.copy_(torch.argmax(lg, dim=-1))
+        self._score()
+
+    def track_logprobs(self, on=True, entropy=False):
+        """From now on every choice of next_tok -- `_greedy()` or `draw()`, inside a captured step or eager after `prefill` --
+        is followed by uamd_token_logprob_f32 on the same logits: `logprobs[b, i]` = log-prob of row b's i-th chosen token
+        under the temperature-scaled, unfiltered distribution (temperature 1 for a greedy step; top-k / top-p / min-p are not
+        applied), `entropies[b, i]` (with `entropy`) that distribution's entropy; i counts the choices since `_lp_slot` was
+        last zeroed. generate() sets all of this per call from its keywords -- a call without them turns tracking off -- so
+        only callers that drive prefill / draw / step themselves call it. Both are [B, cap] fp32 with cap the engine's
+        new-token capacity. Turning it on, off or changing `entropy` drops the captured steps -- their launch list changes;
+        off, the engine launches exactly what it did before."""
+        on = bool(on)
+        entropy = on and bool(entropy)
+        if (on, entropy) == (self._lp_slot is not None, self.entropies is not None):
+            return
+        self._graph = self._graph_s = None
+        self._graph_l = {}
+        self.logprobs = self.entropies = self._lp_slot = self._lp_ws = None
+        if not on:
+            return
+        if not 1 <= self.B <= _dk.TOKEN_LOGPROB_MAX_ROWS:
+            raise NotImplementedError(f"uamd_token_logprob_f32 scores up to {_dk.TOKEN_LOGPROB_MAX_ROWS} rows (batch {self.B})")
+        cap = self.S_n if self.share_prompt else self.S
+        kw = dict(dtype=torch.float32, device=self.dev)
+        self.logprobs = torch.zeros(self.B, cap, **kw)
+        if entropy:
+            self.entropies = torch.zeros(self.B, cap, **kw)
+        self._lp_slot = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self._lp_ws = torch.empty(self.B * 64 * 3, **kw)
+
+    def _score(self):
+        """The log-prob (and entropy) of next_tok under the logits it was chosen from, into column `_lp_slot`, which advances."""
+        if self._lp_slot is None:
+            return
+        _dk.token_logprob_f32(self.logits, self.next_tok, self._sparams if self._sample else None, self._lp_slot, self.logprobs,
+                              self.entropies, self._lp_ws)
+        self._lp_slot.add_(1)
 
     def sampling(self, temperature=None, top_k=0, top_p=1.0, min_p=0.0, seed=None):
         """`sampling()`: greedy steps. `sampling(temperature, top_k, top_p, min_p, seed)`: from now on `draw()` and every step
@@ -433,6 +477,7 @@ class DecodeEngine:
         assert lg.dtype == torch.float32 and lg.stride(-1) == 1
         _dk.sample_f32(lg, self._sparams, self._draw_ctr, out=self.next_tok)
         self._draw_ctr.add_(1)
+        self._score()
         return self.next_tok
 
     def _lm_head(self, x):                       # x [B, H] -> fp32 logits [B, V]
@@ -596,6 +641,7 @@ class DecodeEngine:
         if getattr(self, g) is None:
             # eager warm-up (first-use attribute calls, allocator growth), with the position restored afterwards
             kv0, ctr0 = self._lens.clone(), self._draw_ctr.clone()
+            slot0 = None if self._lp_slot is None else self._lp_slot.clone()
             self._step_body()
             self._lens.copy_(kv0)
             torch.cuda.synchronize()
@@ -606,6 +652,8 @@ class DecodeEngine:
             setattr(self, gl, self.logits)       # the graph's static output buffer (prefill() rebinds self.logits)
             self._lens.copy_(kv0)                # the capture itself does not execute
             self._draw_ctr.copy_(ctr0)
+            if slot0 is not None:
+                self._lp_slot.copy_(slot0)
         getattr(self, g).replay()
         self.logits = getattr(self, gl)
         return self.logits
@@ -735,7 +783,8 @@ class DecodeEngine:
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens=32, eos_token_id=None, do_sample=False, temperature=1.0, top_k=0,
                  generator=None, pad_token_id=None, top_p=1.0, min_p=0.0, attention_mask=None, num_return_sequences=1,
-                 prompt_lookup_num_tokens=None, max_matching_ngram_size=2, append=False, prefill_chunk_size=None):
+                 prompt_lookup_num_tokens=None, max_matching_ngram_size=2, append=False, prefill_chunk_size=None,
+                 output_logprobs=False, output_entropies=False):
         """Greedy (default) or temperature / top-k / top-p / min-p sampling. Returns [B, T + new] token ids. Rows that have
         produced an end-of-sequence token keep emitting `pad_token_id` (default: the first eos id), like HF's generate.
         `attention_mask`: left-padded prompts (see `prefill`); the padded prompt is returned in front of the new tokens.
@@ -755,7 +804,17 @@ class DecodeEngine:
         `lookup_stats["fallback"]`; `lookup_stats` is None after a call without the keyword.
         `append=True`: `input_ids` [B, T_c] are the tokens that FOLLOW what the cache holds (the next turn of a chat, a tool
         result): the engine extends the live cache by them (`extend`) instead of prefilling and decodes as usual; returns
-        [B, T_c + new]. `prefill_chunk_size` = N: the prompt is prefilled in pieces of N (`prefill(chunk=N)`)."""
+        [B, T_c + new]. `prefill_chunk_size` = N: the prompt is prefilled in pieces of N (`prefill(chunk=N)`).
+        `output_logprobs` / `output_entropies`: returns (sequences, logprobs[, entropies]) -- fp32 [B, new]: the log-prob each
+        new token had when it was chosen and the entropy of the distribution it was chosen from, computed inside the token step
+        from its logits (`track_logprobs`; `output_entropies` alone returns the log-probs too). The distribution is the
+        temperature-scaled, unfiltered one (temperature 1 when greedy): what get_per_token_logps_and_entropies gives for the
+        same tokens, without its forward. Columns after a row's end-of-sequence token hold 0.0. The prompt-lookup verify step
+        does not score its tokens: together with `prompt_lookup_num_tokens` this raises ValueError."""
+        want_lp = bool(output_logprobs or output_entropies)
+        if want_lp and prompt_lookup_num_tokens:
+            raise ValueError("output_logprobs / output_entropies with prompt_lookup_num_tokens: the verify step scores no tokens")
+        self.track_logprobs(want_lp, entropy=output_entropies)
         input_ids = input_ids.to(self.dev)
         n = int(num_return_sequences or 1)
         if n > 1 and not do_sample:
@@ -786,6 +845,8 @@ class DecodeEngine:
         logits = self.extend(input_ids) if append else self.prefill(input_ids, attention_mask, repeat=n, **chunked)
         if n > 1:
             input_ids = input_ids.repeat_interleave(n, 0)
+        if want_lp:
+            self._lp_slot.zero_()
         if do_sample:
             gdev = generator.device if generator is not None else self.dev
             seed = torch.randint(-(1 << 63), (1 << 63) - 1, (1,), dtype=torch.int64, device=gdev, generator=generator)
@@ -793,7 +854,10 @@ class DecodeEngine:
             self.draw()
         else:
             self.sampling()
+            if want_lp:
+                self._greedy()                       # the first token's score: the step's own call, eager on the prefill logits
         out = [input_ids]
+        alive = []                                   # per new column: the rows that had not finished before it
         eos_t = None if eos is None else torch.tensor(eos, device=self.dev)
         pad = pad_token_id if pad_token_id is not None else (eos[0] if eos else 0)
         done = torch.zeros(self.B, dtype=torch.bool, device=self.dev)
@@ -814,6 +878,8 @@ class DecodeEngine:
             if eos_t is not None:
                 nxt = torch.where(done, torch.full_like(nxt, pad), nxt)      # finished rows: padding from here on
             out.append(nxt.view(self.B, 1))
+            if want_lp:
+                alive.append(~done)
             if eos_t is not None:
                 done |= torch.isin(nxt, eos_t)
                 if bool(done.all()):
@@ -825,7 +891,12 @@ class DecodeEngine:
             raise RuntimeError("unsloth_amd decode: non-finite logits -- an in-launch hand-off of the fused decode step timed out "
                                "(not every workgroup of a launch was resident: a CU-masked / shared GPU?) or the model produced "
                                "NaN / inf. UNSLOTH_AMD_DECODE_FUSED=0 runs the 14-launch step without hand-offs.")
-        return torch.cat(out, dim=1)
+        if not want_lp:
+            return torch.cat(out, dim=1)
+        # column i was written by the i-th choice (the eager one, then one per step); a finished row's later columns are 0.0
+        keep = torch.stack(alive, dim=1) if alive else torch.zeros(self.B, 0, dtype=torch.bool, device=self.dev)
+        cut = lambda t: torch.where(keep, t[:, :keep.shape[1]], torch.zeros((), dtype=t.dtype, device=self.dev))
+        return (torch.cat(out, dim=1), cut(self.logprobs)) + ((cut(self.entropies),) if output_entropies else ())
 
 
 def filter_logits(logits, top_k=0, top_p=1.0, min_p=0.0):
@@ -1013,12 +1084,21 @@ def unsloth_fast_generate(model, input_ids=None, max_new_tokens=None, max_seq_le
     right-padded or holey attention_mask, ...) are handed to HF's own generate (`model._old_generate`) -- or raise when it is
     unavailable. `share_prompt_cache=True` (the keyword, or the model's record: `wanted_share_prompt`) with
     num_return_sequences = n > 1: the engine is built with share_prompt = n -- one prompt cache for the n samples of a prompt;
-    with n = 1 it does nothing."""
+    with n = 1 it does nothing. `output_logprobs=True` / `output_entropies=True` (the engine's own keywords): the return value is
+    DecodeEngine.generate's tuple (sequences, logprobs[, entropies]), one row per returned sequence under
+    num_return_sequences and share_prompt_cache; a call the engine's token step does not decode raises ValueError."""
     input_ids = kwargs.pop("inputs", input_ids)
     kind = wanted_kv_cache(model, kwargs.pop("kv_cache_dtype", None))       # (the engine's own keyword: HF's generate has none)
     share = wanted_share_prompt(model, kwargs.pop("share_prompt_cache", None))      # (likewise)
     chunk = wanted_prefill_chunk(model, kwargs.pop("prefill_chunk_size", None))     # (likewise)
+    # (likewise; only when asked for: without them the engine's call and its return value are what they were)
+    scores = {k: True for k in ("output_logprobs", "output_entropies") if kwargs.pop(k, False)}
     where, what = route_generate(model, input_ids, max_new_tokens, kwargs)
+    if scores and (where == "old" or what.get("prompt_lookup_num_tokens")):
+        raise ValueError(f"unsloth_fast_generate: {sorted(scores)} come from the decode engine's token step, which this call does "
+                         f"not take ({what if where == 'old' else 'prompt_lookup_num_tokens: the verify step scores no tokens'})")
+    if where == "engine":
+        what.update(scores)
     if where == "engine" and chunk:
         what["prefill_chunk_size"] = chunk
     if where == "old":
