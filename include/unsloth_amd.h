@@ -816,6 +816,24 @@ int uamd_adamw8_shard(float* p32, const void* g16, void* p16, uint8_t* m8, uint8
                       double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
                       double bias_correction2_sqrt, double grad_scale, int dtype, void* stream);
 
+/* Token embedding (csrc/embedding.hip), dtype bf16 / fp16, H % 8 == 0, rows moved as 16-byte vectors: every base pointer
+ * 16-byte aligned, every row stride >= H and a multiple of 8 elements (else UAMD_ERR_ALIGN).
+ * uamd_embedding_fwd: out[t, :] = W[ids[t], :] for t < n, the bits of the weight row. ids: DEVICE int64; an id outside [0, V)
+ * stores a zero row and reads nothing. */
+int uamd_embedding_fwd(const int64_t* ids, int64_t n, const void* W, int64_t ldw, int64_t V, int H, void* out, int64_t ld_out,
+                       int dtype, void* stream);
+/* uamd_embedding_bwd: dW[v, :] = sum of dY[t, :] over the tokens t with id v, from the ids SORTED ascending (stable) and
+ * order[i] = the token (row of dY) of sorted position i, both DEVICE int64 [n]. A run of equal ids is summed in fp32 in a fixed
+ * order -- ascending position within a 128-position segment, segments ascending -- and rounded once: bit-reproducible, no
+ * atomics. Ids outside [0, V) and ids equal to padding_idx (-1: none) contribute nothing; an order[i] outside [0, n) reads nothing.
+ *   mode 0: every row of dW[V, H] is written, rows without a token (and the padding row) with zeros;
+ *   mode 1: dW[v] = rn(fp32(dW[v]) + sum) for the rows that have a token, no other row is touched.
+ * ws: uamd_embedding_bwd_workspace(n, H) floats, 16-byte aligned (fp32 partial rows of the runs that cross a segment). */
+int64_t uamd_embedding_bwd_workspace(int64_t n, int H);
+int uamd_embedding_bwd(const int64_t* sorted_ids, const int64_t* order, int64_t n, const void* dY, int64_t ld_dy, void* dW,
+                       int64_t ld_dw, int64_t V, int H, int64_t padding_idx, int mode, float* ws, int64_t ws_elems, int dtype,
+                       void* stream);
+
 /* debug: (lane,reg) -> (row,col) map of v_mfma_f32_16x16x32_bf16; out = float[2][64][4] */
 int uamd_debug_mfma_probe(float* out, void* stream);
 

@@ -33,6 +33,7 @@ SOURCES = [
     "sampler.hip",
     "token_logprob.hip",
     "adamw.hip",
+    "embedding.hip",
 ]
 
 

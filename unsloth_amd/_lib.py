@@ -211,6 +211,10 @@ SIGNATURES = {
     "uamd_argmax_f32": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "uamd_sample_f32": (c_int, [c_void_p, c_int64, c_int, c_int] + [c_void_p] * 8),
     "uamd_token_logprob_f32": (c_int, [c_void_p, c_int64, c_int, c_int] + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p]),
+    "uamd_embedding_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "uamd_embedding_bwd_workspace": (c_int64, [c_int64, c_int]),
+    "uamd_embedding_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int64,
+                                   c_int, c_void_p, c_int64, c_int, c_void_p]),
     "uamd_debug_mfma_probe": (c_int, [c_void_p, c_void_p]),
 }
 

@@ -88,8 +88,9 @@ class FullGradBuckets:
                 flat_p = torch.zeros(padded, dtype=self.dtype, device=self.device)
                 flat_g = torch.zeros(padded, dtype=self.dtype, device=self.device)
                 # gradient arrivals that complete the bucket: ONE per parameter and backward. A tied embedding has two
-                # producers (lm_head's gradient and the embedding lookup's), but autograd sums them before AccumulateGrad:
-                # the post-accumulate hook fires once (tests/test_full_finetune_gloo.py counts it)
+                # producers (lm_head's gradient and the embedding lookup's): on the autograd path they are summed before
+                # AccumulateGrad and the post-accumulate hook fires once (tests/test_full_finetune_gloo.py counts it); as
+                # direct sinks they report through ready(), which waits for the second (`_half` below)
                 b = dict(names=[n for n, _ in items], params=[p for _, p in items], offsets=offs, numel=padded,
                          flat_p=flat_p, flat_g=flat_g, shard=padded // self.world_size, pending=0, handle=None,
                          launched=False, expected=len(items))
@@ -112,17 +113,22 @@ class FullGradBuckets:
         self.collectives = 0                   # reduce-scatters issued so far (telemetry: tests, bench)
         self._hooks = [p.register_post_accumulate_grad_hook(self._hook) for p in self.params]
         # direct sinks (kernels/utils.GRAD_SINKS): the weight-gradient GEMM / the norm dW kernel / the chunked lm_head
-        # gradient write into the bucket themselves. Tied embeddings keep the autograd path (two producers).
+        # gradient / the embedding's run-reduced gradient (uamd_embedding_bwd) write into the bucket themselves. A tied
+        # embedding has TWO such producers per backward: the lm_head gradient lands first (overwriting on the step's first
+        # micro-batch), the lookup's is added onto it, and the parameter counts as arrived after the second (`_half`).
         self._direct = set()
+        self._two_producers = set()
+        self._half = set()                     # tied ids one producer of which has reported in THIS backward
         if self.device.type == "cuda":
             from .kernels.utils import GRAD_SINKS
             for k in [k for k, ref in GRAD_SINKS.items() if ref() is None]:
                 del GRAD_SINKS[k]
             me = weakref.ref(self)
             for p in self.params:
-                if id(p) not in tied:
-                    GRAD_SINKS[id(p)] = me
-                    self._direct.add(id(p))
+                GRAD_SINKS[id(p)] = me
+                self._direct.add(id(p))
+                if id(p) in tied:
+                    self._two_producers.add(id(p))
         me_ = weakref.ref(self)
         for p in self.params:
             p._uamd_arena = me_
@@ -140,9 +146,12 @@ class FullGradBuckets:
         """The kernel that wrote / added into grad_view(p) has been enqueued."""
         self._written.add(id(p))
         p.grad = self._views[id(p)]
+        if id(p) in self._two_producers and id(p) not in self._half:
+            self._half.add(id(p))              # the other producer (or, failing one, the post-accumulate hook) completes it
+            return
         self._count(p)
 
-    # ---- autograd path (embeddings; everything on the CPU) ------------------------------------------------------------
+    # ---- autograd path (a producer outside the kernels; everything on the CPU) ----------------------------------------
     def _hook(self, p):
         v = self._views[id(p)]
         if p.grad is not None and p.grad.data_ptr() != v.data_ptr():
@@ -210,6 +219,7 @@ class FullGradBuckets:
         for b in self.buckets:
             b["pending"] = 0
         self._arrived.clear()
+        self._half.clear()
 
     def wait(self, bi):
         b = self.buckets[bi]

@@ -23,6 +23,7 @@ from .rope_embedding import (
     Fast_RoPE_Embedding,
     Fast_RoPE_Embedding_QK,
 )
+from .embedding import fast_embedding, Fast_Embedding
 from .swiglu import swiglu_fg_kernel, swiglu_DWf_DW_dfg_kernel
 from .geglu import (
     geglu_exact_forward_kernel,

@@ -32,6 +32,7 @@ from ..kernels import (
     apply_lora_o,
     apply_lora_qkv,
     fast_cross_entropy_loss,
+    fast_embedding,
     fast_rms_layernorm,
     fast_mrope_embedding,
     fast_rope_embedding,
@@ -259,12 +260,25 @@ def LlamaDecoderLayer_fused_residual_forward(self, residual, delta, cos, sin, ro
     return hidden, self.mlp(x)
 
 
+def _embed_tokens(embed, input_ids):
+    """`embed(input_ids)`: through the gather kernel (same bits; a trainable table gets its gradient from uamd_embedding_bwd,
+    written into its gradient sink) when `embed` is a plain torch.nn.Embedding whose 16-bit table is on the GPU; any other
+    module -- a wrapper, one with hooks or with torch's renormalising / sparse options, a table on the host -- is called."""
+    W = getattr(embed, "weight", None)
+    if (type(embed) is torch.nn.Embedding and W.is_cuda and W.dtype in (torch.bfloat16, torch.float16)
+            and W.shape[1] % 8 == 0 and W.is_contiguous() and W.data_ptr() % 16 == 0 and input_ids.device == W.device
+            and embed.max_norm is None and not embed.sparse and not embed.scale_grad_by_freq
+            and not embed._forward_hooks and not embed._forward_pre_hooks):
+        return fast_embedding(input_ids, W, embed.padding_idx)
+    return embed(input_ids)
+
+
 def LlamaModel_fast_forward(self, input_ids=None, attention_mask=None, position_ids=None, inputs_embeds=None,
                             **kwargs):
     """llama.py:866-1245, training path. `self` is the HF LlamaModel."""
     invalidate_cast_cache()          # cached bf16 copies of the LoRA factors live for ONE forward/backward
     if inputs_embeds is None:
-        inputs_embeds = self.embed_tokens(input_ids)
+        inputs_embeds = _embed_tokens(self.embed_tokens, input_ids)
     dtype = _model_dtype(self)
     hidden_states = inputs_embeds.to(dtype)                                        # :955-958
     bsz, q_len, _ = hidden_states.shape
