@@ -816,6 +816,42 @@ int uamd_adamw8_shard(float* p32, const void* g16, void* p16, uint8_t* m8, uint8
                       double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
                       double bias_correction2_sqrt, double grad_scale, int dtype, void* stream);
 
+/* Gradient clipping by global L2 norm, on the device (csrc/grad_norm.hip; torch.nn.utils.clip_grad_norm_ with
+ * error_if_nonfinite = False): the norm, the factor and the step that applies it never touch the host.
+ * uamd_grad_sumsq: partials[p] = sum of g[i]^2 over part p of the n elements of g (dtype fp32 / bf16 / fp16, any element-
+ * aligned address), for the P = uamd_grad_sumsq_parts(n) parts. Split: P = clamp(ceil(n / 8192), 1, 1024), L = ceil(n / P)
+ * rounded up to 8 elements, part p = [p * L, min(n, (p + 1) * L)) (an empty part stores 0): a function of n alone. Widths:
+ * every element is widened to fp64 and squared there (exact), every sum -- lane, wave, workgroup -- is fp64 in a fixed order;
+ * no atomics. The partials are the same bits on every launch and graph replay. partials: P doubles, 8-byte aligned.
+ * uamd_grad_clip_coef: one wave adds n_arrays (1 .. 64) arrays of fp64 partials -- arrays / counts are HOST arrays of device
+ * pointers / lengths, so several buffers, or a value other ranks contributed to, are summed together -- and stores
+ *   *sumsq_out (fp64; NULL = not wanted)      the sum
+ *   norm_coef[0] = fp32(sqrt(sum))            the norm, one rounding
+ *   norm_coef[1] = fp32(min(1, max_norm / (norm_coef[0] + 1e-6)))    in fp64 from the STORED norm, one rounding
+ * (NULL = not wanted). A NaN norm gives a NaN factor, an infinite one 0, like torch. */
+int uamd_grad_sumsq_parts(int64_t n);
+int uamd_grad_sumsq(const void* g, int64_t n, int dtype, double* partials, void* stream);
+int uamd_grad_clip_coef(const double* const* arrays, const int* counts, int n_arrays, double max_norm, double* sumsq_out,
+                        float* norm_coef, void* stream);
+/* The four AdamW entry points above with the clipping factor read from the device: the gradient is multiplied by
+ * fp32(grad_scale) * *coef_dev (an fp32 product; coef_dev: norm_coef + 1 of uamd_grad_clip_coef, 4-byte aligned, not NULL),
+ * loaded once per thread. Everything else -- arguments, arithmetic, alignment rules, zero_grad -- is the plain entry point's;
+ * with *coef_dev == c they produce the bits the plain one gives for grad_scale = c and 1.0 respectively. */
+int uamd_adamw_flat_clip(float* p, float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, double bias_correction1, double bias_correction2_sqrt, double grad_scale,
+                         int zero_grad, const float* coef_dev, void* stream);
+int uamd_adamw_shard_clip(float* p32, const void* g16, void* p16, float* m, float* v, int64_t n, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, double bias_correction1,
+                          double bias_correction2_sqrt, double grad_scale, int dtype, const float* coef_dev, void* stream);
+int uamd_adamw8_flat_clip(float* p, float* g, uint8_t* m8, uint8_t* v8, float* absmax_m, float* absmax_v, const float* code_m,
+                          const float* code_v, int64_t n, double lr, double beta1, double beta2, double eps, double weight_decay,
+                          double bias_correction1, double bias_correction2_sqrt, double grad_scale, int zero_grad,
+                          const float* coef_dev, void* stream);
+int uamd_adamw8_shard_clip(float* p32, const void* g16, void* p16, uint8_t* m8, uint8_t* v8, float* absmax_m, float* absmax_v,
+                           const float* code_m, const float* code_v, int64_t n, int64_t decay_begin, int64_t decay_end,
+                           double lr, double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
+                           double bias_correction2_sqrt, double grad_scale, int dtype, const float* coef_dev, void* stream);
+
 /* Token embedding (csrc/embedding.hip), dtype bf16 / fp16, H % 8 == 0, rows moved as 16-byte vectors: every base pointer
  * 16-byte aligned, every row stride >= H and a multiple of 8 elements (else UAMD_ERR_ALIGN).
  * uamd_embedding_fwd: out[t, :] = W[ids[t], :] for t < n, the bits of the weight row. ids: DEVICE int64; an id outside [0, V)

@@ -33,6 +33,7 @@ SOURCES = [
     "sampler.hip",
     "token_logprob.hip",
     "adamw.hip",
+    "grad_norm.hip",
     "embedding.hip",
 ]
 

@@ -165,6 +165,16 @@ SIGNATURES = {
                          + [c_int, c_void_p]),
     "uamd_adamw8_flat": (c_int, [c_void_p] * 8 + [c_int64] + [ctypes.c_double] * 8 + [c_int, c_void_p]),
     "uamd_adamw8_shard": (c_int, [c_void_p] * 9 + [c_int64] * 3 + [ctypes.c_double] * 8 + [c_int, c_void_p]),
+    "uamd_grad_sumsq_parts": (c_int, [c_int64]),
+    "uamd_grad_sumsq": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "uamd_grad_clip_coef": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int), c_int, ctypes.c_double, c_void_p,
+                                    c_void_p, c_void_p]),
+    "uamd_adamw_flat_clip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + [ctypes.c_double] * 8
+                             + [c_int, c_void_p, c_void_p]),
+    "uamd_adamw_shard_clip": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + [ctypes.c_double] * 8
+                              + [c_int, c_void_p, c_void_p]),
+    "uamd_adamw8_flat_clip": (c_int, [c_void_p] * 8 + [c_int64] + [ctypes.c_double] * 8 + [c_int, c_void_p, c_void_p]),
+    "uamd_adamw8_shard_clip": (c_int, [c_void_p] * 9 + [c_int64] * 3 + [ctypes.c_double] * 8 + [c_int, c_void_p, c_void_p]),
     "uamd_lora_tn": (c_int, [ctypes.POINTER(LoraTnProblem), c_int, c_int, c_void_p, c_int64, c_int, c_void_p]),
     "uamd_attn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64), c_int, c_int,
                               c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_int, c_void_p]),

@@ -39,7 +39,20 @@ __device__ __forceinline__ void adamw_one(float& p, float& g, float& m, float& v
     p = sub_keep(p, a.step_size * m / denom);
 }
 
-__global__ void __launch_bounds__(256) adamw_flat_kernel(AdamArgs a) {
+// The *_clip entry points pass the same arguments plus `coef`, a DEVICE float (the clipping factor uamd_grad_clip_coef left
+// there): the gradient is scaled by grad_scale * *coef, one scalar load per thread. The kernels are templates over the
+// argument struct, so the instantiations of the plain entry points take the arguments and run the code they always did.
+struct AdamClipArgs { AdamArgs a; const float* coef; };
+__device__ __forceinline__ AdamArgs adam_args(const AdamArgs& a) { return a; }
+__device__ __forceinline__ AdamArgs adam_args(const AdamClipArgs& c) {
+    AdamArgs a = c.a;
+    a.grad_scale = c.a.grad_scale * *c.coef;
+    return a;
+}
+
+template <typename A>
+__global__ void __launch_bounds__(256) adamw_flat_kernel(A in) {
+    const AdamArgs a = adam_args(in);
     const int64_t n4 = a.n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
@@ -68,8 +81,9 @@ __global__ void __launch_bounds__(256) adamw_flat_kernel(AdamArgs a) {
 // rank's SHARD of a flat bucket, the gradient shard in the model's 16-bit dtype (what the reduce-scatter delivered), and
 // the updated parameters written back in the 16-bit dtype into the bucket slice the all-gather then broadcasts.
 // 14 B read + 14 B written per parameter.
-template <typename T>
-__global__ void __launch_bounds__(256) adamw_shard_kernel(AdamArgs a, const T* __restrict__ g16, T* __restrict__ p16) {
+template <typename T, typename A>
+__global__ void __launch_bounds__(256) adamw_shard_kernel(A in, const T* __restrict__ g16, T* __restrict__ p16) {
+    const AdamArgs a = adam_args(in);
     const int64_t n4 = a.n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
@@ -128,8 +142,17 @@ __device__ __forceinline__ uint32_t adam8_encode(float x, const float* __restric
 
 // T = float: the flat LoRA arena (fp32 gradient in a.g, zeroed when a.zero_grad); T = bf16 / fp16: a full fine-tuning shard
 // (gradient g16, updated parameters rounded once into p16).
-template <typename T>
-__global__ void __launch_bounds__(256) adamw8_kernel(Adam8Args q, const T* __restrict__ g16, T* __restrict__ p16) {
+struct Adam8ClipArgs { Adam8Args q; const float* coef; };
+__device__ __forceinline__ const Adam8Args& adam8_args(const Adam8Args& q) { return q; }
+__device__ __forceinline__ Adam8Args adam8_args(const Adam8ClipArgs& c) {
+    Adam8Args q = c.q;
+    q.a.grad_scale = c.q.a.grad_scale * *c.coef;
+    return q;
+}
+
+template <typename T, typename A>
+__global__ void __launch_bounds__(256) adamw8_kernel(A in, const T* __restrict__ g16, T* __restrict__ p16) {
+    const Adam8Args q = adam8_args(in);
     constexpr bool FLAT = std::is_same<T, float>::value;
     __shared__ float s_code[2][256];
     __shared__ float s_mids[2][256];
@@ -252,9 +275,7 @@ static unsigned adam8_grid(int64_t n) {
 
 static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
-}  // namespace
-
-extern "C" int uamd_adamw8_flat(float* p, float* g, uint8_t* m8, uint8_t* v8, float* absmax_m, float* absmax_v,
+static int adamw8_flat_step(const float* coef, float* p, float* g, uint8_t* m8, uint8_t* v8, float* absmax_m, float* absmax_v,
                                 const float* code_m, const float* code_v, int64_t n, double lr, double beta1, double beta2,
                                 double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt,
                                 double grad_scale, int zero_grad, void* stream) {
@@ -267,12 +288,16 @@ extern "C" int uamd_adamw8_flat(float* p, float* g, uint8_t* m8, uint8_t* v8, fl
     adam8_scalars(q.a, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2_sqrt, grad_scale);
     q.m8 = m8; q.v8 = v8; q.absmax_m = absmax_m; q.absmax_v = absmax_v; q.code_m = code_m; q.code_v = code_v;
     q.decay_begin = 0; q.decay_end = n;
-    hipLaunchKernelGGL((adamw8_kernel<float>), dim3(adam8_grid(n)), dim3(256), 0, (hipStream_t)stream, q,
-                       (const float*)nullptr, (float*)nullptr);
+    if (coef)
+        hipLaunchKernelGGL((adamw8_kernel<float, Adam8ClipArgs>), dim3(adam8_grid(n)), dim3(256), 0, (hipStream_t)stream,
+                           Adam8ClipArgs{q, coef}, (const float*)nullptr, (float*)nullptr);
+    else
+        hipLaunchKernelGGL((adamw8_kernel<float, Adam8Args>), dim3(adam8_grid(n)), dim3(256), 0, (hipStream_t)stream, q,
+                           (const float*)nullptr, (float*)nullptr);
     return uamd_launch_status();
 }
 
-extern "C" int uamd_adamw8_shard(float* p32, const void* g16, void* p16, uint8_t* m8, uint8_t* v8, float* absmax_m,
+static int adamw8_shard_step(const float* coef, float* p32, const void* g16, void* p16, uint8_t* m8, uint8_t* v8, float* absmax_m,
                                  float* absmax_v, const float* code_m, const float* code_v, int64_t n, int64_t decay_begin,
                                  int64_t decay_end, double lr, double beta1, double beta2, double eps, double weight_decay,
                                  double bias_correction1, double bias_correction2_sqrt, double grad_scale, int dtype,
@@ -289,11 +314,13 @@ extern "C" int uamd_adamw8_shard(float* p32, const void* g16, void* p16, uint8_t
     q.m8 = m8; q.v8 = v8; q.absmax_m = absmax_m; q.absmax_v = absmax_v; q.code_m = code_m; q.code_v = code_v;
     q.decay_begin = decay_begin; q.decay_end = decay_end;
     hipStream_t st = (hipStream_t)stream;
-    UAMD_DISPATCH_HALF(dtype, hipLaunchKernelGGL((adamw8_kernel<T>), dim3(adam8_grid(n)), dim3(256), 0, st, q, (const T*)g16, (T*)p16))
+    UAMD_DISPATCH_HALF(dtype,
+        if (coef) hipLaunchKernelGGL((adamw8_kernel<T, Adam8ClipArgs>), dim3(adam8_grid(n)), dim3(256), 0, st, Adam8ClipArgs{q, coef}, (const T*)g16, (T*)p16);
+        else hipLaunchKernelGGL((adamw8_kernel<T, Adam8Args>), dim3(adam8_grid(n)), dim3(256), 0, st, q, (const T*)g16, (T*)p16))
     return uamd_launch_status();
 }
 
-extern "C" int uamd_adamw_shard(float* p32, const void* g16, void* p16, float* m, float* v, int64_t n, double lr,
+static int adamw_shard_step(const float* coef, float* p32, const void* g16, void* p16, float* m, float* v, int64_t n, double lr,
                                 double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
                                 double bias_correction2_sqrt, double grad_scale, int dtype, void* stream) {
     if (!p32 || !g16 || !p16 || !m || !v || n < 0) return UAMD_ERR_ARG;
@@ -313,11 +340,13 @@ extern "C" int uamd_adamw_shard(float* p32, const void* g16, void* p16, float* m
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks < 1) blocks = 1;
     hipStream_t st = (hipStream_t)stream;
-    UAMD_DISPATCH_HALF(dtype, hipLaunchKernelGGL((adamw_shard_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, a, (const T*)g16, (T*)p16))
+    UAMD_DISPATCH_HALF(dtype,
+        if (coef) hipLaunchKernelGGL((adamw_shard_kernel<T, AdamClipArgs>), dim3((unsigned)blocks), dim3(256), 0, st, AdamClipArgs{a, coef}, (const T*)g16, (T*)p16);
+        else hipLaunchKernelGGL((adamw_shard_kernel<T, AdamArgs>), dim3((unsigned)blocks), dim3(256), 0, st, a, (const T*)g16, (T*)p16))
     return uamd_launch_status();
 }
 
-extern "C" int uamd_adamw_flat(float* p, float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
+static int adamw_flat_step(const float* coef, float* p, float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                                double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt,
                                double grad_scale, int zero_grad, void* stream) {
     if (!p || !g || !m || !v || n < 0) return UAMD_ERR_ARG;
@@ -336,6 +365,78 @@ extern "C" int uamd_adamw_flat(float* p, float* g, float* m, float* v, int64_t n
     int64_t blocks = (n4 + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;            // 16 blocks per CU, grid-stride beyond
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(adamw_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    if (coef) hipLaunchKernelGGL(adamw_flat_kernel<AdamClipArgs>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, AdamClipArgs{a, coef});
+    else hipLaunchKernelGGL(adamw_flat_kernel<AdamArgs>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     return uamd_launch_status();
+}
+
+}  // namespace
+
+// The plain entry points (coef = NULL: the kernels' AdamArgs / Adam8Args instantiations) and their *_clip twins, which take
+// the DEVICE clipping factor as one more pointer in front of the stream (4-byte aligned, not NULL).
+#define UAMD_CLIP_PTR_CHECK(c) \
+    if (!(c)) return UAMD_ERR_ARG; \
+    if (reinterpret_cast<uintptr_t>(c) & 3) return UAMD_ERR_ALIGN;
+
+extern "C" int uamd_adamw_flat(float* p, float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
+                               double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt,
+                               double grad_scale, int zero_grad, void* stream) {
+    return adamw_flat_step(nullptr, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2_sqrt,
+                           grad_scale, zero_grad, stream);
+}
+extern "C" int uamd_adamw_flat_clip(float* p, float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
+                                    double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt,
+                                    double grad_scale, int zero_grad, const float* coef_dev, void* stream) {
+    UAMD_CLIP_PTR_CHECK(coef_dev)
+    return adamw_flat_step(coef_dev, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2_sqrt,
+                           grad_scale, zero_grad, stream);
+}
+
+extern "C" int uamd_adamw_shard(float* p32, const void* g16, void* p16, float* m, float* v, int64_t n, double lr,
+                                double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
+                                double bias_correction2_sqrt, double grad_scale, int dtype, void* stream) {
+    return adamw_shard_step(nullptr, p32, g16, p16, m, v, n, lr, beta1, beta2, eps, weight_decay, bias_correction1,
+                            bias_correction2_sqrt, grad_scale, dtype, stream);
+}
+extern "C" int uamd_adamw_shard_clip(float* p32, const void* g16, void* p16, float* m, float* v, int64_t n, double lr,
+                                     double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
+                                     double bias_correction2_sqrt, double grad_scale, int dtype, const float* coef_dev,
+                                     void* stream) {
+    UAMD_CLIP_PTR_CHECK(coef_dev)
+    return adamw_shard_step(coef_dev, p32, g16, p16, m, v, n, lr, beta1, beta2, eps, weight_decay, bias_correction1,
+                            bias_correction2_sqrt, grad_scale, dtype, stream);
+}
+
+extern "C" int uamd_adamw8_flat(float* p, float* g, uint8_t* m8, uint8_t* v8, float* absmax_m, float* absmax_v,
+                                const float* code_m, const float* code_v, int64_t n, double lr, double beta1, double beta2,
+                                double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt,
+                                double grad_scale, int zero_grad, void* stream) {
+    return adamw8_flat_step(nullptr, p, g, m8, v8, absmax_m, absmax_v, code_m, code_v, n, lr, beta1, beta2, eps, weight_decay,
+                            bias_correction1, bias_correction2_sqrt, grad_scale, zero_grad, stream);
+}
+extern "C" int uamd_adamw8_flat_clip(float* p, float* g, uint8_t* m8, uint8_t* v8, float* absmax_m, float* absmax_v,
+                                     const float* code_m, const float* code_v, int64_t n, double lr, double beta1, double beta2,
+                                     double eps, double weight_decay, double bias_correction1, double bias_correction2_sqrt,
+                                     double grad_scale, int zero_grad, const float* coef_dev, void* stream) {
+    UAMD_CLIP_PTR_CHECK(coef_dev)
+    return adamw8_flat_step(coef_dev, p, g, m8, v8, absmax_m, absmax_v, code_m, code_v, n, lr, beta1, beta2, eps, weight_decay,
+                            bias_correction1, bias_correction2_sqrt, grad_scale, zero_grad, stream);
+}
+
+extern "C" int uamd_adamw8_shard(float* p32, const void* g16, void* p16, uint8_t* m8, uint8_t* v8, float* absmax_m,
+                                 float* absmax_v, const float* code_m, const float* code_v, int64_t n, int64_t decay_begin,
+                                 int64_t decay_end, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                 double bias_correction1, double bias_correction2_sqrt, double grad_scale, int dtype,
+                                 void* stream) {
+    return adamw8_shard_step(nullptr, p32, g16, p16, m8, v8, absmax_m, absmax_v, code_m, code_v, n, decay_begin, decay_end, lr,
+                             beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2_sqrt, grad_scale, dtype, stream);
+}
+extern "C" int uamd_adamw8_shard_clip(float* p32, const void* g16, void* p16, uint8_t* m8, uint8_t* v8, float* absmax_m,
+                                      float* absmax_v, const float* code_m, const float* code_v, int64_t n, int64_t decay_begin,
+                                      int64_t decay_end, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                      double bias_correction1, double bias_correction2_sqrt, double grad_scale, int dtype,
+                                      const float* coef_dev, void* stream) {
+    UAMD_CLIP_PTR_CHECK(coef_dev)
+    return adamw8_shard_step(coef_dev, p32, g16, p16, m8, v8, absmax_m, absmax_v, code_m, code_v, n, decay_begin, decay_end, lr,
+                             beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2_sqrt, grad_scale, dtype, stream);
 }

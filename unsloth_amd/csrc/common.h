@@ -96,6 +96,33 @@ __device__ __forceinline__ float lanes_sum(float v) {
     return v;
 }
 
+// The same patterns on an fp64 value (two 32-bit DPP moves per step): every lane ends with the sum over its 16-lane row, bit
+// for bit the same in all 16 (each step adds the same two partial sums, in either order). wave_sum_dpp_f64 then adds the four
+// rows as (r0 + r1) + (r2 + r3), read with v_readlane: one fixed order for the whole wave, no LDS.
+template <int CTRL>
+__device__ __forceinline__ double dpp_add_f64(double v) {
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)b, CTRL, 0xf, 0xf, true);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(b >> 32), CTRL, 0xf, 0xf, true);
+    return v + __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double lanes16_sum_f64(double v) {
+    v = dpp_add_f64<0xb1>(v);       // quad_perm [1,0,3,2]
+    v = dpp_add_f64<0x4e>(v);       // quad_perm [2,3,0,1]
+    v = dpp_add_f64<0x141>(v);      // row_half_mirror
+    return dpp_add_f64<0x140>(v);   // row_mirror
+}
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, lane);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), lane);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double wave_sum_dpp_f64(double v) {
+    v = lanes16_sum_f64(v);
+    return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+}
+
 // One rotated RoPE pair. Rounding points of the training kernel for 16-bit tables (csrc/rope_embedding.hip rotate<T, NATIVE>, i.e.
 // the reference's Triton arithmetic in the cos / sin dtype): every product and the sum are rounded to T.
 template <typename T>

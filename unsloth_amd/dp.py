@@ -224,7 +224,14 @@ class LoRAGradArena:
                 p.grad = v
 
     def grad_norm(self):
-        return self.arena.norm()
+        """Global L2 norm of the arena, a 0-dim tensor. After finish() the arena is reduced and identical on every rank, so
+        the norm is local. On the GPU: uamd_grad_sumsq (fp64 sums, no host sync); a CPU arena (gloo) has torch's norm."""
+        if not self.arena.is_cuda:
+            return self.arena.norm()
+        if getattr(self, "_gn", None) is None:
+            from .optim import GRAD_PART_MIN, GradNorm
+            self._gn = GradNorm(self.arena.device, self.arena.numel() // GRAD_PART_MIN + 1)
+        return self._gn.run([self.arena], float("inf"), 1)[0].clone()
 
     @property
     def nbytes(self):

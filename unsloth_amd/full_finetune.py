@@ -302,13 +302,22 @@ class ShardedAdamW(torch.optim.Optimizer):
     code per element + one fp32 absmax per 256-element block (optim.py, `uamd_adamw8_shard`): 2 B + 8 B / 256 per parameter
     instead of 8 B. Quant blocks tile each shard from its element 0 and a bucket is ONE launch that carries the decaying
     range -- a block may straddle the boundary to the one-dimensional parameters and must be re-encoded exactly once. On CPU
-    tensors the same rule runs in torch (optim.adam8_step_host)."""
+    tensors the same rule runs in torch (optim.adam8_step_host).
+
+    `max_grad_norm` (None or 0 = off): every step clips the gradient to this global L2 norm, torch's clip_grad_norm_ rule. Each
+    rank sums the squares of ITS shards (uamd_grad_sumsq), the fp64 sums are all-reduced as one device scalar, the factor is
+    formed on the device (uamd_grad_clip_coef) and the *_clip AdamW entry points read it there: no host sync. The norm needs
+    every bucket's exchange, so the step waits for all of them before its first update. `last_grad_norm`: the pre-clip norm
+    of the step just taken, a 0-dim tensor on the buckets' device."""
 
     def __init__(self, model_or_buckets, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, process_group=None,
-                 optim_bits=32):
-        from .optim import QBLOCK, _check_bits, adam8_maps, adam8_zero_code
+                 optim_bits=32, max_grad_norm=None):
+        from .optim import QBLOCK, _check_bits, _check_max_grad_norm, adam8_maps, adam8_zero_code
         _check_bits(optim_bits)
         self.optim_bits = optim_bits
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        self.last_grad_norm = None
+        self._gn = None
         self.buckets = model_or_buckets if isinstance(model_or_buckets, FullGradBuckets) else \
             FullGradBuckets(model_or_buckets, process_group=process_group)
         super().__init__(list(self.buckets.params), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -362,16 +371,27 @@ class ShardedAdamW(torch.optim.Optimizer):
     def arena(self):                      # trainer.unsloth_train adopts `optimizer.arena` as the exchange object
         return self.buckets
 
-    def grad_norm(self):
-        """Global L2 norm of the (reduced) gradient: each rank's shard, summed over ranks. Waits for the exchange."""
+    def _norm(self, max_norm, row):
+        """fp32 {norm, coef} of the (reduced) gradient on the buckets' device: each rank's shards, the fp64 sums of squares
+        summed over ranks; coef = min(1, max_norm / (norm + 1e-6)) from the fp32 norm. Waits for the exchange."""
         B = self.buckets
-        sq = torch.zeros((), dtype=torch.float32, device=B.device)
         for bi in range(len(B.buckets)):
             B.wait(bi)
-            sq += B.grad_shard(bi).float().pow(2).sum()
+        shards = [B.grad_shard(bi) for bi in range(len(B.buckets))]
+        if B.device.type == "cuda":
+            from .optim import GRAD_PART_MIN, GradNorm
+            if self._gn is None:
+                self._gn = GradNorm(B.device, sum(s.numel() // GRAD_PART_MIN + 1 for s in shards))
+            return self._gn.run(shards, max_norm, row, B.group, B.world_size)
+        sq = torch.stack([s.double().square().sum() for s in shards]).sum().reshape(1)     # host arithmetic: the same rule
         if B.world_size > 1:
             dist.all_reduce(sq, op=dist.ReduceOp.SUM, group=B.group)
-        return sq.sqrt()
+        norm = sq.sqrt().float()
+        return torch.cat([norm, (max_norm / (norm.double() + 1e-6)).clamp(max=1.0).float()])
+
+    def grad_norm(self):
+        """Global L2 norm of the (reduced) gradient, a 0-dim tensor. Waits for the exchange."""
+        return self._norm(math.inf, 1)[0].clone()
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
@@ -386,21 +406,29 @@ class ShardedAdamW(torch.optim.Optimizer):
         bc2_sqrt = math.sqrt(1.0 - b2 ** self._t)
         B = self.buckets
         handles = []
+        clip = ()                                        # (device pointer of the clipping factor,) for the *_clip entry points
+        if self.max_grad_norm is not None:
+            out = self._norm(self.max_grad_norm, 0)
+            self.last_grad_norm = out[0]
+            if out.is_cuda:
+                clip = (out.data_ptr() + 4,)
+            else:                                        # host arithmetic: the fp32 product the kernels form
+                grad_scale = float(torch.tensor(grad_scale, dtype=torch.float32) * out[1])
         for bi in range(len(B.buckets)):                 # backward order: the first bucket's exchange finished first
             B.wait(bi)
             g16, p16 = B.grad_shard(bi), B.param_shard(bi)
             p32, m, v = self.master[bi], self.exp_avg[bi], self.exp_avg_sq[bi]
             if self.optim_bits == 8:
-                self._step8(bi, g16, p16, grp, bc1, bc2_sqrt, grad_scale)
+                self._step8(bi, g16, p16, grp, bc1, bc2_sqrt, grad_scale, clip)
             for a, e, decays in self._runs[bi] if self.optim_bits == 32 else ():
                 wd = float(grp["weight_decay"]) if decays else 0.0
                 if p32.is_cuda:
                     from . import _lib
                     es = g16.element_size()
-                    _lib.call("uamd_adamw_shard", p32, p32.data_ptr() + 4 * a, g16.data_ptr() + es * a, p16.data_ptr() + es * a,
-                              m.data_ptr() + 4 * a, v.data_ptr() + 4 * a, e - a, float(grp["lr"]), float(b1), float(b2),
-                              float(grp["eps"]), wd, bc1, bc2_sqrt, float(grad_scale), _lib.dtype_code(g16.dtype),
-                              _lib.stream_of(p32))
+                    _lib.call("uamd_adamw_shard_clip" if clip else "uamd_adamw_shard", p32, p32.data_ptr() + 4 * a,
+                              g16.data_ptr() + es * a, p16.data_ptr() + es * a, m.data_ptr() + 4 * a, v.data_ptr() + 4 * a,
+                              e - a, float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), wd, bc1, bc2_sqrt,
+                              float(grad_scale), _lib.dtype_code(g16.dtype), *clip, _lib.stream_of(p32))
                 else:                                    # host arithmetic of the gloo tests: the same formula in torch
                     g = g16[a:e].to(torch.float32) * grad_scale
                     p32[a:e].mul_(1.0 - grp["lr"] * wd)
@@ -420,7 +448,7 @@ class ShardedAdamW(torch.optim.Optimizer):
         t = self.exp_avg + self.exp_avg_sq + ((self.absmax_m + self.absmax_v) if self.optim_bits == 8 else [])
         return sum(x.numel() * x.element_size() for x in t)
 
-    def _step8(self, bi, g16, p16, grp, bc1, bc2_sqrt, grad_scale):
+    def _step8(self, bi, g16, p16, grp, bc1, bc2_sqrt, grad_scale, clip=()):
         """8-bit moments: the whole shard of bucket `bi` in one launch (one torch pass on the CPU)."""
         p32, m, v = self.master[bi], self.exp_avg[bi], self.exp_avg_sq[bi]
         b1, b2 = grp["betas"]
@@ -429,10 +457,10 @@ class ShardedAdamW(torch.optim.Optimizer):
                  float(grad_scale))
         if p32.is_cuda:
             from . import _lib
-            _lib.call("uamd_adamw8_shard", p32, p32.data_ptr(), g16.data_ptr(), p16.data_ptr(), m.data_ptr(),
-                      v.data_ptr(), self.absmax_m[bi].data_ptr(), self.absmax_v[bi].data_ptr(),
+            _lib.call("uamd_adamw8_shard_clip" if clip else "uamd_adamw8_shard", p32, p32.data_ptr(), g16.data_ptr(),
+                      p16.data_ptr(), m.data_ptr(), v.data_ptr(), self.absmax_m[bi].data_ptr(), self.absmax_v[bi].data_ptr(),
                       self.code_m.data_ptr(), self.code_v.data_ptr(), p32.numel(), d0, d1, *hyper,
-                      _lib.dtype_code(g16.dtype), _lib.stream_of(p32))
+                      _lib.dtype_code(g16.dtype), *clip, _lib.stream_of(p32))
         else:
             from .optim import adam8_step_host
             i = torch.arange(p32.numel())

@@ -9,7 +9,8 @@ them, and `uamd_adamw_flat` (csrc/adamw.hip) walks them once -- zeroing the grad
 the `zero_grad` of the next step.
 
 Interface: a torch.optim.Optimizer (param_groups / state / state_dict / LR schedulers / step hooks work as usual) with
-one parameter group. `step(grad_scale=...)` takes the clipping factor; parameters whose gradient is None are skipped
+one parameter group. `max_grad_norm` clips by global L2 norm inside the step, norm and factor computed and read on the device
+(GradNorm below, csrc/grad_norm.hip); `step(grad_scale=...)` takes a host factor that multiplies with it; parameters whose gradient is None are skipped
 like torch does (all parameters share one step counter: in LoRA training every factor gets a gradient every step). No CPU fallback: the step raises without the HIP library.
 
 `optim_bits=8` (the reference's optim="adamw_8bit", bitsandbytes' block-wise 8-bit AdamW): both moments are one uint8
@@ -81,19 +82,77 @@ def adam8_step_host(p32, g, m8, v8, absmax_m, absmax_v, code_m, code_v, decays, 
         dst.copy_(src)
 
 
+GRAD_PART_MIN = 8192          # uamd_grad_sumsq's smallest part (elements): a buffer of n elements has <= n / 8192 + 1 parts
+
+
+def _check_max_grad_norm(max_grad_norm):
+    """None or 0: no clipping (HF's `max_grad_norm=0` spelling of "off"); else a positive finite limit."""
+    if max_grad_norm is None or max_grad_norm == 0:
+        return None
+    if not (0.0 < max_grad_norm < math.inf):
+        raise ValueError(f"max_grad_norm must be None, 0 or a positive finite number, got {max_grad_norm!r}")
+    return float(max_grad_norm)
+
+
+class GradNorm:
+    """Global L2 norm of flat gradient buffers and the clipping factor, computed and kept on the device
+    (csrc/grad_norm.hip). One workspace, allocated once: the fp64 partials of every buffer back to back, the rank's fp64 sum
+    of squares (what a data-parallel group all-reduces) and two fp32 {norm, coef} pairs -- row 0 belongs to the optimizer's
+    step (`last_grad_norm` is a view of it), row 1 to grad_norm(), which may be called between steps."""
+
+    def __init__(self, device, max_partials):
+        self.partials = torch.zeros(max_partials, dtype=torch.float64, device=device)
+        self.sumsq = torch.zeros(1, dtype=torch.float64, device=device)
+        self.out = torch.zeros(2, 2, dtype=torch.float32, device=device)
+
+    def _finish(self, src, count, max_norm, sumsq_out, out):
+        arrays, counts = (_lib.c_void_p * 1)(src.data_ptr()), (_lib.c_int * 1)(count)
+        _lib.call("uamd_grad_clip_coef", src, arrays, counts, 1, max_norm, _lib.ptr(sumsq_out), _lib.ptr(out),
+                  _lib.stream_of(src))
+
+    def run(self, buffers, max_norm, row, group=None, world_size=1):
+        """{norm, coef} (a 2-element fp32 device tensor, `self.out[row]`) of the concatenation of `buffers`, flat contiguous
+        tensors of fp32 / bf16 / fp16; with `world_size` > 1 every rank passes ITS buffers and the sums of squares are
+        all-reduced over `group` between the two stages. Nothing is read back: no host sync."""
+        L = _lib.lib()
+        used = 0
+        for g in buffers:
+            _lib.require_gpu(g)
+            parts = L.uamd_grad_sumsq_parts(g.numel())
+            if used + parts > self.partials.numel():
+                raise RuntimeError("GradNorm: more partial sums than the workspace was sized for")
+            _lib.call("uamd_grad_sumsq", g, g.data_ptr(), g.numel(), _lib.dtype_code(g.dtype),
+                      self.partials.data_ptr() + 8 * used, _lib.stream_of(g))
+            used += parts
+        out = self.out[row]
+        if world_size > 1:
+            self._finish(self.partials, used, math.inf, self.sumsq, None)
+            torch.distributed.all_reduce(self.sumsq, op=torch.distributed.ReduceOp.SUM, group=group)
+            self._finish(self.sumsq, 1, max_norm, None, out)
+        else:
+            self._finish(self.partials, used, max_norm, None, out)
+        return out
+
+
 def _check_bits(optim_bits):
     if optim_bits not in (8, 32):
         raise ValueError(f"optim_bits must be 8 or 32, got {optim_bits!r}")
 
 
 class FlatAdamW(torch.optim.Optimizer):
-    def __init__(self, model, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, arena=None, optim_bits=32):
+    def __init__(self, model, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, arena=None, optim_bits=32,
+                 max_grad_norm=None):
         """`arena`: the dp.LoRAGradArena that already owns the gradients (data-parallel runs); else one is created
-        (single rank: no collective is ever issued)."""
+        (single rank: no collective is ever issued). `max_grad_norm`: clip the gradient to this global L2 norm in every
+        step, torch.nn.utils.clip_grad_norm_'s rule (HF's max_grad_norm; None or 0 = off). Norm, factor and the step that
+        applies it stay on the device; `last_grad_norm` is the pre-clip norm of the step just taken, a 0-dim device tensor
+        (reading it is the caller's sync)."""
         if not 0.0 <= lr or not 0.0 <= eps or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError("invalid AdamW hyper-parameters")
         _check_bits(optim_bits)
         self.optim_bits = optim_bits
+        self.max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        self.last_grad_norm = None
         if arena is None:
             # two live arenas over the same parameters would both hook gradient accumulation and fight over p.grad and
             # the fused-gradient sinks (the second one's copies racing the first one's collectives): refuse
@@ -138,6 +197,18 @@ class FlatAdamW(torch.optim.Optimizer):
                 off += k
         self._t = 0
         self._writes_seen = self.arena.writes    # arena.writes at the moment the arena was last known to be all zeros
+        self._gn = None                      # GradNorm workspace, allocated at the first norm
+
+    def _norm(self, runs, max_norm, row):
+        """{norm, coef} of the gradient in `runs`, on the device. Taken PER RUN and summed, not over the whole arena: the
+        arena's "ranges without a gradient are zero" does not hold at this point -- a range whose parameter had its
+        `grad` set to None after the backward wrote into it still holds that gradient, and torch's clip_grad_norm_ skips
+        such a parameter like the step does. One run (the whole arena) in a normal LoRA step."""
+        if self._gn is None:
+            # every run has at most len / GRAD_PART_MIN + 1 parts and there are at most as many runs as parameters
+            self._gn = GradNorm(self.flat_p.device, self.flat_p.numel() // GRAD_PART_MIN + len(self._views) + 1)
+        g = self.arena.arena
+        return self._gn.run([g[s:e] for s, e in runs], max_norm, row)
 
     # ------------------------------------------------------------------------------------------
     def _runs(self):
@@ -200,22 +271,27 @@ class FlatAdamW(torch.optim.Optimizer):
         runs = self._runs()
         _lib.require_gpu(self.flat_p)
         g = self.arena.arena
-        L = _lib.lib()
-        with _lib.device_ctx(self.flat_p):
-            hyper = (float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]), bc1, bc2_sqrt,
-                     float(grad_scale), 1, _lib.stream_of(self.flat_p))
-            for s, e in runs:
-                # (a run that does not start on a 16-byte boundary cannot happen for LoRA factors: every numel is a
-                # multiple of 4; the C side checks. 8-bit runs start on a quant-block boundary.)
-                if self.optim_bits == 8:
-                    rc = L.uamd_adamw8_flat(self.flat_p.data_ptr() + 4 * s, g.data_ptr() + 4 * s, self.flat_m.data_ptr() + s,
-                                            self.flat_v.data_ptr() + s, self.absmax_m.data_ptr() + 4 * (s // QBLOCK),
-                                            self.absmax_v.data_ptr() + 4 * (s // QBLOCK), self.code_m.data_ptr(),
-                                            self.code_v.data_ptr(), e - s, *hyper)
-                else:
-                    rc = L.uamd_adamw_flat(self.flat_p.data_ptr() + 4 * s, g.data_ptr() + 4 * s,
-                                           self.flat_m.data_ptr() + 4 * s, self.flat_v.data_ptr() + 4 * s, e - s, *hyper)
-                _lib.check(rc, "uamd_adamw8_flat" if self.optim_bits == 8 else "uamd_adamw_flat")
+        hyper = (float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]), bc1, bc2_sqrt,
+                 float(grad_scale), 1)
+        name = "uamd_adamw8_flat" if self.optim_bits == 8 else "uamd_adamw_flat"
+        if self.max_grad_norm is not None:
+            # the *_clip entry points read the factor the norm kernels just left on the device (times grad_scale)
+            out = self._norm(runs, self.max_grad_norm, 0)
+            self.last_grad_norm = out[0]
+            hyper += (out.data_ptr() + 4,)
+            name += "_clip"
+        hyper += (_lib.stream_of(self.flat_p),)
+        for s, e in runs:
+            # (a run that does not start on a 16-byte boundary cannot happen for LoRA factors: every numel is a
+            # multiple of 4; the C side checks. 8-bit runs start on a quant-block boundary.)
+            if self.optim_bits == 8:
+                _lib.call(name, self.flat_p, self.flat_p.data_ptr() + 4 * s, g.data_ptr() + 4 * s, self.flat_m.data_ptr() + s,
+                          self.flat_v.data_ptr() + s, self.absmax_m.data_ptr() + 4 * (s // QBLOCK),
+                          self.absmax_v.data_ptr() + 4 * (s // QBLOCK), self.code_m.data_ptr(), self.code_v.data_ptr(),
+                          e - s, *hyper)
+            else:
+                _lib.call(name, self.flat_p, self.flat_p.data_ptr() + 4 * s, g.data_ptr() + 4 * s,
+                          self.flat_m.data_ptr() + 4 * s, self.flat_v.data_ptr() + 4 * s, e - s, *hyper)
         self._step_t += 1                    # (shared by every parameter's state entry)
         # every range that had a gradient is zero again; ranges without one were never written
         self._writes_seen = self.arena.writes
@@ -232,7 +308,8 @@ class FlatAdamW(torch.optim.Optimizer):
             p.grad = gv
 
     def grad_norm(self):
-        return self.arena.arena.norm()
+        """Global L2 norm of the gradients a step() would now use (uamd_grad_sumsq, fp64 sums): a 0-dim device tensor."""
+        return self._norm(self._runs(), math.inf, 1)[0].clone()
 
     def moments(self, p):
         """fp32 (exp_avg, exp_avg_sq) of parameter `p`, decoded from the codes and block scales with 8-bit state."""

@@ -125,14 +125,18 @@ OPTIM_32BIT = ("adamw_torch", "adamw_torch_fused")
 OPTIM_8BIT = ("adamw_8bit", "adamw_bnb_8bit", "paged_adamw_8bit")
 
 
-def make_optimizer(model, lr=None, weight_decay=0.01, betas=(0.9, 0.999), arena=None, flat=None, optim=None):
+def make_optimizer(model, lr=None, weight_decay=0.01, betas=(0.9, 0.999), arena=None, flat=None, optim=None,
+                   max_grad_norm=None):
     """AdamW on the trainable (LoRA) parameters. On the GPU with fp32 parameters: optim.FlatAdamW -- parameters,
     gradients and moments in flat arenas, ONE launch per step (`arena`: the dp.LoRAGradArena of a data-parallel run, else
     the optimizer creates its own). `flat=False` (or UNSLOTH_AMD_FLAT_ADAMW=0) keeps torch's fused AdamW.
     `optim`: HF TrainingArguments' spelling. None / "adamw_torch" / "adamw_torch_fused": fp32 moments. "adamw_8bit" /
     "adamw_bnb_8bit" / "paged_adamw_8bit" (the reference notebooks' default): block-wise 8-bit moments, `optim_bits=8` of
     FlatAdamW / ShardedAdamW ("paged" has no meaning without host paging: the same optimizer); needs the HIP path -- CPU
-    parameters or `flat=False` raise instead of substituting fp32 state."""
+    parameters or `flat=False` raise instead of substituting fp32 state.
+    `max_grad_norm` (HF TrainingArguments' name; None or 0 = off): clip the gradient to this global L2 norm inside every
+    step() -- norm, factor and the AdamW launch that reads it all on the device, `optimizer.last_grad_norm` the pre-clip norm
+    (FlatAdamW / ShardedAdamW). torch's AdamW has no such step: asking for it there raises."""
     if optim is not None and optim not in OPTIM_32BIT + OPTIM_8BIT:
         raise ValueError(f"make_optimizer: unknown optim={optim!r}; accepted: None, " + ", ".join(OPTIM_32BIT + OPTIM_8BIT))
     bits = 8 if optim in OPTIM_8BIT else 32
@@ -144,12 +148,16 @@ def make_optimizer(model, lr=None, weight_decay=0.01, betas=(0.9, 0.999), arena=
         # full fine-tuning: flat per-layer buckets + AdamW sharded over the data-parallel group (full_finetune.py)
         from .full_finetune import FullGradBuckets, ShardedAdamW
         return ShardedAdamW(arena if isinstance(arena, FullGradBuckets) else model, lr=lr, betas=betas,
-                            weight_decay=weight_decay, optim_bits=bits)
+                            weight_decay=weight_decay, optim_bits=bits, max_grad_norm=max_grad_norm)
     if flat is None:
         flat = FLAT_ADAMW
     if flat and params and all(p.is_cuda and p.dtype == torch.float32 for p in params):
         from .optim import FlatAdamW
-        return FlatAdamW(model, lr=lr, betas=betas, weight_decay=weight_decay, arena=arena, optim_bits=bits)
+        return FlatAdamW(model, lr=lr, betas=betas, weight_decay=weight_decay, arena=arena, optim_bits=bits,
+                         max_grad_norm=max_grad_norm)
+    if max_grad_norm:
+        raise NotImplementedError("make_optimizer: max_grad_norm is part of the flat HIP optimizers' step (FlatAdamW / "
+                                  "ShardedAdamW); with torch's AdamW call torch.nn.utils.clip_grad_norm_ before step()")
     if bits == 8:
         raise NotImplementedError(f"make_optimizer: optim={optim!r} runs on the flat HIP path only (fp32 LoRA parameters on "
                                   "the GPU, flat=True); there is no fp32 substitute for it")
@@ -176,27 +184,31 @@ def training_step(model, batch, optimizer, arena=None, num_items=None):
     return loss.detach()
 
 
-def unsloth_train(model, batches, optimizer=None, arena=None, max_steps=None, log_every=0):
+def unsloth_train(model, batches, optimizer=None, arena=None, max_steps=None, log_every=0, max_grad_norm=None):
     """trainer.py:49-57 counterpart for pre-tokenised batches (dicts with input_ids/labels[/position_ids/
-    packed_seq_lengths] already on the model's device). Returns the list of per-step losses."""
+    packed_seq_lengths] already on the model's device). Returns the list of per-step losses.
+    `max_grad_norm`: handed to the optimizer built here (make_optimizer); an optimizer passed in keeps its own setting. The
+    clipping adds no host sync to the step; with `log_every` the pre-clip norm is printed next to the loss."""
     model.train()
     if arena is None and optimizer is not None and getattr(optimizer, "arena", None) is not None:
         arena = optimizer.arena                    # FlatAdamW built over (or with) an arena: that one exchanges the gradients
     base = model.get_base_model() if hasattr(model, "get_base_model") else model
     if arena is None and optimizer is None and getattr(base, "_unsloth_full_finetuning", False):
-        optimizer = make_optimizer(model)          # ShardedAdamW owns its FullGradBuckets
+        optimizer = make_optimizer(model, max_grad_norm=max_grad_norm)          # ShardedAdamW owns its FullGradBuckets
         arena = optimizer.arena
     if arena is None and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
         arena = LoRAGradArena(model)               # BEFORE the optimizer: FlatAdamW adopts it instead of creating a second one
     if optimizer is None:
-        optimizer = make_optimizer(model, arena=arena)
+        optimizer = make_optimizer(model, arena=arena, max_grad_norm=max_grad_norm)
     losses, t0 = [], time.time()
     for step, batch in enumerate(batches):
         if max_steps is not None and step >= max_steps:
             break
         losses.append(training_step(model, batch, optimizer, arena))
         if log_every and (step + 1) % log_every == 0:
-            print(f"step {step + 1}: loss {float(losses[-1]):.4f}  ({time.time() - t0:.1f}s)", flush=True)
+            gn = getattr(optimizer, "last_grad_norm", None)          # (read after the loss: the print's one sync covers both)
+            norm = "" if gn is None else f"  grad_norm {float(gn):.4f}"
+            print(f"step {step + 1}: loss {float(losses[-1]):.4f}{norm}  ({time.time() - t0:.1f}s)", flush=True)
     return [float(l) for l in losses]
 
 
