@@ -253,6 +253,28 @@ int uamd_logprob_entropy_forward(const void* logits, int64_t logits_row_stride, 
                                  float logit_softcapping, float logit_scaling, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Full-vocabulary distillation loss between student and teacher logits, both [n_rows, vocab_size] in `dtype`, unit
+ * column stride, any row stride >= vocab_size (TRL GKDTrainer.generalized_jsd_loss; no kernel in the reference).
+ * With p = softmax(teacher / temperature), q = softmax(student / temperature), per row:
+ *   beta == 0: sum p (log p - log q);  beta == 1: sum q (log q - log p);
+ *   otherwise: beta KL(p || m) + (1 - beta) KL(q || m), m = beta p + (1 - beta) q.
+ *   forward : loss, lse_student, lse_teacher (logsumexp of the scaled rows) and kl_student (reverse KL: the loss; JSD:
+ *             KL(q || m); what the backward needs beside the two lse), fp32 [n_rows]; one launch, no atomics.
+ *   backward: student <- dloss[row] * d loss[row] / d student, IN PLACE; the teacher gets no gradient.
+ * labels (int64 when labels_i64 != 0, else int32; NULL: none): a row whose entry is -100 has loss 0 and a zero gradient row.
+ * beta in [0, 1], temperature > 0, else UAMD_ERR_ARG.
+ */
+int uamd_distill_loss_forward(const void* student, int64_t student_row_stride, const void* teacher,
+                              int64_t teacher_row_stride, float* loss, float* lse_student, float* lse_teacher,
+                              float* kl_student, const void* labels, int labels_i64, int64_t n_rows, int vocab_size,
+                              float beta, float temperature, int dtype, void* stream);
+int uamd_distill_loss_backward(void* student, int64_t student_row_stride, const void* teacher,
+                               int64_t teacher_row_stride, const float* dloss, int64_t dloss_stride,
+                               const float* lse_student, const float* lse_teacher, const float* kl_student,
+                               const void* labels, int labels_i64, int64_t n_rows, int vocab_size, float beta,
+                               float temperature, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * bitsandbytes-compatible symbols (exact bitsandbytes signatures; bound by the reference at
  * unsloth/kernels/utils.py:272-275 and called at :650-675).  `code` may be NULL for the *_nf4
  * functions (built-in NF4 table), as the reference passes NULL (:663-664).

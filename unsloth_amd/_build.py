@@ -24,6 +24,7 @@ SOURCES = [
     "qk_norm_rope.hip",
     "glu.hip",
     "cross_entropy_loss.hip",
+    "distill_loss.hip",
     "nf4.hip",
     "gemm.hip",
     "gemm256.hip",

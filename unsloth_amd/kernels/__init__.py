@@ -5,6 +5,8 @@ from .cross_entropy_loss import (
     patch_loss_functions,
     unsloth_fused_ce_loss,
     Fast_CrossEntropyLoss,
+    fast_generalized_jsd_loss,
+    Fast_DistillationLoss,
 )
 from .rms_layernorm import (
     fast_rms_layernorm,

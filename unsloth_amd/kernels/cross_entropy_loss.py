@@ -6,6 +6,9 @@ the fused linear + cross-entropy entry point the reference imports from unsloth_
                                         overwrites logits with the gradient and returns that buffer
   Fast_LogProbEntropy                   its sibling for the RL log-prob path: (log-prob, entropy) per row from the same
                                         single pass (uamd_logprob_entropy_forward), same in-place backward
+  Fast_DistillationLoss                 full-vocabulary divergence between student and teacher logits (forward / reverse KL,
+                                        generalized JSD; uamd_distill_loss_{forward,backward}), same in-place backward;
+                                        fast_generalized_jsd_loss = TRL's GKDTrainer.generalized_jsd_loss on it
   fast_cross_entropy_loss   (:421-449)  sum / n_items
   patch_loss_functions      (:459-473)  installs the fast loss into transformers' LOSS_MAPPING
 
@@ -102,6 +105,111 @@ class Fast_LogProbEntropy(torch.autograd.Function):
             dlosses = dlosses.expand(logits.shape[0]).contiguous()
         _ce_backward_(logits, dlosses, lse, index, ctx.logit_softcapping, ctx.logit_scaling)
         return logits, None, None, None
+
+
+def _check_distill_scalars(beta, temperature):
+    beta, temperature = float(beta), float(temperature)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError(f"distillation loss: beta must be in [0, 1], got {beta}")
+    if not 0.0 < temperature < float("inf"):
+        raise ValueError(f"distillation loss: temperature must be positive and finite, got {temperature}")
+    return beta, temperature
+
+
+def _distill_labels(labels, n_rows, device):
+    """None, or the [n_rows] labels as the kernel takes them (int32 or int64, contiguous); only `== -100` is read."""
+    if labels is None:
+        return None
+    labels = labels.reshape(-1).to(device)
+    if labels.dtype not in (torch.int32, torch.int64):
+        labels = labels.to(torch.int64)
+    if labels.shape[0] != n_rows:
+        raise ValueError(f"distillation loss: {labels.shape[0]} labels for {n_rows} rows of logits")
+    return labels.contiguous()
+
+
+def _distill_pair(student2d, teacher2d):
+    if student2d.shape != teacher2d.shape or student2d.dtype != teacher2d.dtype:
+        raise ValueError(f"distillation loss: student {tuple(student2d.shape)} {student2d.dtype} and teacher "
+                         f"{tuple(teacher2d.shape)} {teacher2d.dtype} must agree in shape and dtype")
+
+
+def _distill_forward(student2d, teacher2d, labels, beta, temperature):
+    """(loss, lse_student, lse_teacher, kl_student) per row, fp32 (uamd_distill_loss_forward): one launch over the two
+    [rows, V] logits, unit column stride, any row stride."""
+    _distill_pair(student2d, teacher2d)
+    n_rows, vocab = student2d.shape
+    out = [torch.empty(n_rows, dtype=torch.float32, device=student2d.device) for _ in range(4)]
+    _lib.call("uamd_distill_loss_forward", student2d, _lib.ptr(student2d), student2d.stride(0), _lib.ptr(teacher2d),
+              teacher2d.stride(0), *[_lib.ptr(o) for o in out], _lib.ptr(labels),
+              int(labels is not None and labels.dtype == torch.int64), n_rows, vocab, beta, temperature,
+              _lib.dtype_code(student2d.dtype), _lib.stream_of(student2d))
+    return out
+
+
+def _distill_backward_(student2d, teacher2d, dlosses, lse_student, lse_teacher, kl_student, labels, beta, temperature):
+    """student2d <- dlosses[row] * d loss[row] / d student2d, in place (uamd_distill_loss_backward)."""
+    n_rows, vocab = student2d.shape
+    _lib.call("uamd_distill_loss_backward", student2d, _lib.ptr(student2d), student2d.stride(0), _lib.ptr(teacher2d),
+              teacher2d.stride(0), _lib.ptr(dlosses), dlosses.stride(0), _lib.ptr(lse_student), _lib.ptr(lse_teacher),
+              _lib.ptr(kl_student), _lib.ptr(labels), int(labels is not None and labels.dtype == torch.int64), n_rows, vocab,
+              beta, temperature, _lib.dtype_code(student2d.dtype), _lib.stream_of(student2d))
+    return student2d
+
+
+class Fast_DistillationLoss(torch.autograd.Function):
+    """Per-row divergence between student and teacher logits [rows, V] over the whole vocabulary, fp32 [rows]: forward KL
+    (beta 0), reverse KL (beta 1) or TRL's generalized JSD, both logits divided by `temperature`; 0 where labels == -100. The
+    backward overwrites the saved student logits with their gradient and returns that buffer, as Fast_CrossEntropyLoss does;
+    the teacher gets none."""
+
+    @staticmethod
+    def forward(ctx, student_logits, teacher_logits, labels=None, beta=0.5, temperature=1.0):
+        beta, temperature = _check_distill_scalars(beta, temperature)
+        _lib.require_gpu(student_logits, teacher_logits)
+        if student_logits.stride(1) != 1:
+            student_logits = student_logits.contiguous()
+        if teacher_logits.stride(1) != 1:
+            teacher_logits = teacher_logits.contiguous()
+        labels = _distill_labels(labels, student_logits.shape[0], student_logits.device)
+        losses, lse_s, lse_t, kl_s = _distill_forward(student_logits, teacher_logits, labels, beta, temperature)
+        ctx.save_for_backward(student_logits, teacher_logits, lse_s, lse_t, kl_s, labels)
+        ctx.beta, ctx.temperature = beta, temperature
+        return losses
+
+    @staticmethod
+    def backward(ctx, dlosses):
+        student, teacher, lse_s, lse_t, kl_s, labels = ctx.saved_tensors
+        dlosses = dlosses.to(torch.float32)
+        if dlosses.dim() == 0 or dlosses.stride(0) == 0:
+            dlosses = dlosses.expand(student.shape[0]).contiguous()
+        _distill_backward_(student, teacher, dlosses, lse_s, lse_t, kl_s, labels, ctx.beta, ctx.temperature)
+        return student, None, None, None, None
+
+
+def fast_generalized_jsd_loss(student_logits, teacher_logits, labels=None, beta=0.5, temperature=1.0, reduction="batchmean"):
+    """TRL's GKDTrainer.generalized_jsd_loss on the hand kernels: student / teacher logits [..., V] (same shape and dtype),
+    labels [...] with -100 on the positions to leave out. Reductions as TRL's: "batchmean" sum / number of unmasked
+    positions (sum / student_logits.size(0) without labels), "sum", "mean" (over positions AND vocabulary); "none" returns
+    the per-position divergences [...], already summed over the vocabulary (TRL returns them element by element).
+    The student logits' gradient is written over them in the backward."""
+    beta, temperature = _check_distill_scalars(beta, temperature)
+    if reduction not in ("batchmean", "sum", "mean", "none"):
+        raise ValueError(f"reduction {reduction!r}: batchmean, sum, mean or none")
+    _lib.require_gpu(student_logits, teacher_logits)
+    V = student_logits.shape[-1]
+    lead = student_logits.shape[:-1]
+    losses = Fast_DistillationLoss.apply(student_logits.reshape(-1, V), teacher_logits.reshape(-1, V), labels, beta, temperature)
+    if reduction == "none":
+        return losses.view(lead)
+    total = losses.sum()
+    if reduction == "sum":
+        return total
+    if labels is not None:
+        n = torch.count_nonzero(labels.to(losses.device) != -100)
+    else:
+        n = student_logits.shape[0] if reduction == "batchmean" else losses.shape[0]
+    return total / n if reduction == "batchmean" else total / (n * V)
 
 
 def fast_cross_entropy_loss(logits, labels, logit_softcapping=0, logit_scaling=0, n_items=None):

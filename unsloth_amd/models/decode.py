@@ -41,6 +41,8 @@ A model with per-head q_norm / k_norm (Qwen3): prefill through the fused norm + 
 uamd_qk_norm_rope_kv_append (the prefill's bits for a token's key), the 16-bit cache. The single-launch step, the FP8 cache,
 share_prompt, prompt-lookup and extend rotate inside kernels that know no norm: NotImplementedError before any launch.
 """
+import contextlib
+import gc
 import math
 import os
 
@@ -53,6 +55,24 @@ from ..kernels.swiglu import swiglu_fg_kernel
 from ..kernels.utils import get_lora_parameters_bias, matmul_lora
 
 SPLIT_KEYS = 128
+
+
+@contextlib.contextmanager
+def _capture(graph):
+    """`torch.cuda.graph(graph)` with Python's cyclic collector held off. torch no longer collects before a capture, and a
+    collection that starts INSIDE one (its timing follows the process's allocation count, nothing the engine controls) can
+    reach a dead engine: destroying that engine's captured graphs and releasing their private pool are device calls a global
+    capture does not allow, and the process aborts inside whatever launch the collector interrupted. Dead cycles are collected
+    before the capture begins; the collector is back on when it ends."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 def _base(model):
@@ -646,7 +666,7 @@ class DecodeEngine:
             self._lens.copy_(kv0)
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with _capture(graph):
                 self._step_body()
             setattr(self, g, graph)
             setattr(self, gl, self.logits)       # the graph's static output buffer (prefill() rebinds self.logits)
@@ -747,7 +767,7 @@ class DecodeEngine:
                 t.copy_(v)
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with _capture(graph):
                 self._lookup_body(R, n_max)
             self._graph_l[(R, n_max)] = graph
             for t, v in saved:                  # the capture itself does not execute

@@ -18,8 +18,9 @@ import torch
 
 from .. import _lib
 from ..kernels import utils as _u
-from ..kernels.cross_entropy_loss import (Fast_CrossEntropyLoss, Fast_LogProbEntropy, _ce_backward_, _ce_forward, _dhidden,
-                                          _logits_chunk, _logprob_entropy_forward, _nn_ok, _transposed_weight)
+from ..kernels.cross_entropy_loss import (Fast_CrossEntropyLoss, Fast_LogProbEntropy, _ce_backward_, _ce_forward,
+                                          _check_distill_scalars, _dhidden, _distill_backward_, _distill_forward,
+                                          _distill_labels, _logits_chunk, _logprob_entropy_forward, _nn_ok, _transposed_weight)
 
 
 class _ChunkedLogProbs(torch.autograd.Function):
@@ -118,6 +119,104 @@ def chunked_selective_log_softmax(logits, index, temperature=1.0, chunks=4, retu
         return lp.view(B, L), ent.view(B, L)
     losses = Fast_CrossEntropyLoss.apply(logits.reshape(B * L, V), index.reshape(-1).to(torch.int64), 0, scale)
     return (-losses).view(B, L)
+
+
+class _ChunkedDistillation(torch.autograd.Function):
+    """Per-row divergence between softmax(hidden @ W^T / tau) and the teacher's distribution, in row chunks: the student's
+    (and, from hidden states, the teacher's) chunk of logits through the MFMA GEMM, uamd_distill_loss_forward on the pair,
+    and -- the lm_head being frozen and a row's loss depending on its own row only -- the in-place backward and d(hidden)
+    through the NN GEMM inside the forward, as _ChunkedLogProbs does."""
+
+    @staticmethod
+    def forward(ctx, hidden2d, weight, weight_t, teacher2d, teacher_weight, labels, beta, temperature, chunk_rows):
+        T, H = hidden2d.shape
+        V = weight.shape[0]
+        dev = hidden2d.device
+        out = torch.empty(T, dtype=torch.float32, device=dev)
+        need_grad = hidden2d.requires_grad
+        dh = torch.empty_like(hidden2d) if need_grad else None
+        for r0 in range(0, T, chunk_rows):
+            r1 = min(T, r0 + chunk_rows)
+            chunk = _logits_chunk(r1 - r0, V, hidden2d.dtype, dev)
+            logits = chunk[:, :V]
+            _u._launch_gemm(hidden2d[r0:r1], [_u._group(weight, logits, V, weight.stride(0))], nf4=False)
+            if teacher_weight is None:
+                teacher = teacher2d[r0:r1]                               # the teacher's logits as given
+            else:
+                teacher = _logits_chunk(r1 - r0, V, hidden2d.dtype, dev)[:, :V]
+                _u._launch_gemm(teacher2d[r0:r1], [_u._group(teacher_weight, teacher, V, teacher_weight.stride(0))], nf4=False)
+            lab = labels[r0:r1] if labels is not None else None
+            losses, lse_s, lse_t, kl_s = _distill_forward(logits, teacher, lab, beta, temperature)
+            out[r0:r1] = losses
+            if need_grad:
+                dl = torch.ones(r1 - r0, dtype=torch.float32, device=dev)
+                _distill_backward_(logits, teacher, dl, lse_s, lse_t, kl_s, lab, beta, temperature)      # logits <- d loss / d logits
+                _dhidden(chunk, logits, weight, weight_t, dh[r0:r1])
+        ctx.save_for_backward(dh)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (dh,) = ctx.saved_tensors
+        if dh is None:
+            return (None,) * 9
+        return ((dh.to(torch.float32) * g.to(torch.float32).unsqueeze(1)).to(dh.dtype),) + (None,) * 8
+
+
+def _rows2d(x):
+    x2d = x.reshape(-1, x.shape[-1])
+    return x2d.contiguous() if x2d.stride(1) != 1 or x2d.stride(0) % 8 else x2d
+
+
+def chunked_hidden_states_distillation_loss(student_hidden, teacher_hidden_or_logits, lm_head, teacher_lm_head=None, labels=None,
+                                            beta=0.5, temperature=1.0, chunk_rows=None, reduction="batchmean"):
+    """Generalized-JSD distillation loss (fast_generalized_jsd_loss) from hidden states, without a [T, V] logits tensor of
+    either model. student_hidden [..., H] and lm_head [V, H] (frozen); the teacher as hidden states [..., H_t] with
+    teacher_lm_head [V, H_t], or, with teacher_lm_head None, as logits [..., V] in the student's dtype. labels [...] with
+    -100 on the positions to leave out. Reductions: "batchmean" (sum / number of unmasked positions), "sum", "none"
+    (per-position divergences [...] fp32). Differentiable w.r.t. student_hidden only."""
+    beta, temperature = _check_distill_scalars(beta, temperature)
+    if reduction not in ("batchmean", "sum", "none"):
+        raise ValueError(f"reduction {reduction!r}: batchmean, sum or none")
+    _lib.require_gpu(student_hidden, teacher_hidden_or_logits, lm_head, teacher_lm_head)
+    if lm_head.requires_grad:
+        raise NotImplementedError("frozen lm_head only (LoRA fine-tuning keeps it frozen)")
+    lead = student_hidden.shape[:-1]
+    h2d = _rows2d(student_hidden)
+    T, H = h2d.shape
+    W = lm_head.detach()
+    if W.dtype != h2d.dtype:
+        W = W.to(h2d.dtype)
+    V = W.shape[0]
+    if teacher_lm_head is None:
+        t2d = teacher_hidden_or_logits.detach().reshape(-1, teacher_hidden_or_logits.shape[-1])
+        if t2d.stride(1) != 1:
+            t2d = t2d.contiguous()
+        Wt_teacher = None
+        if t2d.shape != (T, V) or t2d.dtype != h2d.dtype:
+            raise ValueError(f"teacher logits {tuple(t2d.shape)} {t2d.dtype}: expected {(T, V)} {h2d.dtype}")
+    else:
+        t2d = _rows2d(teacher_hidden_or_logits.detach())
+        Wt_teacher = teacher_lm_head.detach()
+        if Wt_teacher.dtype != h2d.dtype:
+            Wt_teacher = Wt_teacher.to(h2d.dtype)
+        if t2d.dtype != h2d.dtype:
+            t2d = t2d.to(h2d.dtype)
+        if t2d.shape[0] != T or Wt_teacher.shape != (V, t2d.shape[1]):
+            raise ValueError(f"teacher hidden {tuple(t2d.shape)} / lm_head {tuple(Wt_teacher.shape)}: expected {T} rows, vocabulary {V}")
+    if chunk_rows is None:
+        chunk_rows = min(2048, max(256, -(-T // 4)))          # two transient chunks: <= 1 GB of logits at vocab 128k
+    chunk_rows = max(1, int(chunk_rows))
+    nn = _nn_ok(min(chunk_rows, T), V, H) and W.stride(1) == 1 and W.stride(0) % 8 == 0
+    Wt = None if nn else _transposed_weight(W, lm_head if W.dtype == lm_head.dtype else None)
+    lab = _distill_labels(labels, T, h2d.device)
+    losses = _ChunkedDistillation.apply(h2d, W, Wt, t2d, Wt_teacher, lab, beta, temperature, chunk_rows)
+    if reduction == "none":
+        return losses.view(lead)
+    if reduction == "sum":
+        return losses.sum()
+    n = torch.count_nonzero(lab != -100) if lab is not None else T
+    return losses.sum() / n
 
 
 # ======================================================================================================================
