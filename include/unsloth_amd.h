@@ -892,6 +892,36 @@ int uamd_embedding_bwd(const int64_t* sorted_ids, const int64_t* order, int64_t 
                        int64_t ld_dw, int64_t V, int H, int64_t padding_idx, int mode, float* ws, int64_t ws_elems, int dtype,
                        void* stream);
 
+/* Mixture-of-experts expert block (csrc/moe.hip), dtype bf16 / fp16. T tokens, k experts per token, S = T k slots < 2^31, slot
+ * f = t k + j is the flat index into top_k_index [T, k]; E <= 256 experts. A slot whose id is outside [0, E) belongs to no
+ * expert: nothing is read or written through it.
+ * uamd_moe_plan: routing metadata, all on the device, deterministic. top_k_index: DEVICE int64 (idx64 != 0) or int32 [S].
+ *   offsets [E + 1]: the segment of each expert in sorted order; rows [S]: sorted position -> slot f, stable (ascending f inside
+ *   an expert; positions past offsets[E] are not written); tiles [1 + 2 uamd_moe_max_tiles(S, E)]: tiles[0] = live row tiles,
+ *   then (expert, first sorted row) per tile of 128 rows -- a tile never straddles two experts.
+ *   ws: uamd_moe_plan_workspace(S, E) int32. */
+int64_t uamd_moe_max_tiles(int64_t S, int E);
+int64_t uamd_moe_plan_workspace(int64_t S, int E);
+int uamd_moe_plan(const void* top_k_index, int idx64, int64_t S, int E, int32_t* offsets, int32_t* rows, int32_t* tiles,
+                  int32_t* ws, int64_t ws_elems, void* stream);
+/* uamd_moe_gemm: one launch; for every sorted row s of every expert e (from a plan):
+ *     C[c_row(s), 0:N] (+)= row_scale(s) * (A[a_row(s), 0:K] @ op(W_e)),   W_e = W + e * expert_stride
+ *   form_nn == 0: W_e is [N, K], K contiguous (op = transpose); form_nn != 0: W_e is [K, N], N contiguous. ldw = its row stride.
+ *   a_row(s) = rows[s] / topk (gather_a) or s; c_row(s) = rows[s] (scatter_c) or s; row_scale: fp32 indexed by rows[s], NULL = 1,
+ *   applied to the fp32 accumulators; accumulate != 0 adds the existing C; one rounding to the activation dtype.
+ *   The bits of an output row depend on its input row and its expert's weights alone.
+ *   K % 64 == 0 and N % 8 == 0 (else UAMD_ERR_ARG); strides multiples of 8 elements, pointers 16-byte aligned (UAMD_ERR_ALIGN). */
+int uamd_moe_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t expert_stride, void* C, int64_t ldc,
+                  const int32_t* offsets, const int32_t* rows, const int32_t* tiles, const float* row_scale, int64_t S, int E,
+                  int N, int K, int topk, int form_nn, int gather_a, int scatter_c, int accumulate, int dtype, void* stream);
+/* uamd_moe_combine_fwd: out[t, :] = sum_j w[t k + j] * Y[t k + j, :], fp32 in j order, one rounding; w: fp32 [S] or NULL (unit
+ * weights). uamd_moe_combine_bwd: dw[t k + j] = <dOut[t, :], Y[t k + j, :]> in fp32 (0 for a slot that is skipped).
+ * top_k_index (NULL: none) makes both skip the slots whose id is outside [0, E). H % 8 == 0. */
+int uamd_moe_combine_fwd(const void* Y, int64_t ldy, const float* w, const void* top_k_index, int idx64, int E, void* out,
+                         int64_t ld_out, int64_t T, int k, int H, int dtype, void* stream);
+int uamd_moe_combine_bwd(const void* dOut, int64_t ld_dout, const void* Y, int64_t ldy, const void* top_k_index, int idx64, int E,
+                         float* dw, int64_t T, int k, int H, int dtype, void* stream);
+
 /* debug: (lane,reg) -> (row,col) map of v_mfma_f32_16x16x32_bf16; out = float[2][64][4] */
 int uamd_debug_mfma_probe(float* out, void* stream);
 

@@ -36,6 +36,7 @@ SOURCES = [
     "adamw.hip",
     "grad_norm.hip",
     "embedding.hip",
+    "moe.hip",
 ]
 
 

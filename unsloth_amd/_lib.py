@@ -229,6 +229,15 @@ SIGNATURES = {
     "uamd_embedding_bwd_workspace": (c_int64, [c_int64, c_int]),
     "uamd_embedding_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int64,
                                    c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "uamd_moe_max_tiles": (c_int64, [c_int64, c_int]),
+    "uamd_moe_plan_workspace": (c_int64, [c_int64, c_int]),
+    "uamd_moe_plan": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "uamd_moe_gemm": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "uamd_moe_combine_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int,
+                                     c_int, c_int, c_void_p]),
+    "uamd_moe_combine_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int64, c_int,
+                                     c_int, c_int, c_void_p]),
     "uamd_debug_mfma_probe": (c_int, [c_void_p, c_void_p]),
 }
 

@@ -27,6 +27,7 @@ from .rope_embedding import (
 )
 from .embedding import fast_embedding, Fast_Embedding
 from .swiglu import swiglu_fg_kernel, swiglu_DWf_DW_dfg_kernel
+from .moe import moe_plan, moe_grouped_gemm, moe_experts_forward, patch_moe_experts, Fast_MoeExperts
 from .geglu import (
     geglu_exact_forward_kernel,
     geglu_exact_backward_kernel,
